@@ -2,7 +2,7 @@
 // normal priority unless argv says otherwise): (a) overlap: a 200-us one-block spin kernel on each of the two streams at
 // once -- 200 us if they run concurrently, 400 if serialised; (b) ping-pong: 50 rounds of { main: short kernel, record;
 // side: wait, short kernel, record; main: wait } -- microseconds per round trip.
-// hipcc -O2 --offload-arch=gfx950 tools/micro/queue_probe.hip -o tools/bin/queue_probe ; GPU_MAX_HW_QUEUES=8 tools/bin/queue_probe 12
+// hipcc -O2 --offload-arch=gfx950 tools/micro/queue_probe.hip -o tools/bin/queue_probe ; tools/bin/queue_probe 12
 #include <hip/hip_runtime.h>
 #include <chrono>
 #include <cstdio>
