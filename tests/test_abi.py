@@ -65,3 +65,42 @@ def test_exchange_entry_points_validate_and_resolve_rccl_without_a_gpu():
     assert lib.disyolo_cast_f32_bf16(None, buf, 4, None) == -1
     assert lib.disyolo_cmdlist_count(None, 0, 0) == -1
     assert lib.disyolo_cmdlist_lane_stream(None, 1) is None
+
+
+def test_loss_entry_points_reject_unsupported_arguments_before_any_launch():
+    """csrc/loss.hip: each unsupported argument of the three loss kernels comes back as an error code with
+    disyolo_last_error set, before anything touches a device (the pointers below are host buffers that a launch
+    would fault on)"""
+    lib = L.load()
+    buf = ctypes.create_string_buffer(1 << 16)
+    p = ctypes.cast(buf, ctypes.c_void_p)
+    three = (ctypes.c_void_p * 3)(p, p, p)
+    anchors = (ctypes.c_float * 18)(*([32.0] * 18))
+    scales = (ctypes.c_float * 4)(2.0, 1.0, 1.0, 1.0)
+    B, S = 2, 64
+    need = lib.disyolo_yolo_loss_workspace(B, S, 3)
+    assert 0 < need <= len(buf)
+
+    def yolo(max_boxes=20, S=S, num_class=3, ws_bytes=len(buf)):
+        return lib.disyolo_yolo_loss(three, three, p, max_boxes, B, S, num_class, anchors, 0.5, scales, three, p, p,
+                                     ws_bytes, None)
+
+    assert yolo(max_boxes=65) == -1 and b"max_boxes" in lib.disyolo_last_error()
+    assert yolo(max_boxes=0) == -1 and b"max_boxes" in lib.disyolo_last_error()
+    assert yolo(num_class=6) == -1 and b"bad sizes" in lib.disyolo_last_error()      # 3 * (5 + 6) > 32 padded channels
+    assert yolo(num_class=0) == -1 and b"bad sizes" in lib.disyolo_last_error()
+    assert yolo(S=80) == -1 and b"bad sizes" in lib.disyolo_last_error()             # not a multiple of 32
+    assert yolo(ws_bytes=need - 1) == -2 and b"workspace" in lib.disyolo_last_error()   # DISYOLO_E_WORKSPACE
+
+    def rois(n_det, n_gt):
+        return lib.disyolo_mask_rois(p, 30, p, 20, p, p, B, S // 2, n_det, n_gt, 0.5, p, p, None)
+
+    assert rois(9, 8) == -1 and b"n_det + n_gt" in lib.disyolo_last_error()           # 17 > DISYOLO_ROI_MAX
+    assert rois(-1, 3) == -1
+
+    def psroi(k):
+        return lib.disyolo_psroi_loss(p, p, 20, p, p, B, S // 2, k, 5.0, p, p, p, len(buf), None)
+
+    assert lib.disyolo_psroi_loss_workspace(B, S // 2) <= len(buf)
+    for k in (2, 4):
+        assert psroi(k) == -1 and b"k = 3" in lib.disyolo_last_error()

@@ -258,27 +258,30 @@ def test_assemble_without_detections_keeps_nothing(dev):
     assert not keep.any() and np.ndim(wm[0]) == 0 and wm[0] == 0.0       # scalar 0.0 (:933)
 
 
-def run_mask_loss(dev, det, tb, tm, score, perms=None):
+def run_mask_loss(dev, det, tb, tm, score, perms=None, sm=SM, fill=0.0):
+    """mask_rois + psroi_loss on a score map of sm x sm (GT masks tm at 2 sm); the RoI table, the count and the
+    dscore rows start out as ``fill`` (int32 -1 for the table, bf16 ``fill`` for dscore)"""
     B = det.shape[0]
     G = cfg.MAX_BOX_PER_IMAGE
-    rois = torch.zeros(B, L.ROI_MAX, L.ROI_W, dtype=torch.int32, device=dev)
-    cnt = torch.zeros(B, dtype=torch.int32, device=dev)
+    ifill = 0 if fill == 0.0 else -1
+    rois = torch.full((B, L.ROI_MAX, L.ROI_W), ifill, dtype=torch.int32, device=dev)
+    cnt = torch.full((B,), ifill, dtype=torch.int32, device=dev)
     pd = torch.arange(30, dtype=torch.int32, device=dev).repeat(B, 1).contiguous()
     pg = torch.arange(G, dtype=torch.int32, device=dev).repeat(B, 1).contiguous()
     if perms is not None:
         pd = torch.as_tensor(np.stack([p[0] for p in perms]), device=dev).int().contiguous()
         pg = torch.as_tensor(np.stack([p[1] for p in perms]), device=dev).int().contiguous()
-    L.mask_rois(torch.as_tensor(det, device=dev), 30, torch.as_tensor(tb.reshape(B, G, 5), device=dev), G, pd, pg, B, SM,
+    L.mask_rois(torch.as_tensor(det, device=dev), 30, torch.as_tensor(tb.reshape(B, G, 5), device=dev), G, pd, pg, B, sm,
                 cfg.MASK_ROI_DET, cfg.MASK_ROI_GT, cfg.MASK_ROI_IOU, rois, cnt)
-    dscore = torch.zeros(B, SM, SM, L.GRAD_LD, dtype=torch.bfloat16, device=dev)
-    loss = torch.zeros(1, device=dev)
-    L.psroi_loss(score.to(dev), torch.as_tensor(tm, device=dev).to(torch.uint8).contiguous(), G, rois, cnt, B, SM, 3,
+    dscore = torch.full((B, sm, sm, L.GRAD_LD), fill, dtype=torch.bfloat16, device=dev)
+    loss = torch.full((1,), fill, device=dev)
+    L.psroi_loss(score.to(dev), torch.as_tensor(tm, device=dev).to(torch.uint8).contiguous(), G, rois, cnt, B, sm, 3,
                  cfg.MASK_SCALE, dscore, loss, L.Workspace(dev))
     torch.cuda.synchronize()
     return rois.cpu().numpy(), cnt.cpu().numpy(), float(loss.cpu()[0]), dscore.float().cpu()
 
 
-def expected_rois(det, tb, perms=None):
+def expected_rois(det, tb, perms=None, sm=SM):
     """the RoI table the kernel must produce, from the oracle's selection + bin edges"""
     out = []
     for i in range(det.shape[0]):
@@ -286,8 +289,8 @@ def expected_rois(det, tb, perms=None):
         pos, assign, gt_rows = O.select_mask_rois(det[i], tb[i, 0, 0, 0], pd, pg)
         rows = []
         for r in range(len(pos)):
-            px = np.round(pos[r] * np.float32(SM))
-            area = int((O.channel_index_map(px, SM) >= 0).sum())
+            px = np.round(pos[r] * np.float32(sm))
+            area = int((O.channel_index_map(px, sm) >= 0).sum())
             rows.append(O.kmask_edges(px[0], px[2]) + O.kmask_edges(px[1], px[3]) + [int(gt_rows[assign[r]]), area, 1, 0])
         out.append(rows)
     return out
