@@ -4,8 +4,9 @@
 //   residual block 1   act3 = leaky(bn3(conv1x1(act2)))           64 -> 32     yolo/yolo3_net_pos.py:169-176
 //     (post 0)         act4 = leaky(bn4(conv3x3(act3))) + act2    32 -> 64
 //   mask head          act80 = leaky(bn(conv1x1([act4, up2(act79)])))   96 -> 32   yolo/yolo3_net_pos.py:404-412
-//     (post 1)         act81 = leaky(bn(conv3x3(act80)))                32 -> 64
-//                      out   = conv1x1(act81) + bias                    64 -> 9 (k_map^2 position-sensitive score maps), f32
+//     (post 1, 2, 3)   act81 = leaky(bn(conv3x3(act80)))                32 -> 64
+//                      out   = conv1x1(act81) + bias                    64 -> 9, 25, 49 (k_map^2 position-sensitive score
+//                                                                        maps of k_map = 3, 5, 7), f32
 //
 // Unfused, the 32- and 64-channel intermediates of these chains are written and read back at 288^2: at B = 32 the
 // residual block moves 1.36 GB for 0.68 GB of input + output (97 + 175 us), the mask head 1.24 GB for 0.43 GB
@@ -23,7 +24,10 @@
 //   post 0   folded BN + leaky + the residual (the centre of the input tile, still in LDS), bf16 rows leave through a
 //            per-wave staging tile as 64-byte half lines;
 //   post 1   folded BN + leaky -> bf16 tile [128][64] in LDS -> 1x1 conv 64 -> 9 on the matrix cores (weights padded to 16
-//            rows, 2 MFMAs per 16 pixels) + bias, f32 [pixels][9] straight from the accumulators.
+//            rows, 2 MFMAs per 16 pixels) + bias, f32 [pixels][9] straight from the accumulators.  The 25- and 49-output
+//            heads (posts 2, 3) run 2 and 4 such 16-row groups; their weights are read per tile from global memory (8 KB,
+//            cache-resident) one group at a time: the 9-output kernel already uses all 256 VGPRs its occupancy allows, and
+//            the extra 36 registers of 4 resident groups would spill (as does the unrolled group loop: 20 B / lane at 49).
 #include <utility>
 #include "common.h"
 #include "runtime.h"
@@ -41,7 +45,6 @@ constexpr int FPW = NTF / NW;
 constexpr int AP = 80;                              // bytes per pixel of the intermediate tile
 constexpr int SROW = 80;                            // staging: 16 pixels x (64 B + pad)
 constexpr int TP = 144;                             // post 1: bytes per pixel of the 64-channel tile
-constexpr int NOUT = 9;
 static_assert(NTF % NW == 0, "fragments must divide over the waves");
 
 template <int KIN>
@@ -65,16 +68,18 @@ struct BParams {
   const bf16* wB;         // packed [64][9 * 32]
   const float* scB;
   const float* shB;
-  const bf16* wC;         // post 1: packed [9][64]
+  const bf16* wC;         // post 1 / 2 / 3: packed [NOUT][64]
   const float* biasC;
-  void* y;                // post 0: bf16 [B][H][W][64]; post 1: f32 [B][H][W][9]
+  void* y;                // post 0: bf16 [B][H][W][64]; post 1 / 2 / 3: f32 [B][H][W][NOUT]
   int B, H, W, C0, C1, tilesY, tilesX, tiles;
   int gb, gy, gx;         // gridDim.x tiles as (images, tile rows, tile columns)
   float alpha;
 };
 
-template <int KIN, int POST>
+// NOUT: outputs of the final 1x1 conv (POST 1 only): 9 with its weights in registers, 25 / 49 streamed per 16-row group
+template <int KIN, int POST, int NOUT = 9>
 __global__ __launch_bounds__(NW * 64, 2) void block32_kernel(BParams p) {
+  constexpr bool WC_REG = NOUT <= 16;
   using C = Cfg<KIN>;
   constexpr int XP = C::XP, CPP = C::CPP, IPT = C::IPT;
   constexpr unsigned X_OFF = 0, A_OFF = C::X_BYTES, DUMMY_OFF = A_OFF + C::A_BYTES, BN_OFF = DUMMY_OFF + C::DUMMY_BYTES,
@@ -111,7 +116,7 @@ __global__ __launch_bounds__(NW * 64, 2) void block32_kernel(BParams p) {
   // post 1: the 64 -> 9 weights, rows 9..15 zero
   bf16x8 wCr[2];
   f32x4 biasC = {0.f, 0.f, 0.f, 0.f};
-  if (POST == 1) {
+  if (POST == 1 && WC_REG) {
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {
       const bf16x8 v = *reinterpret_cast<const bf16x8*>(p.wC + (size_t)(frow < NOUT ? frow : 0) * 64 + ks * 32 + cq * 8);
@@ -330,10 +335,44 @@ __global__ __launch_bounds__(NW * 64, 2) void block32_kernel(BParams p) {
           *reinterpret_cast<uint2*>(stg + ((ph * 4 + g) * 16 + frow) * TP + (hh * 32 + nf * 16 + cq * 4) * 2) = o;
         }
       __syncthreads();
-      // 64 -> 9: this wave's two patch rows
+      // 64 -> NOUT: this wave's two patch rows
       float* const yf = reinterpret_cast<float*>(p.y);
+      if (!WC_REG) {
+        bf16x8 xv[2][2];
 #pragma unroll
-      for (int j = 0; j < 2; ++j) {
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+          for (int ks = 0; ks < 2; ++ks)
+            xv[j][ks] = *reinterpret_cast<const bf16x8*>(stg + ((wave * 2 + j) * 16 + frow) * TP + ks * 64 + cq * 16);
+#pragma unroll 1
+        for (int gi = 0; gi < (NOUT + 15) / 16; ++gi) {
+          // group gi: output channels gi*16 .. gi*16 + 15 (rows beyond NOUT zero)
+          const int oc = gi * 16 + frow;
+          bf16x8 w[2];
+#pragma unroll
+          for (int ks = 0; ks < 2; ++ks) {
+            const bf16x8 v = *reinterpret_cast<const bf16x8*>(p.wC + (size_t)(oc < NOUT ? oc : 0) * 64 + ks * 32 + cq * 8);
+            const bf16x8 z = {};
+            w[ks] = oc < NOUT ? v : z;
+          }
+          f32x4 bias;
+#pragma unroll
+          for (int r = 0; r < 4; ++r) bias[r] = (gi * 16 + cq * 4 + r < NOUT) ? p.biasC[gi * 16 + cq * 4 + r] : 0.f;
+#pragma unroll
+          for (int j = 0; j < 2; ++j) {
+            f32x4 a = bias;
+#pragma unroll
+            for (int ks = 0; ks < 2; ++ks) a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[ks], xv[j][ks], a, 0, 0, 0);
+            const size_t m = ((size_t)b * p.H + ty * PH + wave * 2 + j) * p.W + tx * PW + frow;
+            float* dstp = yf + m * NOUT + gi * 16 + cq * 4;
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+              if (gi * 16 + cq * 4 + r < NOUT) dstp[r] = a[r];
+          }
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < 2 && WC_REG; ++j) {
         const int row = wave * 2 + j;
         f32x4 a = biasC;
 #pragma unroll
@@ -361,18 +400,18 @@ __global__ __launch_bounds__(NW * 64, 2) void block32_kernel(BParams p) {
 }
 
 template <int KIN, int POST>
-constexpr int lds_bytes() {
+constexpr int lds_bytes() {   // (the same for every NOUT)
   using C = Cfg<KIN>;
   return C::X_BYTES + C::A_BYTES + C::DUMMY_BYTES + C::BN_BYTES + (POST == 0 ? NW * 2 * 16 * SROW : PH * PW * TP);
 }
 
-template <int KIN, int POST>
+template <int KIN, int POST, int NOUT = 9>
 int launch_block32(BParams& p, hipStream_t s) {
   constexpr int LDS = lds_bytes<KIN, POST>();
   static_assert(2 * LDS <= 160 * 1024, "two blocks per CU");
   static bool attr_set = false;
   if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&block32_kernel<KIN, POST>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&block32_kernel<KIN, POST, NOUT>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
     attr_set = true;
   }
   static const int ncu = [] {
@@ -386,17 +425,22 @@ int launch_block32(BParams& p, hipStream_t s) {
   p.gb = grid / tpi;
   p.gy = (grid % tpi) / p.tilesX;
   p.gx = grid % p.tilesX;
-  hipLaunchKernelGGL((block32_kernel<KIN, POST>), dim3(grid), dim3(NW * 64), LDS, s, p);
+  hipLaunchKernelGGL((block32_kernel<KIN, POST, NOUT>), dim3(grid), dim3(NW * 64), LDS, s, p);
   DY_CHECK_LAUNCH();
   return DISYOLO_OK;
 }
 
 }  // namespace
 
+// post 1 / 2 / 3: the mask head of a k_map = 3 / 5 / 7 grid (9 / 25 / 49 f32 score maps)
+static int post_nout(int post) { return post == 1 ? 9 : post == 2 ? 25 : post == 3 ? 49 : 0; }
+
 extern "C" int disyolo_block32_fused_ok(int B, int H, int W, int C0, int C1, int post) {
-  const bool shape = (C0 == 64 && C1 == 0 && post == 0) || (C0 == 64 && C1 == 32 && post == 1);
+  const bool shape = (C0 == 64 && C1 == 0 && post == 0) || (C0 == 64 && C1 == 32 && post_nout(post) > 0);
+  // bytes per pixel of the largest tensor: 64 bf16 channels in / out, or the f32 score maps (36 / 100 / 196 B)
+  const int64_t px_bytes = post_nout(post) * 4 > 128 ? post_nout(post) * 4 : 128;
   return (shape && B > 0 && H > 0 && W > 0 && H % PH == 0 && W % PW == 0 &&
-          (int64_t)B * H * W * 128 < (1LL << 31)) ? 1 : 0;   // bytes of the largest tensor (64 bf16 channels in / out; the f32 score maps are 36 B / pixel)
+          (int64_t)B * H * W * px_bytes < (1LL << 31)) ? 1 : 0;
 }
 
 extern "C" int disyolo_block32_fused_fwd(const void* x0, const void* x1, int C0, int C1, const void* wA, const float* scaleA,
@@ -405,9 +449,9 @@ extern "C" int disyolo_block32_fused_fwd(const void* x0, const void* x1, int C0,
                                          void* stream) {
   DY_REQUIRE(x0 && wA && scaleA && shiftA && wB && scaleB && shiftB && y, "block32_fused: null pointer");
   DY_REQUIRE(disyolo_block32_fused_ok(B, H, W, C0, C1, post) == 1,
-             "block32_fused: covers [64 -> 32 -> 64 + residual] (post 0) and [64 + up(32) -> 32 -> 64 -> 9] (post 1), H %% %d == 0, W %% %d == 0",
+             "block32_fused: covers [64 -> 32 -> 64 + residual] (post 0) and [64 + up(32) -> 32 -> 64 -> 9 / 25 / 49] (post 1 / 2 / 3), H %% %d == 0, W %% %d == 0",
              PH, PW);
-  DY_REQUIRE(post == 0 || (x1 && wC && biasC), "block32_fused: post 1 needs x1, wC, biasC");
+  DY_REQUIRE(post == 0 || (x1 && wC && biasC), "block32_fused: post %d needs x1, wC, biasC", post);
   DY_RECORD_OR_RUN([=](void* s) {
     return disyolo_block32_fused_fwd(x0, x1, C0, C1, wA, scaleA, shiftA, wB, scaleB, shiftB, post, wC, biasC, y, B, H, W, alpha, s);
   });
@@ -419,5 +463,11 @@ extern "C" int disyolo_block32_fused_fwd(const void* x0, const void* x1, int C0,
   p.B = B; p.H = H; p.W = W; p.C0 = C0; p.C1 = C1;
   p.tilesY = H / PH; p.tilesX = W / PW; p.tiles = B * p.tilesY * p.tilesX;
   p.alpha = alpha;
-  return post == 0 ? launch_block32<64, 0>(p, (hipStream_t)stream) : launch_block32<96, 1>(p, (hipStream_t)stream);
+  hipStream_t st = (hipStream_t)stream;
+  switch (post) {
+    case 0: return launch_block32<64, 0>(p, st);
+    case 1: return launch_block32<96, 1>(p, st);
+    case 2: return launch_block32<96, 1, 25>(p, st);
+    default: return launch_block32<96, 1, 49>(p, st);
+  }
 }

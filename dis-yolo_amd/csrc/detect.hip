@@ -364,18 +364,20 @@ __global__ __launch_bounds__(64) void nms_merge_kernel(const float4* boxes, cons
   if (tid == 0) det_count[b] = nk < max_det ? nk : max_det;
 }
 
-// bin edges of assemble_kmask_from_box (yolo/yolo3_net_pos.py:804-813) for k = 3:
-// [int(lo), rint(lo + sub), rint(lo + 2*sub), int(hi)], sub = (hi - lo)/3, f32 math,
+// bin edges of assemble_kmask_from_box (yolo/yolo3_net_pos.py:804-813) for a k x k grid:
+// [int(lo), rint(lo + j*sub) for j = 1..k-1, int(hi)], sub = (hi - lo)/k, f32 math,
 // rintf = round-half-to-even like tf.round.
-__device__ __forceinline__ void bin_edges3(float lo, float hi, int e[4]) {
-  const float sub = (hi - lo) / 3.f;
+template <int K>
+__device__ __forceinline__ void bin_edges(float lo, float hi, int e[K + 1]) {
+  const float sub = (hi - lo) / (float)K;
   e[0] = (int)lo;
-  e[1] = (int)rintf(lo + sub);
-  e[2] = (int)rintf(lo + 2.f * sub);
-  e[3] = (int)hi;
+#pragma unroll
+  for (int j = 1; j < K; ++j) e[j] = (int)rintf(lo + (float)j * sub);
+  e[K] = (int)hi;
 }
 
-// masks[b,r,y,x] = sigmoid(score[b,y,x,bin(y,x)]) inside the box, 0.5 outside (:925-928)
+// masks[b,r,y,x] = sigmoid(score[b,y,x,bin(y,x)]) inside the box, 0.5 outside (:925-928); score rows have k*k channels
+template <int K>
 __global__ __launch_bounds__(256) void psroi_assemble_kernel(const float* score, const float* det, int B, int max_det,
                                                              int Sm, float* masks, int* keep) {
   const int r = blockIdx.y, b = blockIdx.z;
@@ -384,21 +386,25 @@ __global__ __launch_bounds__(256) void psroi_assemble_kernel(const float* score,
   const float y1 = rintf(d[0] * sz), x1 = rintf(d[1] * sz), y2 = rintf(d[2] * sz), x2 = rintf(d[3] * sz);
   const bool kp = (y2 - y1) > 0.f && (x2 - x1) > 0.f;
   if (blockIdx.x == 0 && threadIdx.x == 0) keep[b * max_det + r] = kp ? 1 : 0;
-  int gy[4], gx[4];
-  bin_edges3(y1, y2, gy);
-  bin_edges3(x1, x2, gx);
+  int gy[K + 1], gx[K + 1];
+  bin_edges<K>(y1, y2, gy);
+  bin_edges<K>(x1, x2, gx);
   const int npx = Sm * Sm;
   float* out = masks + ((size_t)b * max_det + r) * npx;
-  const float* sc = score + (size_t)b * npx * 9;
+  const float* sc = score + (size_t)b * npx * (K * K);
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < npx; i += gridDim.x * blockDim.x) {
     float v = 0.f;
     if (kp) {
       const int y = i / Sm, x = i - y * Sm;
       float logit = 0.f;
-      if (y >= gy[0] && y < gy[3] && x >= gx[0] && x < gx[3]) {
-        const int by = (y >= gy[1]) + (y >= gy[2]);
-        const int bx = (x >= gx[1]) + (x >= gx[2]);
-        logit = sc[(size_t)i * 9 + by * 3 + bx];
+      if (y >= gy[0] && y < gy[K] && x >= gx[0] && x < gx[K]) {
+        int by = 0, bx = 0;
+#pragma unroll
+        for (int j = 1; j < K; ++j) {
+          by += y >= gy[j];
+          bx += x >= gx[j];
+        }
+        logit = sc[(size_t)i * (K * K) + by * K + bx];
       }
       v = 1.f / (1.f + expf(-logit));
     }
@@ -575,13 +581,14 @@ extern "C" int disyolo_detect(const float* logits3, const float* logits2, const 
 extern "C" int disyolo_psroi_assemble(const float* score, const float* detections, int B, int max_det, int map_size,
                                       int k, float* masks, int32_t* keep, void* stream) {
   DY_REQUIRE(score && detections && masks && keep && B > 0 && max_det > 0 && map_size > 0, "psroi_assemble: bad args");
-  DY_REQUIRE(k == 3, "psroi_assemble: only k = 3 (the reference's active branch, yolo/yolo3_net_pos.py:894-897)");
+  DY_REQUIRE(k == 3 || k == 5 || k == 7, "psroi_assemble: k must be one of k = 3, 5, 7 (got %d)", k);
   DY_RECORD_OR_RUN([=](void* s) { return disyolo_psroi_assemble(score, detections, B, max_det, map_size, k, masks, keep, s); });
   const int npx = map_size * map_size;
   int gx = ceil_div(npx, 256 * 4);
   if (gx < 1) gx = 1;
-  hipLaunchKernelGGL(psroi_assemble_kernel, dim3(gx, max_det, B), dim3(256), 0, (hipStream_t)stream, score, detections,
-                     B, max_det, map_size, masks, keep);
+  auto kern = k == 3 ? psroi_assemble_kernel<3> : k == 5 ? psroi_assemble_kernel<5> : psroi_assemble_kernel<7>;
+  hipLaunchKernelGGL(kern, dim3(gx, max_det, B), dim3(256), 0, (hipStream_t)stream, score, detections, B, max_det, map_size,
+                     masks, keep);
   DY_CHECK_LAUNCH();
   return DISYOLO_OK;
 }

@@ -6,8 +6,8 @@
 // per image; here one thread owns one score-map pixel and walks the (<=10) RoIs.
 //
 // Gradients wrt head logits / score maps are written as bf16 rows padded to 32 channels
-// (zeros beyond the real channels) so they feed the MFMA data/weight-gradient convs
-// directly.  Scalar losses use per-block partials + a fixed-order final sum.
+// (64 for the 49 score maps of a 7 x 7 grid; zeros beyond the real channels) so they feed
+// the MFMA data/weight-gradient convs directly.  Scalar losses use per-block partials + a fixed-order final sum.
 #include <array>
 #include "common.h"
 #include "runtime.h"
@@ -207,21 +207,29 @@ __global__ __launch_bounds__(64) void shuffle_perm_kernel(int* perm_a, int na, i
 }
 
 // ---- mask-loss RoI selection (yolo/yolo3_net_pos.py:757-796, 842) ------------------
+// An RoI row of a k x k grid holds roi_w(k) = 2 (k + 1) + 4 int32 words: gy0..gyk, gx0..gxk, gt_row, area, valid, 0
+// (12 words at k = 3).  The grids of the reference's list k = 3, 5, 7 are separate template instances.
 constexpr int ROI_MAX = 16;
-constexpr int ROI_W = 12;  // gy0..3, gx0..3, gt_row, area, valid, pad
-__device__ __forceinline__ void bin_edges3(float lo, float hi, int e[4]) {
-  const float sub = (hi - lo) / 3.f;
+constexpr int roi_w(int k) { return 2 * (k + 1) + 4; }
+constexpr int dscore_ld(int k) { return (k * k + 31) / 32 * 32; }   // channel pitch of dscore: conv82's cout_pad
+// bin edges of assemble_kmask_from_box (:804-813): [int(lo), rint(lo + j*sub) for j = 1..k-1, int(hi)], sub = (hi - lo)/k,
+// f32 math (this file is compiled without contraction), rintf = round-half-to-even like tf.round
+template <int K>
+__device__ __forceinline__ void bin_edges(float lo, float hi, int e[K + 1]) {
+  const float sub = (hi - lo) / (float)K;
   e[0] = (int)lo;
-  e[1] = (int)rintf(lo + sub);
-  e[2] = (int)rintf(lo + 2.f * sub);
-  e[3] = (int)hi;
+#pragma unroll
+  for (int j = 1; j < K; ++j) e[j] = (int)rintf(lo + (float)j * sub);
+  e[K] = (int)hi;
 }
 // One 64-thread block per image: the image's detections, ground-truth boxes and permutations are staged in
 // LDS by all lanes, then lane 0 runs the (inherently sequential, order-defining) selection on them -- the
 // single-thread version spent 40 us in dependent global loads.
+template <int K>
 __global__ __launch_bounds__(64) void mask_rois_kernel(const float* det_g, int max_det, const float* true_boxes_g, int G,
                                                        const int* perm_det_g, const int* perm_gt_g, int B, int Sm, int n_det,
                                                        int n_gt, float iou_thr, int* rois, int* roi_count) {
+  constexpr int RW = roi_w(K);
   __shared__ float s_det[64 * 6];
   __shared__ float s_tb[64 * 5];
   __shared__ int s_pd[64], s_pg[64];
@@ -267,7 +275,7 @@ __global__ __launch_bounds__(64) void mask_rois_kernel(const float* det_g, int m
     ++nr; ++taken;
   }
   int cnt = 0;
-  int* out = rois + (size_t)b * ROI_MAX * ROI_W;
+  int* out = rois + (size_t)b * ROI_MAX * RW;
   for (int r = 0; r < nr; ++r) {
     float best = -INFINITY;
     int arg = 0;
@@ -289,85 +297,92 @@ __global__ __launch_bounds__(64) void mask_rois_kernel(const float* det_g, int m
       const float sz = (float)Sm;
       const float y1 = rintf(rb[r][0] * sz), x1 = rintf(rb[r][1] * sz);
       const float y2 = rintf(rb[r][2] * sz), x2 = rintf(rb[r][3] * sz);
-      int gy[4], gx[4];
-      bin_edges3(y1, y2, gy);
-      bin_edges3(x1, x2, gx);
-      int* o = out + cnt * ROI_W;
-      for (int k = 0; k < 4; ++k) {
+      int gy[K + 1], gx[K + 1];
+      bin_edges<K>(y1, y2, gy);
+      bin_edges<K>(x1, x2, gx);
+      int* o = out + cnt * RW;
+      for (int k = 0; k <= K; ++k) {
         o[k] = gy[k];
-        o[4 + k] = gx[k];
+        o[K + 1 + k] = gx[k];
       }
-      o[8] = grow[arg];
+      o[2 * K + 2] = grow[arg];
       // mask_object pixel count (:848): sum over the k*k bins, clipped to the map
       int area = 0;
-      for (int by = 0; by < 3; ++by)
-        for (int bx = 0; bx < 3; ++bx) {
+      for (int by = 0; by < K; ++by)
+        for (int bx = 0; bx < K; ++bx) {
           const int hh = min(gy[by + 1], Sm) - max(gy[by], 0), ww = min(gx[bx + 1], Sm) - max(gx[bx], 0);
           if (hh > 0 && ww > 0) area += hh * ww;
         }
-      o[9] = area;
-      o[10] = 1;
-      o[11] = 0;
+      o[2 * K + 3] = area;
+      o[2 * K + 4] = 1;
+      o[2 * K + 5] = 0;
       ++cnt;
     }
   }
   for (int r = cnt; r < ROI_MAX; ++r)
-    for (int k = 0; k < ROI_W; ++k) out[r * ROI_W + k] = 0;
+    for (int k = 0; k < RW; ++k) out[r * RW + k] = 0;
   roi_count[b] = cnt;
 }
 
-// one thread = one score-map pixel; loops the image's positive RoIs
+// one thread = one score-map pixel; loops the image's positive RoIs.  score rows have k*k channels, dscore rows
+// dscore_ld(k) (the pad channels are written as zeros); the k*k gradient accumulators stay in registers.
+template <int K>
 __global__ __launch_bounds__(256) void psroi_loss_kernel(const float* score, const uint8_t* true_masks, int G,
                                                          const int* rois, const int* roi_count, int B, int Sm,
                                                          float mask_scale, bf16* dscore, float* partial) {
-  __shared__ int s_roi[ROI_MAX * ROI_W];
+  constexpr int RW = roi_w(K), KK = K * K, LD = dscore_ld(K);
+  __shared__ int s_roi[ROI_MAX * RW];
   __shared__ float s_red[4][ROI_MAX];
   const int b = blockIdx.y;
   const int cnt = roi_count[b];
-  for (int i = threadIdx.x; i < ROI_MAX * ROI_W; i += 256) s_roi[i] = rois[(size_t)b * ROI_MAX * ROI_W + i];
+  for (int i = threadIdx.x; i < ROI_MAX * RW; i += 256) s_roi[i] = rois[(size_t)b * ROI_MAX * RW + i];
   __syncthreads();
   const int npx = Sm * Sm;
   const int i = blockIdx.x * 256 + threadIdx.x;
-  float g[9];
+  float g[KK];
 #pragma unroll
-  for (int k = 0; k < 9; ++k) g[k] = 0.f;
+  for (int k = 0; k < KK; ++k) g[k] = 0.f;
   float lsum[ROI_MAX];
 #pragma unroll
   for (int r = 0; r < ROI_MAX; ++r) lsum[r] = 0.f;
   if (i < npx && cnt > 0) {
     const int y = i / Sm, x = i - y * Sm;
-    const float* sc = score + ((size_t)b * npx + i) * 9;
+    const float* sc = score + ((size_t)b * npx + i) * KK;
     const int S = 2 * Sm;
     const float coef0 = mask_scale / ((float)B * (float)cnt);
 #pragma unroll
     for (int r = 0; r < ROI_MAX; ++r) {
       if (r < cnt) {
-        const int* o = s_roi + r * ROI_W;
-        if (y >= o[0] && y < o[3] && x >= o[4] && x < o[7]) {
-          const int by = (y >= o[1]) + (y >= o[2]);
-          const int bx = (x >= o[5]) + (x >= o[6]);
-          const int ch = by * 3 + bx;
+        const int* o = s_roi + r * RW;
+        if (y >= o[0] && y < o[K] && x >= o[K + 1] && x < o[2 * K + 1]) {
+          int by = 0, bx = 0;
+#pragma unroll
+          for (int j = 1; j < K; ++j) {
+            by += y >= o[j];
+            bx += x >= o[K + 1 + j];
+          }
+          const int ch = by * K + bx;
           const float logit = sc[ch];
           // GT mask down-sampled by exact 2x legacy bilinear == [::2, ::2] (:773-775)
-          const float gt = true_masks[(((size_t)b * G + o[8]) * S + 2 * y) * S + 2 * x] ? 1.f : 0.f;
-          const float inv_area = 1.f / (float)o[9];
+          const float gt = true_masks[(((size_t)b * G + o[2 * K + 2]) * S + 2 * y) * S + 2 * x] ? 1.f : 0.f;
+          const float inv_area = 1.f / (float)o[2 * K + 3];
           lsum[r] = sigmoid_ce(gt, logit) * inv_area;
           const float dv = (sigmoidf_(logit) - gt) * inv_area * coef0;
 #pragma unroll
-          for (int k = 0; k < 9; ++k) g[k] += (k == ch) ? dv : 0.f;
+          for (int k = 0; k < KK; ++k) g[k] += (k == ch) ? dv : 0.f;
         }
       }
     }
   }
   if (i < npx) {
-    float v[32];
+    uint4* o = reinterpret_cast<uint4*>(dscore + ((size_t)b * npx + i) * LD);
 #pragma unroll
-    for (int k = 0; k < 32; ++k) v[k] = k < 9 ? g[k] : 0.f;
-    uint4* o = reinterpret_cast<uint4*>(dscore + ((size_t)b * npx + i) * DL_LD);
-    o[0] = pack8(v);
-    o[1] = pack8(v + 8);
-    o[2] = pack8(v + 16);
-    o[3] = pack8(v + 24);
+    for (int c = 0; c < LD / 8; ++c) {
+      float v[8];
+#pragma unroll
+      for (int k = 0; k < 8; ++k) v[k] = c * 8 + k < KK ? g[c * 8 + k] : 0.f;
+      o[c] = pack8(v);
+    }
   }
 #pragma unroll
   for (int r = 0; r < ROI_MAX; ++r) {
@@ -384,7 +399,7 @@ __global__ __launch_bounds__(256) void psroi_loss_kernel(const float* score, con
 // per image: mask_scale * mean_r(sum_r);  an RoI whose area is 0 yields 0/0 = NaN like the
 // reference.  One block per image: 16 RoIs x 16 partial-row lanes.
 __global__ __launch_bounds__(256) void psroi_loss_image_kernel(const float* partial, const int* rois,
-                                                               const int* roi_count, int nblk, float mask_scale,
+                                                               const int* roi_count, int nblk, int rw, float mask_scale,
                                                                float* img_loss) {
   __shared__ double sh[16][ROI_MAX];
   const int b = blockIdx.x, r = threadIdx.x % ROI_MAX, l = threadIdx.x / ROI_MAX;
@@ -398,7 +413,7 @@ __global__ __launch_bounds__(256) void psroi_loss_image_kernel(const float* part
     for (int q = 0; q < cnt; ++q) {
       double s = 0.0;
       for (int k = 0; k < 16; ++k) s += sh[k][q];
-      if (rois[((size_t)b * ROI_MAX + q) * ROI_W + 9] == 0) s = NAN;
+      if (rois[((size_t)b * ROI_MAX + q) * rw + rw - 3] == 0) s = NAN;   // the area word
       img += s;
     }
     img_loss[b] = cnt > 0 ? (float)((double)mask_scale * img / (double)cnt) : 0.f;
@@ -488,20 +503,32 @@ extern "C" int disyolo_shuffle_perm(int32_t* perm_det, int n_det, int32_t* perm_
   return DISYOLO_OK;
 }
 
-extern "C" int disyolo_mask_rois(const float* detections, int max_det, const float* true_boxes, int G,
-                                 const int32_t* perm_det, const int32_t* perm_gt, int B, int map_size, int n_det,
-                                 int n_gt, float iou_thresh, int32_t* rois, int32_t* roi_count, void* stream) {
+// the grids of the reference's list (yolo/yolo3_net_pos.py:808-823): "k = 3" stays in every refusal's text
+static bool kmap_supported(int k) { return k == 3 || k == 5 || k == 7; }
+
+extern "C" int disyolo_mask_rois_k(const float* detections, int max_det, const float* true_boxes, int G,
+                                   const int32_t* perm_det, const int32_t* perm_gt, int B, int map_size, int k, int n_det,
+                                   int n_gt, float iou_thresh, int32_t* rois, int32_t* roi_count, void* stream) {
   DY_REQUIRE(detections && true_boxes && rois && roi_count, "mask_rois: null pointer");
+  DY_REQUIRE(kmap_supported(k), "mask_rois: k must be one of k = 3, 5, 7 (got %d)", k);
   DY_REQUIRE(B > 0 && max_det > 0 && max_det <= 64 && G > 0 && G <= 64 && map_size > 0, "mask_rois: bad sizes");
   DY_REQUIRE(n_det >= 0 && n_gt >= 0 && n_det + n_gt <= ROI_MAX, "mask_rois: n_det + n_gt > %d", ROI_MAX);
   DY_RECORD_OR_RUN([=](void* s) {
-    return disyolo_mask_rois(detections, max_det, true_boxes, G, perm_det, perm_gt, B, map_size, n_det, n_gt, iou_thresh,
-                             rois, roi_count, s);
+    return disyolo_mask_rois_k(detections, max_det, true_boxes, G, perm_det, perm_gt, B, map_size, k, n_det, n_gt,
+                               iou_thresh, rois, roi_count, s);
   });
-  hipLaunchKernelGGL(mask_rois_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, detections, max_det,
-                     true_boxes, G, perm_det, perm_gt, B, map_size, n_det, n_gt, iou_thresh, rois, roi_count);
+  auto kern = k == 3 ? mask_rois_kernel<3> : k == 5 ? mask_rois_kernel<5> : mask_rois_kernel<7>;
+  hipLaunchKernelGGL(kern, dim3(B), dim3(64), 0, (hipStream_t)stream, detections, max_det, true_boxes, G, perm_det,
+                     perm_gt, B, map_size, n_det, n_gt, iou_thresh, rois, roi_count);
   DY_CHECK_LAUNCH();
   return DISYOLO_OK;
+}
+
+extern "C" int disyolo_mask_rois(const float* detections, int max_det, const float* true_boxes, int G,
+                                 const int32_t* perm_det, const int32_t* perm_gt, int B, int map_size, int n_det,
+                                 int n_gt, float iou_thresh, int32_t* rois, int32_t* roi_count, void* stream) {
+  return disyolo_mask_rois_k(detections, max_det, true_boxes, G, perm_det, perm_gt, B, map_size, 3, n_det, n_gt,
+                             iou_thresh, rois, roi_count, stream);
 }
 
 extern "C" size_t disyolo_psroi_loss_workspace(int B, int map_size) {
@@ -514,7 +541,7 @@ extern "C" int disyolo_psroi_loss(const float* score, const uint8_t* true_masks,
                                   float* loss, void* workspace, size_t workspace_bytes, void* stream) {
   DY_REQUIRE(score && true_masks && rois && roi_count && dscore && loss, "psroi_loss: null pointer");
   DY_REQUIRE(B > 0 && map_size > 0 && G > 0, "psroi_loss: bad sizes");
-  DY_REQUIRE(k == 3, "psroi_loss: only k = 3 (the reference's active branch, yolo/yolo3_net_pos.py:810-813)");
+  DY_REQUIRE(kmap_supported(k), "psroi_loss: k must be one of k = 3, 5, 7 (got %d)", k);
   if (!workspace || workspace_bytes < disyolo_psroi_loss_workspace(B, map_size)) {
     disyolo_set_error("psroi_loss: workspace too small");
     return DISYOLO_E_WORKSPACE;
@@ -525,12 +552,13 @@ extern "C" int disyolo_psroi_loss(const float* score, const uint8_t* true_masks,
   });
   hipStream_t st = (hipStream_t)stream;
   const int nblk = ceil_div((size_t)map_size * map_size, 256);
-  hipLaunchKernelGGL(psroi_loss_kernel, dim3(nblk, B), dim3(256), 0, st, score, true_masks, G, rois, roi_count, B,
-                     map_size, mask_scale, (bf16*)dscore, (float*)workspace);
+  auto kern = k == 3 ? psroi_loss_kernel<3> : k == 5 ? psroi_loss_kernel<5> : psroi_loss_kernel<7>;
+  hipLaunchKernelGGL(kern, dim3(nblk, B), dim3(256), 0, st, score, true_masks, G, rois, roi_count, B, map_size, mask_scale,
+                     (bf16*)dscore, (float*)workspace);
   DY_CHECK_LAUNCH();
   float* img_loss = (float*)workspace + (size_t)B * nblk * ROI_MAX;
   hipLaunchKernelGGL(psroi_loss_image_kernel, dim3(B), dim3(256), 0, st, (const float*)workspace, rois, roi_count,
-                     nblk, mask_scale, img_loss);
+                     nblk, roi_w(k), mask_scale, img_loss);
   DY_CHECK_LAUNCH();
   hipLaunchKernelGGL(psroi_loss_final_kernel, dim3(1), dim3(64), 0, st, (const float*)img_loss, B, loss);
   DY_CHECK_LAUNCH();

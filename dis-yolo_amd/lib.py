@@ -19,6 +19,17 @@ LIB_PATH = os.environ.get("DISYOLO_LIB", os.path.join(_HERE, "libdisyolo_hip.so"
 GRAD_LD = 32
 ROI_MAX = 16
 ROI_W = 12
+K_MAPS = (3, 5, 7)          # position-sensitive grids the mask path covers (the reference's list)
+
+
+def roi_w(k: int) -> int:
+    """int32 words per RoI row of a k x k grid (DISYOLO_ROI_W_K): gy0..gyk, gx0..gxk, gt_row, area, valid, 0"""
+    return 2 * (k + 1) + 4
+
+
+def block32_post(k: int) -> int:
+    """``post`` code of block32_fused_fwd for the mask head of a k x k grid (1, 2, 3 for k = 3, 5, 7)"""
+    return {3: 1, 5: 2, 7: 3}[k]
 CONV_LEAKY, CONV_OUT_F32, CONV_STATS, CONV_BN_BWD_STATS, CONV_BN_FUSED, CONV_BN_BWD_FUSED = 1, 2, 4, 8, 16, 32
 
 
@@ -124,6 +135,8 @@ _SIGS = {
     "disyolo_shuffle_perm": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p]),
     "disyolo_mask_rois": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p] + [C.c_int] * 4 +
                           [C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "disyolo_mask_rois_k": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p] + [C.c_int] * 5 +
+                            [C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
     "disyolo_psroi_loss_workspace": (C.c_size_t, [C.c_int, C.c_int]),
     "disyolo_psroi_loss": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p] + [C.c_int] * 3 +
                            [C.c_float] + [C.c_void_p] * 3 + [C.c_size_t, C.c_void_p]),
@@ -632,8 +645,8 @@ def block32_fused_ok(B: int, H: int, W: int, C0: int, C1: int, post: int) -> boo
 
 def block32_fused_fwd(x0, x1, wA, scaleA, shiftA, wB, scaleB, shiftB, y, post=0, wC=None, biasC=None, alpha=0.1) -> None:
     """[1x1 (C0 + up2(C1)) -> 32] -> [3x3 32 -> 64] with folded batch norms in one launch; post 0: + residual x0 -> bf16 y
-    (the first residual block), post 1: -> [1x1 64 -> 9] + bias -> f32 y (the mask head).  The 32- and 64-channel
-    intermediates are not materialised."""
+    (the first residual block), post 1 / 2 / 3: -> [1x1 64 -> 9 / 25 / 49] + bias -> f32 y (the mask head of a k = 3 / 5 / 7
+    grid, block32_post(k)).  The 32- and 64-channel intermediates are not materialised."""
     _need(x0, torch.bfloat16, "x0")
     _need(y, torch.bfloat16 if post == 0 else torch.float32, "y")
     B, H, W, C0 = x0.shape
@@ -642,7 +655,7 @@ def block32_fused_fwd(x0, x1, wA, scaleA, shiftA, wB, scaleB, shiftB, y, post=0,
     if x1 is not None:
         _need(x1, torch.bfloat16, "x1")
         _need_shape(x1, (B, H // 2, W // 2, C1), "block32_fused_fwd: x1")
-    _need_shape(y, (B, H, W, 9 if post else 64), "block32_fused_fwd: y")
+    _need_shape(y, (B, H, W, {0: 64, 1: 9, 2: 25, 3: 49}[post]), "block32_fused_fwd: y")
     fn = lambda: _check(load().disyolo_block32_fused_fwd(_p(x0), _p(x1), C0, C1, _p(wA), _p(scaleA), _p(shiftA), _p(wB), _p(scaleB),
                                                          _p(shiftB), post, _p(wC), _p(biasC), _p(y), B, H, W, alpha, _stream()),
                         "block32_fused_fwd")
@@ -1000,9 +1013,11 @@ def shuffle_perm(perm_det, perm_gt, B, seed, step_counter) -> None:
 
 
 def mask_rois(detections, max_det, true_boxes, G, perm_det, perm_gt, B, map_size, n_det, n_gt, iou_thresh, rois,
-              roi_count) -> None:
-    _check(load().disyolo_mask_rois(_p(detections), max_det, _p(true_boxes), G, _p(perm_det), _p(perm_gt), B, map_size,
-                                    n_det, n_gt, iou_thresh, _p(rois), _p(roi_count), _stream()), "mask_rois")
+              roi_count, k: int = 3) -> None:
+    """rois int32 [B, ROI_MAX, roi_w(k)]"""
+    _need_shape(rois, (B, ROI_MAX, roi_w(k)), "mask_rois: rois")
+    _check(load().disyolo_mask_rois_k(_p(detections), max_det, _p(true_boxes), G, _p(perm_det), _p(perm_gt), B, map_size,
+                                      k, n_det, n_gt, iou_thresh, _p(rois), _p(roi_count), _stream()), "mask_rois")
 
 
 def psroi_loss(score, true_masks, G, rois, roi_count, B, map_size, k, mask_scale, dscore, loss, ws: Workspace) -> None:

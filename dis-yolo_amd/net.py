@@ -122,7 +122,7 @@ class YOLONet(object):
     def __init__(self, training: bool = False, device=None, image_size: Optional[int] = None,
                  batch_size: Optional[int] = None, stage: int = 1, lock: Optional[Dict[int, bool]] = None,
                  seed: int = 0, xavier_locked: bool = True, plan_only: bool = False, dtype: str = "bf16",
-                 backbone_pair: bool = False):
+                 backbone_pair: bool = False, k_map: Optional[int] = None):
         # 1. parameters (yolo/yolo3_net_pos.py:15-38)
         self.batchsize = int(batch_size if batch_size is not None else cfg.BATCH_SIZE)
         self.classes = cfg.CLASSES
@@ -130,7 +130,10 @@ class YOLONet(object):
         self.anchors = np.asarray(cfg.ANCHORS, dtype=np.float32)
         self.num_anchor = 3
         self.output_depth = (self.num_class + 5) * self.num_anchor
-        self.k = cfg.K_MAP
+        # k_map x k_map position-sensitive score maps (conv82 emits k_map^2 channels); cfg.K_MAP unless given
+        self.k = int(k_map if k_map is not None else cfg.K_MAP)
+        if self.k not in L.K_MAPS:
+            raise ValueError("k_map must be one of %s (got %d)" % (", ".join(map(str, L.K_MAPS)), self.k))
         self.k_mapout = self.k * self.k
         self.object_scale = cfg.OBJECT_SCALE
         self.noobject_scale = cfg.NOOBJECT_SCALE
@@ -414,9 +417,10 @@ class YOLONet(object):
                 l.wp = torch.zeros(l.cout, K, dtype=BF16, device=dev)
             l.cout_pad = l.cout if l.cout % 32 == 0 else ((l.cout + 31) // 32) * 32
             if self.training and not l.lock:
-                # gradient wrt this layer's conv output (bf16, row pitch cout_pad)
+                # gradient wrt this layer's conv output (bf16, row pitch cout_pad: GRAD_LD for the heads and for conv82 up to
+                # k_map = 5, 64 for the 49 score maps of k_map = 7)
                 if l.kind == "lin":
-                    l.dx = torch.zeros(B, l.Ho, l.Wo, L.GRAD_LD, dtype=BF16, device=dev)
+                    l.dx = torch.zeros(B, l.Ho, l.Wo, l.cout_pad, dtype=BF16, device=dev)
                 else:
                     l.dx = torch.zeros(B, l.Ho, l.Wo, l.cout, dtype=BF16, device=dev)
             if self.training and has_trainable_upto[l.idx] and l.kind != "lin":
@@ -452,7 +456,7 @@ class YOLONet(object):
             self.true_masks = torch.zeros(B, G, S, S, dtype=torch.uint8, device=dev)
             self.perm_det = torch.arange(cfg.MAX_DETECTION, dtype=torch.int32, device=dev).repeat(B, 1).contiguous()
             self.perm_gt = torch.arange(G, dtype=torch.int32, device=dev).repeat(B, 1).contiguous()
-            self.rois = torch.zeros(B, L.ROI_MAX, L.ROI_W, dtype=torch.int32, device=dev)
+            self.rois = torch.zeros(B, L.ROI_MAX, L.roi_w(self.k), dtype=torch.int32, device=dev)
             self.roi_count = torch.zeros(B, dtype=torch.int32, device=dev)
             self._in_sets = None
             if self.pair:     # the per-batch inputs of the trainable part, once per half
@@ -886,7 +890,7 @@ class YOLONet(object):
         l80, l81, l82 = self.by_idx[80], self.by_idx[81], self.by_idx[82]
         self._fold_trainable(80, 81)
         L.block32_fused_fwd(self._input_of(l80, l80.src), self._input_of(l80, l80.src_up), l80.wp, l80.scale, l80.shift, l81.wp, l81.scale,
-                            l81.shift, l82.act, post=1, wC=l82.wp, biasC=l82.bias, alpha=cfg.ALPHA)
+                            l81.shift, l82.act, post=L.block32_post(self.k), wC=l82.wp, biasC=l82.bias, alpha=cfg.ALPHA)
 
     def _forward_prefix(self, upto: int, is_training: bool) -> None:
         """layers 1..upto one after the other on the current lane (the pipelined backbone), same kernels as
@@ -948,8 +952,9 @@ class YOLONet(object):
                         and L.block64_fused_ok(self.B, lb.Ho, lb.Wo, self.by_idx[i3 - 2].cout)):
                     plan[i3 - 1], plan[i3] = None, (lambda i3=i3: self._forward_block64(i3))
             l80, l82 = self.by_idx[80], self.by_idx[82]
-            if (first <= 80 and last >= 82 and self._inference_mode((80, 81, 82), is_training) and l82.cout == 9
-                    and L.block32_fused_ok(self.B, l82.Ho, l82.Wo, self.by_idx[l80.src].cout, self.by_idx[l80.src_up].cout, 1)):
+            if (first <= 80 and last >= 82 and self._inference_mode((80, 81, 82), is_training)
+                    and L.block32_fused_ok(self.B, l82.Ho, l82.Wo, self.by_idx[l80.src].cout, self.by_idx[l80.src_up].cout,
+                                           L.block32_post(self.k))):
                 plan[80], plan[81], plan[82] = None, None, self._forward_mask_head
         return plan
 
@@ -1269,7 +1274,7 @@ class YOLONet(object):
         Sm = self.S // 2
         L.mask_rois(self.detections, cfg.MAX_DETECTION, self.true_boxes, cfg.MAX_BOX_PER_IMAGE, self.perm_det,
                     self.perm_gt, self.B, Sm, cfg.MASK_ROI_DET, cfg.MASK_ROI_GT, cfg.MASK_ROI_IOU, self.rois,
-                    self.roi_count)
+                    self.roi_count, k=self.k)
         if side:
             L.lane_sync(0, 1)
         m = self.by_idx[82]
@@ -1425,7 +1430,7 @@ class YOLONet(object):
                 # with DISYOLO_TAIL_MAIN > 0 the loss differed from run to run)
                 wsl = self.ws_aux if pside else self.ws
                 if pl.kind == "lin":
-                    L.colsum(pl.dx, pl.dbias, pM, L.GRAD_LD, pl.cout, wsl)   # bias gradient
+                    L.colsum(pl.dx, pl.dbias, pM, pl.cout_pad, pl.cout, wsl)   # bias gradient
                 if pl.idx == 1:
                     if pl.cout == 32 and os.environ.get("DISYOLO_FIRST_WGRAD_MFMA", "1") != "0":
                         # the first layer's own kernel: taps as the M axis of the MFMA, the f32 image rounded to bf16 on
@@ -1493,7 +1498,7 @@ class YOLONet(object):
                 continue
             M = B * l.Ho * l.Wo
             if l.kind == "lin":
-                dx, ld = l.dx, L.GRAD_LD
+                dx, ld = l.dx, l.cout_pad
             else:
                 if not l.grad_set:
                     raise L.DisyoloError("layer %d received no gradient" % l.idx)

@@ -48,6 +48,8 @@ def main():
     ap.add_argument("--size", type=int, default=192)
     ap.add_argument("--batch", type=int, default=4)
     ap.add_argument("--out", default="/tmp/disyolo_example")
+    ap.add_argument("--k-map", type=int, default=cfg.K_MAP, choices=(3, 5, 7),
+                    help="position-sensitive mask grid (k x k score maps, cfg.K_MAP)")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     rng = np.random.RandomState(0)
@@ -55,7 +57,7 @@ def main():
 
     # --- train: stage 1 (conv1-52 locked), batches built on the GPU from the polygon records
     data = defect_train(labels, batch_size=args.batch, image_size=args.size, device=dev, rng=np.random.RandomState(1))
-    net = YOLONet(training=True, device=dev, image_size=args.size, batch_size=args.batch, stage=1, seed=0)
+    net = YOLONet(training=True, device=dev, image_size=args.size, batch_size=args.batch, stage=1, seed=0, k_map=args.k_map)
     solver = Solver(net, data, output_dir=args.out, max_iter=args.steps, summary_iter=max(1, args.steps // 4),
                     save_iter=args.steps, log=print)
     hist = solver.train()
@@ -65,7 +67,7 @@ def main():
     # --- test: reload the checkpoint the Solver wrote into an inference net
     prefix = checkpoint.latest_checkpoint(os.path.join(args.out, "checkpoint"))
     print("restoring", prefix)
-    inf = YOLONet(training=False, device=dev, image_size=args.size, batch_size=1, stage=1, seed=123)
+    inf = YOLONet(training=False, device=dev, image_size=args.size, batch_size=1, stage=1, seed=123, k_map=args.k_map)
     checkpoint.restore_net(inf, prefix)
     rec = labels[0]
     from disyolo_amd.evaluate import image_read

@@ -36,6 +36,9 @@ extern "C" {
 #define DISYOLO_GRAD_LD 32      /* channel pitch of the head-logit / score-map gradients */
 #define DISYOLO_ROI_MAX 16      /* RoI slots per image in the mask-loss RoI table       */
 #define DISYOLO_ROI_W 12        /* int32 words per RoI: gy0..3, gx0..3, gt_row, area, valid, 0 */
+/* int32 words per RoI of a k x k position-sensitive grid (k = 3, 5, 7): gy0..gyk, gx0..gxk, gt_row, area, valid, 0;
+ * DISYOLO_ROI_W_K(3) == DISYOLO_ROI_W */
+#define DISYOLO_ROI_W_K(k) (2 * ((k) + 1) + 4)
 
 int disyolo_version(void);
 const char* disyolo_last_error(void);
@@ -193,9 +196,10 @@ int disyolo_conv12_fused_fwd(const float* images, const float* w1_hwio, const fl
  *   post 0  (C0 = 64, C1 = 0): y bf16 [B,H,W,64] = leaky(bnB(conv3x3(leaky(bnA(conv1x1(x0)))))) + x0 -- the first residual
  *           block (conv_bn 'convolutional3' + res_conv_bn 'convolutional4'), yolo/yolo3_net_pos.py:169-176;
  *   post 1  (C0 = 64, C1 = 32): y f32 [B,H,W,9] = conv1x1(leaky(bnB(conv3x3(leaky(bnA(conv1x1([x0, up2(x1)]))))))) + biasC -- the
- *           mask head (conv_bn 'convolutional80', 'convolutional81', conv 'convolutional82'), yolo/yolo3_net_pos.py:404-412; x1 bf16 [B,H/2,W/2,32] is read at (y/2, x/2).
- * x0 bf16 NHWC; wA packed [32][C0+C1], wB packed [64][9*32], wC packed [9][64] (pack_weights).  _ok: 1 when covered
- * (those two shapes, H a multiple of 8, W of 16). */
+ *           mask head (conv_bn 'convolutional80', 'convolutional81', conv 'convolutional82'), yolo/yolo3_net_pos.py:404-412; x1 bf16 [B,H/2,W/2,32] is read at (y/2, x/2);
+ *   post 2, 3: the same mask head with NOUT = 25, 49 score maps (K_MAP = 5, 7): y f32 [B,H,W,NOUT].
+ * x0 bf16 NHWC; wA packed [32][C0+C1], wB packed [64][9*32], wC packed [NOUT][64] (pack_weights; NOUT = 9 for post 1).
+ * _ok: 1 when covered (those shapes, H a multiple of 8, W of 16, the largest tensor under 2^31 bytes). */
 int disyolo_block32_fused_ok(int B, int H, int W, int C0, int C1, int post);
 int disyolo_block32_fused_fwd(const void* x0, const void* x1, int C0, int C1, const void* wA, const float* scaleA,
                               const float* shiftA, const void* wB, const float* scaleB, const float* shiftB, int post,
@@ -390,8 +394,13 @@ int disyolo_yolo_loss(const float* const logits[3], const float* const labels[3]
 /* ---- position-sensitive RoI assembly (yolo/yolo3_net_pos.py:750-938) ---- */
 /* RoI selection for the mask loss (:757-796): detections [B,max_det,6], true_boxes [B,G,5],
  * perm_det int32 [B,max_det] / perm_gt int32 [B,G] replace tf.random_shuffle (:781-782).
- * Writes rois int32 [B,DISYOLO_ROI_MAX,DISYOLO_ROI_W] (positive RoIs first: the k+1 bin edges
- * per axis on the S/2 grid after tf.round, assigned GT row, pixel area) and roi_count [B]. */
+ * Writes rois int32 [B,DISYOLO_ROI_MAX,DISYOLO_ROI_W_K(k)] (positive RoIs first: the k+1 bin edges
+ * per axis on the S/2 grid after tf.round, assigned GT row, pixel area) and roi_count [B].
+ * k = 3, 5 or 7; disyolo_mask_rois is the k = 3 case (rows of DISYOLO_ROI_W words). */
+int disyolo_mask_rois_k(const float* detections, int max_det, const float* true_boxes, int G,
+                        const int32_t* perm_det, const int32_t* perm_gt, int B, int map_size, int k,
+                        int n_det, int n_gt, float iou_thresh, int32_t* rois, int32_t* roi_count,
+                        void* stream);
 int disyolo_mask_rois(const float* detections, int max_det, const float* true_boxes, int G,
                       const int32_t* perm_det, const int32_t* perm_gt, int B, int map_size,
                       int n_det, int n_gt, float iou_thresh, int32_t* rois, int32_t* roi_count,
@@ -402,7 +411,9 @@ int disyolo_mask_rois(const float* detections, int max_det, const float* true_bo
 int disyolo_shuffle_perm(int32_t* perm_det, int n_det, int32_t* perm_gt, int n_gt, int B, uint32_t seed,
                          const int64_t* step_counter, void* stream);
 /* masked BCE over assembled logits + gradient wrt the score maps (:799-858).
- * score f32 [B,Sm,Sm,k*k]; true_masks uint8 [B,G,2Sm,2Sm]; dscore bf16 [B,Sm,Sm,32] (padded);
+ * k = 3, 5 or 7; score f32 [B,Sm,Sm,k*k]; rois from disyolo_mask_rois_k with the same k;
+ * true_masks uint8 [B,G,2Sm,2Sm]; dscore bf16 [B,Sm,Sm,P] with P = round_up(k*k, 32) (32 for
+ * k = 3, 5; 64 for k = 7: conv82's padded output pitch), channels k*k..P-1 written as zeros;
  * loss f32[1] = mask_scale * mean_b(mean_r(sum BCE / area)). */
 size_t disyolo_psroi_loss_workspace(int B, int map_size);
 int disyolo_psroi_loss(const float* score, const uint8_t* true_masks, int G, const int32_t* rois,
@@ -410,7 +421,8 @@ int disyolo_psroi_loss(const float* score, const uint8_t* true_masks, int G, con
                        void* dscore, float* loss, void* workspace, size_t workspace_bytes,
                        void* stream);
 /* inference assembly (val_test, :862-938): masks f32 [B,max_det,Sm,Sm] = sigmoid(selected
- * channel) inside the box, 0.5 outside; keep int32 [B,max_det] = 1 for rows with h>0 and w>0. */
+ * channel) inside the box, 0.5 outside; keep int32 [B,max_det] = 1 for rows with h>0 and w>0.
+ * k = 3, 5 or 7; score f32 [B,Sm,Sm,k*k]. */
 int disyolo_psroi_assemble(const float* score, const float* detections, int B, int max_det,
                            int map_size, int k, float* masks, int32_t* keep, void* stream);
 
