@@ -13,6 +13,7 @@ Two kinds of check:
 """
 import math
 
+import pytest
 import torch
 import torch.nn.functional as F
 
@@ -34,6 +35,14 @@ C_DX_REL, C_DX_FIRST = 2.0 ** -8, 2.0 ** -8             # dx: rel*|want| + first
 # differs from it by independent bf16 roundings, which the sqrt term carries  [0.77]
 C_SUM_SQRT_OWN, C_SUM_ABS_OWN = 2.0 ** -16, 2.0 ** -23
 C_SUM_SQRT, C_SUM_ABS = 2.0 ** -7, 2.0 ** -14
+
+
+@pytest.fixture
+def tuned_tables():
+    """a test that loads a tile table (net.autotune(cache=...) fills lib.TUNED) clears it afterwards"""
+    from disyolo_amd import lib as L
+    yield
+    L.TUNED.clear()
 
 
 def f64(t: torch.Tensor) -> torch.Tensor:

@@ -36,6 +36,7 @@ import pytest
 import torch
 
 import backward_ref as R
+from backward_ref import tuned_tables  # noqa: F401  (fixture)
 from disyolo_amd import config as cfg
 from disyolo_amd import lib as L
 from disyolo_amd.net import YOLONet, var_name
@@ -52,7 +53,10 @@ CONFIGS = {
     "stage1_576_b8_inkernel_bwd": (1, 576, 8, True),
     "stage1_832_b4": (1, 832, 4, False),            # configs[4] per GPU
     "stage2_576_b8": (2, 576, 8, False),
+    "stage1_576_b8_tuned": (1, 576, 8, False),      # ... with the tile table bench.py loads for it
 }
+# configurations that load a committed tile table (autotune(cache=...) only reads it) instead of the launcher's heuristic tiles
+TABLES = {"stage1_576_b8_tuned": "tune_train_B8_576_stage1.json"}
 
 
 REPORTS = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "test_reports")
@@ -62,6 +66,14 @@ def _report(name, rep):
     os.makedirs(REPORTS, exist_ok=True)
     with open(os.path.join(REPORTS, name + ".json"), "w") as f:
         json.dump(rep, f, indent=1)
+
+
+def _load_table(net, tag):
+    if tag in TABLES:
+        path = os.path.join(os.path.dirname(REPORTS), "profiles", TABLES[tag])
+        assert os.path.exists(path), path        # (autotune(cache=) would time the candidates and write the file)
+        net.autotune(cache=path)
+        assert L.TUNED
 
 
 def _net(dev, stage, S, B, inkernel_bwd=False):
@@ -197,9 +209,10 @@ def run_part_a(net, tag):
 
 
 @pytest.mark.parametrize("tag", list(CONFIGS))
-def test_backward_matches_f64_layer_by_layer(dev, tag):
+def test_backward_matches_f64_layer_by_layer(dev, tag, tuned_tables):
     stage, S, B, inkernel = CONFIGS[tag]
     net = _net(dev, stage, S, B, inkernel)
+    _load_table(net, tag)
     rep = run_part_a(net, tag)
     if inkernel and not rep["forms"]["fused"]:
         pytest.skip("no layer takes the in-launch batch-norm backward at %d^2, B = %d" % (S, B))
@@ -224,7 +237,7 @@ def test_recorded_step_gradients_are_bitwise_the_eager_ones(dev):
 
 
 # ------------------------------------------------------------------------------------------------ Part B: integer operands
-EXACT_CONFIGS = {"stage2_576_b8": (2, 576, 8), "stage1_832_b4": (1, 832, 4)}
+EXACT_CONFIGS = {"stage2_576_b8": (2, 576, 8), "stage1_832_b4": (1, 832, 4), "stage1_576_b8_tuned": (1, 576, 8)}
 
 
 def _ints(t, lo, hi, gen):
@@ -240,9 +253,10 @@ def _bn_partials_ref(grad, tgt):
 
 
 @pytest.mark.parametrize("tag", list(EXACT_CONFIGS))
-def test_backward_launches_are_exact_on_integers(dev, tag):
+def test_backward_launches_are_exact_on_integers(dev, tag, tuned_tables):
     stage, S, B = EXACT_CONFIGS[tag]
     net = YOLONet(training=True, device=dev, image_size=S, batch_size=B, stage=stage, seed=0)
+    _load_table(net, tag)
     gen = torch.Generator(device=dev).manual_seed(11)
     t0 = time.perf_counter()
     launches, fails = [], []

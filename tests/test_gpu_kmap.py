@@ -15,6 +15,7 @@ from disyolo_amd.net import YOLONet
 from test_gpu_conv import _block32_operands, bf16r, check, pack_ref
 from test_gpu_loss import assert_grad_close, mask_case
 from test_gpu_net import oracle_params, rel_err
+from forward_ref import val_test_k
 
 pytestmark = pytest.mark.gpu
 
@@ -39,23 +40,6 @@ def loss_mask_k(detections, mask_pos, true_boxes, true_masks, perms, k):
             per_roi.append((mobj * O.sigmoid_ce(gtm, logits)).sum() / mobj.sum())
         total = total + O.MASK_SCALE * torch.stack(per_roi).mean()
     return total / B
-
-
-def val_test_k(detections, mask_pos, k):
-    """O.val_test (yolo/yolo3_net_pos.py:862-938) with a k x k grid"""
-    det_box, det_mask = [], []
-    size = mask_pos.shape[1]
-    for i in range(mask_pos.shape[0]):
-        prop = detections[i].astype(np.float32)
-        pb = np.round(prop[:, :4] * np.float32(size))
-        keep = np.where(((pb[:, 2] - pb[:, 0]) > 0) & ((pb[:, 3] - pb[:, 1]) > 0))[0]
-        prop, pb = prop[keep], pb[keep]
-        if prop.size > 0:
-            det_mask.append(torch.stack([torch.sigmoid(O.assemble_logits(mask_pos[i], b, k)[0]) for b in pb]).float().numpy())
-        else:
-            det_mask.append(np.float32(0.0))
-        det_box.append(prop)
-    return det_box, det_mask
 
 
 def expected_rois_k(det, tb, perms, sm, k):
