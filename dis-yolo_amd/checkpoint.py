@@ -432,15 +432,18 @@ def save_net(net, prefix: str) -> None:
 def restore_net(net, prefix: str, stage1_include: bool = False) -> List[str]:
     """stage1_include=True: ``assign_from_checkpoint_fn(include, ignore_missing_vars=True)`` -- variables in
     the include list that the file holds (shape mismatches raise, as TF does); False: ``Saver.restore`` of
-    every variable (a missing one raises).  Returns the restored names."""
+    every variable (a missing one raises).  Shapes are checked first: a file that both lacks variables and holds one at
+    another shape (another mask_stride or k_map) raises the ValueError naming that variable.  Returns the restored names."""
     names = stage1_include_names() if stage1_include else list(net.params)
     got = load_checkpoint(prefix, names)
+    # shapes first: a checkpoint of another mask subnet (mask_stride) or grid (k_map) both lacks variables and holds some
+    # at another shape -- the error names the first such variable
+    for n, a in got.items():
+        if n in net.params and tuple(a.shape) != tuple(net.params[n].shape):
+            raise ValueError("variable %s: checkpoint shape %s, graph shape %s" % (n, a.shape, tuple(net.params[n].shape)))
     if not stage1_include:
         missing = [n for n in names if n not in got]
         if missing:
             raise KeyError("checkpoint %s lacks %d variables, e.g. %s" % (prefix, len(missing), missing[:3]))
-    for n, a in got.items():
-        if n in net.params and tuple(a.shape) != tuple(net.params[n].shape):
-            raise ValueError("variable %s: checkpoint shape %s, graph shape %s" % (n, a.shape, tuple(net.params[n].shape)))
     net.load_state_dict({n: a for n, a in got.items() if n in net.params}, strict=False)
     return sorted(got)

@@ -33,6 +33,9 @@ ALPHA = 0.1
 BATCH_SIZE = 2
 IMAGE_SIZE = 576
 K_MAP = 3
+# mask subnet: score maps at IMAGE_SIZE / MASK_STRIDE; 2 = the reference's active m = 1/2 (yolo/yolo3_net_pos.py:380-412),
+# 4 = its m = 1/4 (:361-378), 1 = its m = 1 (:414-461)
+MASK_STRIDE = 2
 
 BASE_GRID = int(IMAGE_SIZE / 32)
 

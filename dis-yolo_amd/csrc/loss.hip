@@ -325,10 +325,11 @@ __global__ __launch_bounds__(64) void mask_rois_kernel(const float* det_g, int m
 }
 
 // one thread = one score-map pixel; loops the image's positive RoIs.  score rows have k*k channels, dscore rows
-// dscore_ld(k) (the pad channels are written as zeros); the k*k gradient accumulators stay in registers.
+// dscore_ld(k) (the pad channels are written as zeros); the k*k gradient accumulators stay in registers.  The GT masks
+// are st x the score map's size (st = the mask subnet's stride: 1, 2, 4).
 template <int K>
 __global__ __launch_bounds__(256) void psroi_loss_kernel(const float* score, const uint8_t* true_masks, int G,
-                                                         const int* rois, const int* roi_count, int B, int Sm,
+                                                         const int* rois, const int* roi_count, int B, int Sm, int st,
                                                          float mask_scale, bf16* dscore, float* partial) {
   constexpr int RW = roi_w(K), KK = K * K, LD = dscore_ld(K);
   __shared__ int s_roi[ROI_MAX * RW];
@@ -348,7 +349,7 @@ __global__ __launch_bounds__(256) void psroi_loss_kernel(const float* score, con
   if (i < npx && cnt > 0) {
     const int y = i / Sm, x = i - y * Sm;
     const float* sc = score + ((size_t)b * npx + i) * KK;
-    const int S = 2 * Sm;
+    const int S = st * Sm;
     const float coef0 = mask_scale / ((float)B * (float)cnt);
 #pragma unroll
     for (int r = 0; r < ROI_MAX; ++r) {
@@ -363,8 +364,8 @@ __global__ __launch_bounds__(256) void psroi_loss_kernel(const float* score, con
           }
           const int ch = by * K + bx;
           const float logit = sc[ch];
-          // GT mask down-sampled by exact 2x legacy bilinear == [::2, ::2] (:773-775)
-          const float gt = true_masks[(((size_t)b * G + o[2 * K + 2]) * S + 2 * y) * S + 2 * x] ? 1.f : 0.f;
+          // GT mask down-sampled by exact st-x legacy bilinear == [::st, ::st] (:773-775)
+          const float gt = true_masks[(((size_t)b * G + o[2 * K + 2]) * S + st * y) * S + st * x] ? 1.f : 0.f;
           const float inv_area = 1.f / (float)o[2 * K + 3];
           lsum[r] = sigmoid_ce(gt, logit) * inv_area;
           const float dv = (sigmoidf_(logit) - gt) * inv_area * coef0;
@@ -539,22 +540,32 @@ extern "C" size_t disyolo_psroi_loss_workspace(int B, int map_size) {
 extern "C" int disyolo_psroi_loss(const float* score, const uint8_t* true_masks, int G, const int32_t* rois,
                                   const int32_t* roi_count, int B, int map_size, int k, float mask_scale, void* dscore,
                                   float* loss, void* workspace, size_t workspace_bytes, void* stream) {
+  return disyolo_psroi_loss_s(score, true_masks, G, rois, roi_count, B, map_size, 2, k, mask_scale, dscore, loss,
+                              workspace, workspace_bytes, stream);
+}
+
+extern "C" int disyolo_psroi_loss_s(const float* score, const uint8_t* true_masks, int G, const int32_t* rois,
+                                    const int32_t* roi_count, int B, int map_size, int mask_stride, int k,
+                                    float mask_scale, void* dscore, float* loss, void* workspace,
+                                    size_t workspace_bytes, void* stream) {
   DY_REQUIRE(score && true_masks && rois && roi_count && dscore && loss, "psroi_loss: null pointer");
   DY_REQUIRE(B > 0 && map_size > 0 && G > 0, "psroi_loss: bad sizes");
   DY_REQUIRE(kmap_supported(k), "psroi_loss: k must be one of k = 3, 5, 7 (got %d)", k);
+  DY_REQUIRE(mask_stride == 1 || mask_stride == 2 || mask_stride == 4,
+             "psroi_loss: mask_stride must be one of 1, 2, 4 (got %d)", mask_stride);
   if (!workspace || workspace_bytes < disyolo_psroi_loss_workspace(B, map_size)) {
     disyolo_set_error("psroi_loss: workspace too small");
     return DISYOLO_E_WORKSPACE;
   }
   DY_RECORD_OR_RUN([=](void* s) {
-    return disyolo_psroi_loss(score, true_masks, G, rois, roi_count, B, map_size, k, mask_scale, dscore, loss, workspace,
-                              workspace_bytes, s);
+    return disyolo_psroi_loss_s(score, true_masks, G, rois, roi_count, B, map_size, mask_stride, k, mask_scale, dscore,
+                                loss, workspace, workspace_bytes, s);
   });
   hipStream_t st = (hipStream_t)stream;
   const int nblk = ceil_div((size_t)map_size * map_size, 256);
   auto kern = k == 3 ? psroi_loss_kernel<3> : k == 5 ? psroi_loss_kernel<5> : psroi_loss_kernel<7>;
-  hipLaunchKernelGGL(kern, dim3(nblk, B), dim3(256), 0, st, score, true_masks, G, rois, roi_count, B, map_size, mask_scale,
-                     (bf16*)dscore, (float*)workspace);
+  hipLaunchKernelGGL(kern, dim3(nblk, B), dim3(256), 0, st, score, true_masks, G, rois, roi_count, B, map_size,
+                     mask_stride, mask_scale, (bf16*)dscore, (float*)workspace);
   DY_CHECK_LAUNCH();
   float* img_loss = (float*)workspace + (size_t)B * nblk * ROI_MAX;
   hipLaunchKernelGGL(psroi_loss_image_kernel, dim3(B), dim3(256), 0, st, (const float*)workspace, rois, roi_count,

@@ -20,6 +20,7 @@ GRAD_LD = 32
 ROI_MAX = 16
 ROI_W = 12
 K_MAPS = (3, 5, 7)          # position-sensitive grids the mask path covers (the reference's list)
+MASK_STRIDES = (1, 2, 4)    # GT mask -> score map sampling steps psroi_loss_s covers (score maps at S, S/2, S/4)
 
 
 def roi_w(k: int) -> int:
@@ -140,6 +141,8 @@ _SIGS = {
     "disyolo_psroi_loss_workspace": (C.c_size_t, [C.c_int, C.c_int]),
     "disyolo_psroi_loss": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p] + [C.c_int] * 3 +
                            [C.c_float] + [C.c_void_p] * 3 + [C.c_size_t, C.c_void_p]),
+    "disyolo_psroi_loss_s": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p] + [C.c_int] * 4 +
+                             [C.c_float] + [C.c_void_p] * 3 + [C.c_size_t, C.c_void_p]),
     "disyolo_psroi_assemble": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] * 3),
     "disyolo_mask_paste": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
                                      C.c_void_p, C.c_void_p]),
@@ -1020,11 +1023,13 @@ def mask_rois(detections, max_det, true_boxes, G, perm_det, perm_gt, B, map_size
                                       k, n_det, n_gt, iou_thresh, _p(rois), _p(roi_count), _stream()), "mask_rois")
 
 
-def psroi_loss(score, true_masks, G, rois, roi_count, B, map_size, k, mask_scale, dscore, loss, ws: Workspace) -> None:
+def psroi_loss(score, true_masks, G, rois, roi_count, B, map_size, k, mask_scale, dscore, loss, ws: Workspace,
+               mask_stride: int = 2) -> None:
+    """true_masks uint8 [B, G, mask_stride * map_size, mask_stride * map_size], sampled at [::mask_stride, ::mask_stride]"""
     need = load().disyolo_psroi_loss_workspace(B, map_size)
     buf = ws.get(need)
-    _check(load().disyolo_psroi_loss(_p(score), _p(true_masks), G, _p(rois), _p(roi_count), B, map_size, k, mask_scale,
-                                     _p(dscore), _p(loss), _p(buf), buf.numel(), _stream()), "psroi_loss")
+    _check(load().disyolo_psroi_loss_s(_p(score), _p(true_masks), G, _p(rois), _p(roi_count), B, map_size, mask_stride, k,
+                                       mask_scale, _p(dscore), _p(loss), _p(buf), buf.numel(), _stream()), "psroi_loss")
 
 
 def psroi_assemble(score, detections, B, max_det, map_size, k, masks, keep) -> None:

@@ -46,11 +46,17 @@ class Layer:
             setattr(self, s, None)
 
 
-def build_topology(num_class: int, k_map: int) -> List[Layer]:
-    """The layer table of build_network (yolo/yolo3_net_pos.py:159-412, active m=1/2 mask
-    subnet).  ``src`` = producing layer (0 = the image); ``src_up`` = layer whose output is
-    nearest-upsampled x2 and concatenated AFTER ``src`` (:290-291); ``shortcut`` = layer
-    added after the activation (:148-151)."""
+MASK_STRIDES = (4, 2, 1)     # mask subnets m = 1/4, 1/2, 1: score maps at S/4, S/2, S (yolo/yolo3_net_pos.py:361-461)
+
+
+def build_topology(num_class: int, k_map: int, mask_stride: int = 2) -> List[Layer]:
+    """The layer table of build_network (yolo/yolo3_net_pos.py:159-461).  ``mask_stride`` picks the mask subnet: 2 = the
+    active m=1/2 one (:380-412, 82 layers), 4 = m=1/4 (:361-378, 79 layers), 1 = m=1 (:414-461, 85 layers); the last
+    layer emits the k_map^2 score maps.  ``src`` = producing layer (0 = the image); ``src_up`` = layer whose output is
+    nearest-upsampled x2 and concatenated AFTER ``src`` (:290-291); ``shortcut`` = layer added after the activation
+    (:148-151)."""
+    if mask_stride not in MASK_STRIDES:
+        raise ValueError("mask_stride must be one of %s (got %r)" % (", ".join(map(str, MASK_STRIDES)), mask_stride))
     out_depth = (num_class + 5) * 3
     Ls: List[Layer] = []
 
@@ -96,21 +102,35 @@ def build_topology(num_class: int, k_map: int) -> List[Layer]:
     add(73, 256, 128, 1, 1, "bn", 72)
     add(74, 128, 256, 3, 1, "bn", 73)
     add(75, 256, out_depth, 1, 1, "lin", 74)
-    # mask subnet m = 1/2
+    # mask subnet: conv76-78 are common to every m (score maps at S/4 after conv78)
     add(76, 128, 64, 1, 1, "bn", 73)
     add(77, 192, 64, 1, 1, "bn", 9, src_up=76)
     add(78, 64, 128, 3, 1, "bn", 77)
-    add(79, 128, 32, 1, 1, "bn", 78)
-    add(80, 96, 32, 1, 1, "bn", 4, src_up=79)
-    add(81, 32, 64, 3, 1, "bn", 80)
-    add(82, 64, k_map * k_map, 1, 1, "lin", 81)
+    if mask_stride == 4:           # m = 1/4 (:361-378)
+        add(79, 128, k_map * k_map, 1, 1, "lin", 78)
+    else:                          # m = 1/2 (:380-412)
+        add(79, 128, 32, 1, 1, "bn", 78)
+        add(80, 96, 32, 1, 1, "bn", 4, src_up=79)
+        add(81, 32, 64, 3, 1, "bn", 80)
+        if mask_stride == 2:
+            add(82, 64, k_map * k_map, 1, 1, "lin", 81)
+        else:                      # m = 1 (:414-461)
+            add(82, 64, 16, 1, 1, "bn", 81)
+            add(83, 48, 16, 1, 1, "bn", 1, src_up=82)
+            add(84, 16, 32, 3, 1, "bn", 83)
+            add(85, 32, k_map * k_map, 1, 1, "lin", 84)
     Ls.sort(key=lambda l: l.idx)
     # the residual shortcut of block [1x1 (i-1), 3x3 res (i)] is the block input = out(i-2)
     for l in Ls:
         if l.kind == "res":
             l.shortcut = l.idx - 2
-    assert [l.idx for l in Ls] == list(range(1, 83))
+    assert [l.idx for l in Ls] == list(range(1, score_layer_of(mask_stride) + 1))
     return Ls
+
+
+def score_layer_of(mask_stride: int) -> int:
+    """index of the layer that emits the score maps (the last layer): 79 / 82 / 85 for m = 1/4, 1/2, 1"""
+    return {4: 79, 2: 82, 1: 85}[mask_stride]
 
 
 def var_name(i: int, leaf: str) -> str:
@@ -122,7 +142,7 @@ class YOLONet(object):
     def __init__(self, training: bool = False, device=None, image_size: Optional[int] = None,
                  batch_size: Optional[int] = None, stage: int = 1, lock: Optional[Dict[int, bool]] = None,
                  seed: int = 0, xavier_locked: bool = True, plan_only: bool = False, dtype: str = "bf16",
-                 backbone_pair: bool = False, k_map: Optional[int] = None):
+                 backbone_pair: bool = False, k_map: Optional[int] = None, mask_stride: Optional[int] = None):
         # 1. parameters (yolo/yolo3_net_pos.py:15-38)
         self.batchsize = int(batch_size if batch_size is not None else cfg.BATCH_SIZE)
         self.classes = cfg.CLASSES
@@ -135,6 +155,12 @@ class YOLONet(object):
         if self.k not in L.K_MAPS:
             raise ValueError("k_map must be one of %s (got %d)" % (", ".join(map(str, L.K_MAPS)), self.k))
         self.k_mapout = self.k * self.k
+        # mask subnet resolution: score maps at S / mask_stride (4, 2, 1 = the reference's m = 1/4, 1/2, 1); cfg.MASK_STRIDE
+        # unless given.  The last layer (score_layer) emits the score maps: 79, 82 or 85
+        self.mask_stride = int(mask_stride if mask_stride is not None else cfg.MASK_STRIDE)
+        if self.mask_stride not in MASK_STRIDES:
+            raise ValueError("mask_stride must be one of %s (got %d)" % (", ".join(map(str, MASK_STRIDES)), self.mask_stride))
+        self.score_layer = score_layer_of(self.mask_stride)
         self.object_scale = cfg.OBJECT_SCALE
         self.noobject_scale = cfg.NOOBJECT_SCALE
         self.class_scale = cfg.CLASS_SCALE
@@ -170,8 +196,8 @@ class YOLONet(object):
             self.ws_det = L.Workspace(self.device)      # scratch of the detection filter (either lane)
         self._reg_fresh = False
         # lock map: stage 1 = conv1-52 locked (shipped source), stage 2 = all trainable
-        self.lock = dict(lock) if lock is not None else {i: (stage == 1 and i <= 52) for i in range(1, 83)}
-        self.layers = build_topology(self.num_class, self.k)
+        self.lock = dict(lock) if lock is not None else {i: (stage == 1 and i <= 52) for i in range(1, self.score_layer + 1)}
+        self.layers = build_topology(self.num_class, self.k, self.mask_stride)
         self.by_idx = {l.idx: l for l in self.layers}
         self._lr = float(cfg.LEARNING_RATE)
         self.lr_dev = None       # device copy read by the optimizer kernel (set in _init_params)
@@ -415,7 +441,9 @@ class YOLONet(object):
             if l.idx > 1:
                 K = l.k * l.k * l.cin
                 l.wp = torch.zeros(l.cout, K, dtype=BF16, device=dev)
-            l.cout_pad = l.cout if l.cout % 32 == 0 else ((l.cout + 31) // 32) * 32
+            # (a batch-normalised layer of 16 * odd channels -- m = 1's conv82 / conv83 -- keeps its own width: its gradient is
+            # the 16-channel source of its data-gradient conv, which the conv takes as it is)
+            l.cout_pad = l.cout if (l.cout % 32 == 0 or (l.kind != "lin" and l.cout % 16 == 0)) else ((l.cout + 31) // 32) * 32
             if self.training and not l.lock:
                 # gradient wrt this layer's conv output (bf16, row pitch cout_pad: GRAD_LD for the heads and for conv82 up to
                 # k_map = 5, 64 for the 49 score maps of k_map = 7)
@@ -510,6 +538,9 @@ class YOLONet(object):
         if [l.idx for l in ls] != list(range(self.FP8_FROM, self.FP8_UPTO + 1)) or not all(
                 l.lock or not self.training for l in self.layers[:self.FP8_UPTO]):
             raise L.DisyoloError("dtype='fp8' needs conv1-52 in inference mode (stage 1 training, or training=False)")
+        if self.FP8_FROM <= 1 and any(1 in (l.src, l.src_up) for l in self.layers if l.idx > 2):
+            # (conv1's output would be e4m3 only, and m = 1's conv83 reads it as a bf16 source)
+            raise L.DisyoloError("dtype='fp8' with DISYOLO_FP8_FROM=1 and mask_stride=1: conv83 needs act1 in bf16")
         # the bf16 layer in front of the first fp8 layer: its output is also kept as e4m3 (one quantisation pass per forward)
         self._fp8_entry = self.by_idx[self.FP8_FROM - 1] if self.FP8_FROM > 1 else None
         if self._fp8_entry is not None:
@@ -780,9 +811,11 @@ class YOLONet(object):
     # the trunk continues (58/59 after 57, 66/67 after 65, 74/75 after 73)
     HEAD_BRANCH = {58: 57, 66: 65, 74: 73}
     HEAD_LAYERS = (58, 59, 66, 67, 74, 75)
+    # ... and the first layer after each such branch, back on the main lane: head 2, head 3, the mask subnet (every m)
+    TRUNK_RESUME = (60, 68, 76)
 
     def _forward_layers(self, is_training: bool, first: int = 1) -> None:
-        plan = self._fusion_plan(is_training, first, 82)
+        plan = self._fusion_plan(is_training, first, self.score_layer)
         xwaits = []
         for l in self.layers:
             if l.idx < first:
@@ -791,7 +824,7 @@ class YOLONet(object):
                 if l.idx in self.HEAD_BRANCH:
                     L.lane_sync(0, 1)        # the branch point's output is ready on the main lane
                     L.set_lane(1)
-                elif l.idx in (60, 68, 76):
+                elif l.idx in self.TRUNK_RESUME:
                     L.set_lane(0)
             if self._overlap_rec:
                 # cross-replay waits are emitted in front of the first launch that EXECUTES at or after their layer (a layer
@@ -951,8 +984,8 @@ class YOLONet(object):
                 if (first <= i3 - 1 and last >= i3 and self._inference_mode((i3 - 1, i3), is_training)
                         and L.block64_fused_ok(self.B, lb.Ho, lb.Wo, self.by_idx[i3 - 2].cout)):
                     plan[i3 - 1], plan[i3] = None, (lambda i3=i3: self._forward_block64(i3))
-            l80, l82 = self.by_idx[80], self.by_idx[82]
-            if (first <= 80 and last >= 82 and self._inference_mode((80, 81, 82), is_training)
+            l80, l82 = self.by_idx.get(80), self.by_idx.get(82)
+            if (self.mask_stride == 2 and first <= 80 and last >= 82 and self._inference_mode((80, 81, 82), is_training)
                     and L.block32_fused_ok(self.B, l82.Ho, l82.Wo, self.by_idx[l80.src].cout, self.by_idx[l80.src_up].cout,
                                            L.block32_post(self.k))):
                 plan[80], plan[81], plan[82] = None, None, self._forward_mask_head
@@ -964,6 +997,8 @@ class YOLONet(object):
             return False
         if not self._inference_mode((1, 2), is_training):
             return False            # (a trainable conv1 / conv2 needs its own output -- and its batch statistics)
+        if any(1 in (l.src, l.src_up, l.shortcut) for l in self.layers if l.idx != 2):
+            return False            # (act1 has another consumer: m = 1's conv83)
         return L.conv12_fused_ok(self.B, self.S, self.S)
 
     def _forward_layer(self, l, is_training: bool) -> None:
@@ -1110,7 +1145,7 @@ class YOLONet(object):
                 self._use_half(prev_half)
         preds = [self.by_idx[i].act.view(self.B, self.by_idx[i].Ho, self.by_idx[i].Wo, 3, 5 + self.num_class)
                  for i in (75, 67, 59)]
-        return preds, self.detections, self.by_idx[82].act
+        return preds, self.detections, self.by_idx[self.score_layer].act
 
     def evaluation(self, images, clip_window, det_thresh=cfg.OBJ_THRESHOLD, masks_on_device: bool = False):
         """``sess.run(net.evaluation)`` (val_test, yolo/yolo3_net_pos.py:862-938): returns
@@ -1125,10 +1160,10 @@ class YOLONet(object):
             self.infer(images, clip_window)
         else:
             self.forward(images, clip_window, det_thresh, is_training=False)
-            Sm = self.S // 2
+            Sm = self.S // self.mask_stride
             if self.masks is None:
                 self.masks = torch.zeros(self.B, cfg.MAX_DETECTION, Sm, Sm, dtype=F32, device=self.device)
-            L.psroi_assemble(self.by_idx[82].act, self.detections, self.B, cfg.MAX_DETECTION, Sm, self.k, self.masks,
+            L.psroi_assemble(self.by_idx[self.score_layer].act, self.detections, self.B, cfg.MAX_DETECTION, Sm, self.k, self.masks,
                              self.keep)
         keep = self.keep.cpu().numpy().astype(bool)
         det = self.detections.cpu().numpy()
@@ -1147,7 +1182,7 @@ class YOLONet(object):
         and optionally a hipGraph; afterwards ``infer()`` is one replay.  Outputs stay on the
         device, fixed-shape: detections [B,30,6], det_count [B], masks [B,30,S/2,S/2],
         keep [B,30] (BASELINE.json config 4)."""
-        Sm = self.S // 2
+        Sm = self.S // self.mask_stride
         if self.masks is None:
             self.masks = torch.zeros(self.B, cfg.MAX_DETECTION, Sm, Sm, dtype=F32, device=self.device)
         prog = L.CmdList()
@@ -1162,7 +1197,7 @@ class YOLONet(object):
             with prog:
                 self._forward_layers(False)
                 self._detect(det_thresh)
-                L.psroi_assemble(self.by_idx[82].act, self.detections, self.B, cfg.MAX_DETECTION, Sm, self.k, self.masks,
+                L.psroi_assemble(self.by_idx[self.score_layer].act, self.detections, self.B, cfg.MAX_DETECTION, Sm, self.k, self.masks,
                                  self.keep)
         finally:
             self.use_side_lane = side_lane
@@ -1266,20 +1301,20 @@ class YOLONet(object):
             # detection filter -> RoI selection -> mask loss only feed the mask subnet's backward: side
             # lane, while the main lane finishes the mask subnet's forward, the YOLO loss and the heads'
             # backward.  The head logits (59 / 67 / 75) were produced on the side lane itself, so the
-            # filter starts as soon as they exist; only the mask loss waits for the main lane (layer 82)
+            # filter starts as soon as they exist; only the mask loss waits for the main lane (the score layer)
             L.set_lane(1)
         if self.shuffle_seed is not None:
             L.shuffle_perm(self.perm_det, self.perm_gt, self.B, int(self.shuffle_seed) & 0xffffffff, self.step_dev)
         self._detect(det_thresh)
-        Sm = self.S // 2
+        Sm = self.S // self.mask_stride
         L.mask_rois(self.detections, cfg.MAX_DETECTION, self.true_boxes, cfg.MAX_BOX_PER_IMAGE, self.perm_det,
                     self.perm_gt, self.B, Sm, cfg.MASK_ROI_DET, cfg.MASK_ROI_GT, cfg.MASK_ROI_IOU, self.rois,
                     self.roi_count, k=self.k)
         if side:
             L.lane_sync(0, 1)
-        m = self.by_idx[82]
+        m = self.by_idx[self.score_layer]
         L.psroi_loss(m.act, self.true_masks, cfg.MAX_BOX_PER_IMAGE, self.rois, self.roi_count, self.B, Sm, self.k,
-                     self.mask_scale, m.dx, self.mask_loss, self.ws_aux if side else self.ws)
+                     self.mask_scale, m.dx, self.mask_loss, self.ws_aux if side else self.ws, mask_stride=self.mask_stride)
         # the mask subnet's backward waits for THIS point of the side lane (not for the weight gradients
         # that lane picks up afterwards: a whole-lane sync there kept the main lane idle for 250-500 us)
         self._mask_mark = L.lane_mark(1) if side else -1
@@ -1489,7 +1524,7 @@ class YOLONet(object):
 
         for l in visit:
             pos = order.index(l) if not l.lock else -1
-            if l.idx == 82 and getattr(self, "_mask_loss_pending", False):
+            if l.idx == self.score_layer and getattr(self, "_mask_loss_pending", False):
                 L.lane_wait(self._mask_mark, 0)          # dscore comes from the side lane
                 self._mask_loss_pending = False
             if l.lock:

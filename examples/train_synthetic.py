@@ -50,6 +50,8 @@ def main():
     ap.add_argument("--out", default="/tmp/disyolo_example")
     ap.add_argument("--k-map", type=int, default=cfg.K_MAP, choices=(3, 5, 7),
                     help="position-sensitive mask grid (k x k score maps, cfg.K_MAP)")
+    ap.add_argument("--mask-stride", type=int, default=cfg.MASK_STRIDE, choices=(4, 2, 1),
+                    help="mask subnet: score maps at size/4, size/2 (cfg.MASK_STRIDE) or size (m = 1/4, 1/2, 1)")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     rng = np.random.RandomState(0)
@@ -57,7 +59,8 @@ def main():
 
     # --- train: stage 1 (conv1-52 locked), batches built on the GPU from the polygon records
     data = defect_train(labels, batch_size=args.batch, image_size=args.size, device=dev, rng=np.random.RandomState(1))
-    net = YOLONet(training=True, device=dev, image_size=args.size, batch_size=args.batch, stage=1, seed=0, k_map=args.k_map)
+    net = YOLONet(training=True, device=dev, image_size=args.size, batch_size=args.batch, stage=1, seed=0, k_map=args.k_map,
+                  mask_stride=args.mask_stride)
     solver = Solver(net, data, output_dir=args.out, max_iter=args.steps, summary_iter=max(1, args.steps // 4),
                     save_iter=args.steps, log=print)
     hist = solver.train()
@@ -67,7 +70,8 @@ def main():
     # --- test: reload the checkpoint the Solver wrote into an inference net
     prefix = checkpoint.latest_checkpoint(os.path.join(args.out, "checkpoint"))
     print("restoring", prefix)
-    inf = YOLONet(training=False, device=dev, image_size=args.size, batch_size=1, stage=1, seed=123, k_map=args.k_map)
+    inf = YOLONet(training=False, device=dev, image_size=args.size, batch_size=1, stage=1, seed=123, k_map=args.k_map,
+                  mask_stride=args.mask_stride)
     checkpoint.restore_net(inf, prefix)
     rec = labels[0]
     from disyolo_amd.evaluate import image_read

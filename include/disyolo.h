@@ -420,6 +420,13 @@ int disyolo_psroi_loss(const float* score, const uint8_t* true_masks, int G, con
                        const int32_t* roi_count, int B, int map_size, int k, float mask_scale,
                        void* dscore, float* loss, void* workspace, size_t workspace_bytes,
                        void* stream);
+/* disyolo_psroi_loss at any mask subnet stride: true_masks uint8 [B,G,s*Sm,s*Sm] sampled at
+ * [::s, ::s] (TF's legacy bilinear resize at an exact integer factor; identity at s = 1).
+ * mask_stride s = 1, 2 or 4 (score maps at S, S/2, S/4); disyolo_psroi_loss is its s = 2 case. */
+int disyolo_psroi_loss_s(const float* score, const uint8_t* true_masks, int G, const int32_t* rois,
+                         const int32_t* roi_count, int B, int map_size, int mask_stride, int k,
+                         float mask_scale, void* dscore, float* loss, void* workspace,
+                         size_t workspace_bytes, void* stream);
 /* inference assembly (val_test, :862-938): masks f32 [B,max_det,Sm,Sm] = sigmoid(selected
  * channel) inside the box, 0.5 outside; keep int32 [B,max_det] = 1 for rows with h>0 and w>0.
  * k = 3, 5 or 7; score f32 [B,Sm,Sm,k*k]. */
