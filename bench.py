@@ -11,6 +11,11 @@ selection + position-sensitive mask loss, backward (dgrad / wgrad / BN), Adam, w
 re-pack -- the work of ``sess.run([total_loss, optimizer])`` (train_yolo3_mask.py:216).
 Weak scaling: 8 images per GPU; gradients are all-reduced over RCCL, overlapped with
 backward.  One JSON line is printed by rank 0.
+
+A plain run measures the headline and nothing else: set-up, warm-up, the timed steps, the
+--dump-outputs arrays, the line.  --full adds what takes runs of its own: the box fingerprint,
+per-kernel HIP-event times and the roofline, the secondary workloads (child processes) and
+the CPU baseline.
 """
 import argparse
 import json
@@ -536,10 +541,15 @@ def main():
                     help="after the timed steps, write what the last step returned to its caller as DIR/<name>.npy: "
                          "train -- total_loss, loss_terms, trainable_variables (after the update), moving_statistics; "
                          "infer -- detections, det_count, masks, keep (a fixed, seeded sample of an array over 4 M elements)")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the stage-2 / B=32 inference lines of 'secondary'")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-kernel-events", action="store_true")
-    ap.add_argument("--no-box", action="store_true", help="skip the box fingerprint (rocm-smi + the 36^2 layer / 512 MB copy micro-benchmark)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the box fingerprint, per-kernel HIP-event times + roofline, the secondary "
+                         "workloads and the CPU baseline (each can be dropped again with its --no-* option)")
+    ap.add_argument("--no-secondary", action="store_true", help="--full: skip the stage-2 / B=32 inference lines of 'secondary'")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-kernel-events", action="store_true",
+                    help="skip the eager steps before the recorded step (--full: the per-kernel HIP-event times of the roofline)")
+    ap.add_argument("--no-box", action="store_true",
+                    help="--full: skip the box fingerprint (rocm-smi + the 36^2 layer / 512 MB copy micro-benchmark)")
     ap.add_argument("--pipeline", default="auto", choices=("auto", "on", "off"),
                     help="cross-step software pipeline of the locked backbone (stage 1): each step computes the "
                          "backbone forward of the NEXT batch on a third lane while it runs heads/losses/backward/Adam "
@@ -579,6 +589,8 @@ def main():
                     help="launch self-test (no GPU): every rank reports its RANK / LOCAL_RANK / WORLD_SIZE over a gloo group and "
                          "rank 0 prints them as one JSON line")
     args = ap.parse_args()
+    if not args.full:
+        args.no_secondary = args.no_cpu_baseline = args.no_box = True
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -670,16 +682,18 @@ def main():
         net.train_step(None, want_loss=False)
         n_trained[0] += 1
 
-    # per-kernel durations for the roofline: HIP events around every conv launch over K eager
+    # per-kernel durations for the roofline (--full): HIP events around every conv launch over K eager
     # steps of the same workload (events cannot time nodes inside a graph replay; the kernels
-    # and their arguments are identical in all three modes)
+    # and their arguments are identical in all three modes).  These steps train, so a plain run takes
+    # them too, without the events: the warm-up and the timed steps start from the same weights either way
     timer = None
     if not args.no_kernel_events:      # every rank runs these steps (they contain the collectives)
         for _ in range(2):
             step()
         torch.cuda.synchronize()
-        timer = L.KernelTimer()
-        L.TIMER = timer
+        if args.full:
+            timer = L.KernelTimer()
+            L.TIMER = timer
         for _ in range(args.steps):
             step()
         torch.cuda.synchronize()
@@ -736,7 +750,7 @@ def main():
     dp_trace = None
     if net.dp is not None and net.dp.inlist:
         dp_trace = net.dp.describe()     # the collectives are commands of the step: there is no host-side wait to trace
-    elif net.dp is not None:
+    elif net.dp is not None and args.full:
         # after the timed regions: a few steps with the exchange traced (events around every bucket's wait)
         net.dp.trace = []
         for _ in range(5):

@@ -127,3 +127,24 @@ def test_bench_fails_on_a_non_finite_loss(dev):
     bad = subprocess.run(cmd + ["--poison"], stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, timeout=600)
     line = json.loads([ln for ln in bad.stdout.decode().splitlines() if ln.startswith("{")][-1])
     assert bad.returncode == 3 and line["value"] is None and "non-finite" in line["error"]
+
+
+def test_plain_bench_run_trains_what_the_full_run_trains(dev, tmp_path):
+    """a plain bench.py run skips the box fingerprint and the per-kernel events but still takes the eager steps before
+    the recorded step: its dumped variables and losses equal those of a --full run bit for bit"""
+    import json
+    import subprocess
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--batch", "2", "--size", "64", "--steps", "2", "--warmup", "2",
+           "--autotune", "off"]
+    lines = {}
+    for mode, extra in (("plain", []), ("full", ["--full", "--no-secondary", "--no-cpu-baseline"])):
+        r = subprocess.run(cmd + extra + ["--dump-outputs", str(tmp_path / mode)], stdout=subprocess.PIPE,
+                           stderr=subprocess.DEVNULL, timeout=600)
+        assert r.returncode == 0, mode
+        lines[mode] = json.loads([ln for ln in r.stdout.decode().splitlines() if ln.startswith("{")][-1])
+    assert "roofline" not in lines["plain"] and lines["plain"]["config"]["box"] is None
+    assert "roofline" in lines["full"] and lines["full"]["config"]["box"] is not None
+    assert lines["plain"]["config"]["steps_trained"] == lines["full"]["config"]["steps_trained"]
+    for name in ("total_loss", "loss_terms", "trainable_variables", "moving_statistics"):
+        np.testing.assert_array_equal(np.load(tmp_path / "plain" / (name + ".npy")),
+                                      np.load(tmp_path / "full" / (name + ".npy")), err_msg=name)

@@ -19,7 +19,7 @@ try:
 except Exception:
     commit = os.environ.get("DISYOLO_COMMIT", "working tree")
 out = {"measured_at": (sys.argv[4] if len(sys.argv) > 4 else commit),
-       "method": "rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE in separate passes over `bench.py --no-cpu-baseline --no-secondary "
+       "method": "rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE in separate passes over `bench.py --full --no-cpu-baseline --no-secondary "
                  "--no-box` (the bench's own default steps / warm-up / repeats, committed tile table); per-kernel mean over all its launches (KiB); "
                  "FETCH_SIZE doubled (gfx950 counts 128-B requests at 64 B, MI355X_MICROARCH.md HBM section), WRITE_SIZE as is; "
                  "hbm_mb_per_launch_corrected = (2*fetch_kb + write_kb) * 1024 / 1e6",
