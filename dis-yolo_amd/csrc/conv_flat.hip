@@ -543,10 +543,6 @@ size_t flat_epilogue_bytes(const FlatShape& s) {
   return (size_t)s.xch_frags * 4096 + (size_t)s.nwaves * 32 * 80 + (size_t)s.nwaves * 64 * 2 * sizeof(float) + 2 * 64 * sizeof(float);
 }
 constexpr size_t LDS_MAX = 160 * 1024;
-int flat_stages_env() {      // DISYOLO_FLAT_STAGES=2: two stages everywhere (A/B of the pipeline depth)
-  static const int v = [] { const char* e = getenv("DISYOLO_FLAT_STAGES"); return e ? atoi(e) : 0; }();
-  return v;
-}
 
 template <int MW, int MI, int NWV, int NI, int KG, int ST>
 int launch_cfg(const ConvParams& q, int P, int FR, int HP, size_t lds, hipStream_t s) {
@@ -577,7 +573,7 @@ bool flat_ok(const disyolo_conv_desc* d, int id, FlatGeom* g) {
   const int np = flat_halo_pieces(fs.bm, d->W) + 9 * fs.bn / 16;
   if ((np + fs.nwaves - 1) / fs.nwaves > FLAT_DMAX) return false;        // DMA slots per wave
   if ((size_t)2 * np * 1024 > LDS_MAX) return false;
-  const bool three = (size_t)3 * np * 1024 <= LDS_MAX && d->C0 >= 96 && flat_stages_env() != 2;
+  const bool three = (size_t)3 * np * 1024 <= LDS_MAX && d->C0 >= 96;
   if (g) *g = FlatGeom{fs.bm, fs.bn, (int)((frame + fs.bm - 1) / fs.bm), three ? 3 : 2};
   return true;
 }
@@ -593,14 +589,11 @@ int launch_flat(const ConvParams& p, int id, hipStream_t s) {
   const int64_t frame = (int64_t)p.B * FR;
   q.tilesM = (int)((frame + fs.bm - 1) / fs.bm);
   q.tilesN = p.Cout / fs.bn;
-  {
-    static const bool on = [] { const char* e = getenv("DISYOLO_XCD_N"); return !(e && e[0] == '0'); }();
-    q.xcd_n = (on && q.tilesN >= 8 && (int64_t)p.bytesw > (int64_t)p.bytes0) ? 1 : 0;
-  }
+  q.xcd_n = (q.tilesN >= 8 && (int64_t)p.bytesw > (int64_t)p.bytes0) ? 1 : 0;
   const int HP = flat_halo_pieces(fs.bm, p.W);
   const size_t stage = (size_t)(HP + 9 * fs.bn / 16) * 1024;
   const size_t epi = flat_epilogue_bytes(fs);
-  const bool three = 3 * stage <= LDS_MAX && p.Cin >= 96 && flat_stages_env() != 2;
+  const bool three = 3 * stage <= LDS_MAX && p.Cin >= 96;
   size_t lds = (three ? 3 : 2) * stage;
   if (lds < epi) lds = epi;
   if (id == 24)

@@ -395,8 +395,7 @@ extern "C" int disyolo_conv2d_fp8_fwd(const disyolo_conv_desc* d, const void* w_
   // 64-pixel tiles when 128-pixel tiles would leave CUs without a block (the 18x18 / 36x36 maps at batch 8)
   const bool small = bk64 && d->Cout >= 128 && ceil_div(p.M, 128) * ceil_div(d->Cout, 128) < 256;
   // the block-scaled MFMA (K slices of 128 bytes) wherever the input has >= 128 channels: conv10-52 of the backbone
-  static const bool mx_on = [] { const char* e = getenv("DISYOLO_FP8_MX"); return !(e && e[0] == '0'); }();
-  const bool mx = mx_on && (d->C0 % 128) == 0 && d->Cout >= 128;
+  const bool mx = (d->C0 % 128) == 0 && d->Cout >= 128;
   if (small) {
     if (mx) launch_fp8<64, 128, 128, true>(p, s); else launch_fp8<64, 128, 64>(p, s);
   } else if (d->Cout > 64) {

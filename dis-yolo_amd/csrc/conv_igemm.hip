@@ -2016,12 +2016,8 @@ int launch_halo(const ConvParams& p, Patch pt, hipStream_t s) {
   const int tilesY = p.H / pt.ph, tilesX = p.W / pt.pw;
   q.tilesM = p.B * tilesY * tilesX;
   q.tilesN = ceil_div(p.Cout, BN);
-  {
-    static const bool on = [] { const char* e = getenv("DISYOLO_XCD_N"); return !(e && e[0] == '0'); }();
-    q.xcd_n = (on && q.tilesN >= 8 && (int64_t)p.bytesw > (int64_t)p.bytes0) ? 1 : 0;
-    static const bool split = [] { const char* e = getenv("DISYOLO_HALO_SPLIT_ROWS"); return !(e && e[0] == '0'); }();
-    q.halo_split = split ? 1 : 0;
-  }
+  q.xcd_n = (q.tilesN >= 8 && (int64_t)p.bytesw > (int64_t)p.bytes0) ? 1 : 0;
+  q.halo_split = 1;
   constexpr int SLAB = NW * 1024, BIM = (9 * BN * 4 + NW * 64 - 1) / (NW * 64);
   // two stages (compute slice c while slice c+1 lands); a one-slice layer (32 input channels) uses the first only.
   // The epilogue's scratch (stats rows + per-wave staging tiles) must fit as well.
@@ -2076,18 +2072,12 @@ int launch_ks(const ConvParams& p, hipStream_t s) {
   q.nk = p.K / BK;
   q.pcls = 0; q.Mc = 0; q.tilesMc = 0;
   if (KS == 3 && KG == 1 && p.dshift == 1 && !(p.Ho & 1) && !(p.Wo & 1) && !(p.flags & DISYOLO_CONV_STATS)) {
-    static const bool on = [] { const char* e = getenv("DISYOLO_DGRAD_PCLS"); return !(e && e[0] == '0'); }();
-    if (on) {
-      q.pcls = 1;
-      q.Mc = p.B * (p.Ho >> 1) * (p.Wo >> 1);
-      q.tilesMc = ceil_div(q.Mc, BM);
-      q.tilesM = 4 * q.tilesMc;
-    }
+    q.pcls = 1;
+    q.Mc = p.B * (p.Ho >> 1) * (p.Wo >> 1);
+    q.tilesMc = ceil_div(q.Mc, BM);
+    q.tilesM = 4 * q.tilesMc;
   }
-  {
-    static const bool on = [] { const char* e = getenv("DISYOLO_XCD_N"); return !(e && e[0] == '0'); }();
-    q.xcd_n = (on && q.tilesN >= 8 && (int64_t)p.bytesw > (int64_t)p.bytes0 + (int64_t)p.bytes1) ? 1 : 0;
-  }
+  q.xcd_n = (q.tilesN >= 8 && (int64_t)p.bytesw > (int64_t)p.bytes0 + (int64_t)p.bytes1) ? 1 : 0;
   const int grid = q.tilesM * q.tilesN;
   constexpr int NW = WM * WN, SLAB = 1024 * NW, ROWB = BK * 2;
   constexpr int A_BYTES = (BM * ROWB + SLAB - 1) / SLAB * SLAB, B_BYTES = (BN * ROWB + SLAB - 1) / SLAB * SLAB;
@@ -2121,9 +2111,7 @@ int launch_ks(const ConvParams& p, hipStream_t s) {
   constexpr size_t EXCL_LDS = (size_t)81 * 1024;
   if (cluster && lds < EXCL_LDS) lds = EXCL_LDS;
   if (tl_query.active) {
-    static const bool bwd_gemm_on = [] { const char* e = getenv("DISYOLO_BN_INKERNEL_BWD_GEMM"); return !(e && e[0] == '0'); }();
-    static const bool fwd_gemm_on = [] { const char* e = getenv("DISYOLO_BN_INKERNEL_FWD_GEMM"); return !(e && e[0] == '0'); }();
-    tl_query.have = KG == 1 && q.pcls == 0 && (tl_query.want_bwd ? (HAS_BWD && bwd_gemm_on) : fwd_gemm_on);
+    tl_query.have = KG == 1 && q.pcls == 0 && (!tl_query.want_bwd || HAS_BWD);
     tl_query.grid = grid;
     tl_query.rows = q.tilesM;
     tl_query.bn = BN;
@@ -2519,8 +2507,7 @@ extern "C" int disyolo_conv2d_bn_fused_ok(const disyolo_conv_desc* d) {
   const LaunchQuery q = tl_query;
   tl_query = LaunchQuery{};
   if (rc != DISYOLO_OK || !q.have) return 0;          // (a kernel without the epilogue: streaming / flat-frame forms, split-K tiles)
-  static const int max_row_kb = [] { const char* e = getenv("DISYOLO_BN_INKERNEL_ROW_KB"); return e ? atoi(e) : 128; }();
-  if ((int64_t)q.rows * q.bn * 8 > (int64_t)max_row_kb * 1024) return 0;      // every block sums all the rows of its channel tile
+  if ((int64_t)q.rows * q.bn * 8 > 128 * 1024) return 0;      // every block sums all the rows of its channel tile
   return (q.resident > 0 && q.grid <= q.resident) ? 1 : 0;
 }
 

@@ -336,7 +336,7 @@ struct Wg3Params {
   int tilesCi, tilesCo, tiles;
   int leadA, leadB;
   unsigned bytesx, bytesy;
-  int debug;  // DISYOLO_WG3_DEBUG ablations (1: no epilogue stores, 2: no main loop, 4: no DMA in the loop)
+  int debug;  // ablation bits the kernel still tests; the host always passes 0 (1: no epilogue stores, 2: no main loop, 4: no DMA in the loop)
 };
 
 struct PixState {
@@ -812,18 +812,13 @@ __global__ __launch_bounds__(512) void conv_first_wgrad_mfma_kernel(const float*
     slab[o] = ((red[o] + red[1024 + o]) + (red[2048 + o] + red[3072 + o])) + ((red[4096 + o] + red[5120 + o]) + (red[6144 + o] + red[7168 + o]));
 }
 
-int env_int(const char* name, int dflt) {
-  const char* v = getenv(name);
-  return (v && v[0]) ? atoi(v) : dflt;
-}
 void plan(const disyolo_conv_desc* d, int* bn, int* splits, int* steps_per_split, int* steps) {
   const int M = d->B * d->Ho * d->Wo;
   const int K = d->ksize * d->ksize * (d->C0 + d->C1);
   *bn = d->Cout > 64 ? 128 : (d->Cout > 32 ? 64 : 32);
   const int tiles = ceil_div(K, 128) * ceil_div(d->Cout, *bn);
   *steps = ceil_div(M, 32);
-  static const int target = env_int("DISYOLO_WG_BLOCKS", 256);
-  static const int min_steps = env_int("DISYOLO_WG_MINSTEPS", 16);
+  const int target = 256, min_steps = 16;
   int s = target / tiles;  // fill the 256 CUs about twice; a full grid needs no pixel split
   if (s < 1) s = 1;
   const int max_s = ceil_div(*steps, min_steps);
@@ -834,50 +829,44 @@ void plan(const disyolo_conv_desc* d, int* bn, int* splits, int* steps_per_split
 }
 
 
+constexpr int WG3_ST = 3;     // pipeline stages of the gradient image (prefetch depth WG3_ST - 1)
 struct Plan3 {
-  int co_t, R, splits, cps, chunks, tilesCi, tilesCo, leadA, leadB, st, s2;
+  int co_t, R, splits, cps, chunks, tilesCi, tilesCo, leadA, leadB, s2;
   size_t lds;
 };
 // tap-fused kernel: 3x3, SAME pads, no fused concat, 32 | Cin, 4 | Cout; stride 1, or stride 2 on even maps (pad 0 before,
 // 1 after) where four rings of 8 chunks fit (output rows up to 319 pixels)
 bool plan3(const disyolo_conv_desc* d, int opts, Plan3* q) {
-  static const int enabled = env_int("DISYOLO_WG3", 1);
-  static const int s2_enabled = env_int("DISYOLO_WG3_S2", 1);
   // blocks aimed at per launch.  192, not one per CU: in the step these kernels run on the side lane beside the main
   // lane's data-gradient convs, and a grid that leaves a quarter of the CUs free costs the weight gradient less than it gives
   // the critical chain (interleaved A/B, ms per step at 256 / 192 / 160: stage 1 4.181 / 4.162 / 4.162, stage 2 9.849 / 9.807 /
   // 9.846, 832^2 4.312 / 4.297 / 4.286; 384 and 512: +4 %)
-  static const int target = env_int("DISYOLO_WG3_BLOCKS", 192);
-  if (!enabled || (opts & DISYOLO_WGRAD_IM2COL)) return false;
+  const int target = 192;
+  if (opts & DISYOLO_WGRAD_IM2COL) return false;
   if (d->ksize != 3 || d->C1 != 0 || d->in_div != 1 || d->C0 % 32 || d->Cout % 4 || d->Cout < 32) return false;
   q->s2 = 0;
   if (d->stride == 2) {
-    if (!s2_enabled || d->pad_t != 0 || d->pad_l != 0 || (d->H & 1) || (d->W & 1) || d->Ho * 2 != d->H || d->Wo * 2 != d->W) return false;
+    if (d->pad_t != 0 || d->pad_l != 0 || (d->H & 1) || (d->W & 1) || d->Ho * 2 != d->H || d->Wo * 2 != d->W) return false;
     q->s2 = 1;
   } else if (d->stride != 1 || d->pad_t != 1 || d->pad_l != 1 || d->Ho != d->H || d->Wo != d->W) {
     return false;
   }
   const int P = d->Wo + 1, Hp = d->Ho + 1;
-  static const int cot_env = env_int("DISYOLO_WG3_COT", 0);
   q->co_t = d->Cout > 64 ? 128 : 64;
-  if (cot_env == 64) q->co_t = 64;
   // A layer whose 128-channel tiles would need exactly two pixel splits gets 64-channel tiles and no split
   // instead: same block count, the gradient is stored once, no partial sums to write and re-read.
-  if (cot_env == 0 && q->co_t == 128) {
+  if (q->co_t == 128) {
     const int t128 = (d->C0 / 32) * ceil_div(d->Cout, 128);
     if ((target + t128 / 2) / t128 == 2) q->co_t = 64;
   }
   q->leadB = q->s2 ? 0 : ceil_div(P + 1, 64);
   q->leadA = 1 + P / 64;
   if (q->s2) q->co_t = 64;                // (four rings: 132 KiB of input, 24 KiB of gradient stages)
-  static const int st_env = env_int("DISYOLO_WG3_ST", 3);
-  q->st = st_env < 3 ? 3 : (st_env > 5 ? 5 : st_env);     // pipeline stages of the gradient image (prefetch depth st - 1)
+  const int need = (WG3_ST - 1) + q->leadA + q->leadB + 1;
+  q->R = need <= 8 ? 8 : (need <= 16 ? 16 : 32);
   for (;;) {
-    const int need = (q->st - 1) + q->leadA + q->leadB + 1;
-    q->R = need <= 8 ? 8 : (need <= 16 ? 16 : 32);
-    q->lds = (size_t)(q->s2 ? 4 : 1) * ((size_t)q->R * 4096 + 1024) + (size_t)q->st * 64 * (size_t)q->co_t * 2;
+    q->lds = (size_t)(q->s2 ? 4 : 1) * ((size_t)q->R * 4096 + 1024) + (size_t)WG3_ST * 64 * (size_t)q->co_t * 2;
     if (need <= 32 && q->lds <= 160 * 1024) break;
-    if (q->st > 3) { --q->st; continue; }
     if (q->co_t == 128) { q->co_t = 64; continue; }
     return false;
   }
@@ -893,39 +882,28 @@ bool plan3(const disyolo_conv_desc* d, int opts, Plan3* q) {
   q->splits = ceil_div(q->chunks, q->cps);
   return true;
 }
-template <int CO_T, int R, int NW, int ST>
-int launch3s(const Wg3Params& p, const Plan3& q, hipStream_t s) {
+template <int CO_T, int R>
+int launch3(const Wg3Params& p, const Plan3& q, hipStream_t s) {
   static bool attr_done = false;
-  auto fn = conv_wgrad3x3_kernel<CO_T, R, ST, NW>;
+  auto fn = conv_wgrad3x3_kernel<CO_T, R, WG3_ST, 4>;
   if (!attr_done) {
     if (hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
       (void)hipGetLastError();
     }
     attr_done = true;
   }
-  hipLaunchKernelGGL(fn, dim3(q.tilesCi * q.tilesCo * q.splits), dim3(NW * 64), q.lds, s, p);
+  hipLaunchKernelGGL(fn, dim3(q.tilesCi * q.tilesCo * q.splits), dim3(256), q.lds, s, p);
   return 0;
-}
-template <int CO_T, int R, int NW>
-int launch3w(const Wg3Params& p, const Plan3& q, hipStream_t s) {
-  if (q.st == 5) return launch3s<CO_T, R, NW, 5>(p, q, s);
-  if (q.st == 4) return launch3s<CO_T, R, NW, 4>(p, q, s);
-  return launch3s<CO_T, R, NW, 3>(p, q, s);
 }
 int launch3_s2(const Wg3Params& p, const Plan3& q, hipStream_t s) {
   static bool attr_done = false;
-  auto fn = conv_wgrad3x3_kernel<64, 8, 3, 4, 1>;
+  auto fn = conv_wgrad3x3_kernel<64, 8, WG3_ST, 4, 1>;
   if (!attr_done) {
     if (hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) (void)hipGetLastError();
     attr_done = true;
   }
   hipLaunchKernelGGL(fn, dim3(q.tilesCi * q.tilesCo * q.splits), dim3(256), q.lds, s, p);
   return 0;
-}
-template <int CO_T, int R>
-int launch3(const Wg3Params& p, const Plan3& q, hipStream_t s) {
-  static const int waves = env_int("DISYOLO_WG3_WAVES", 4);
-  return waves == 4 ? launch3w<CO_T, R, 4>(p, q, s) : launch3w<CO_T, R, 8>(p, q, s);
 }
 
 }  // namespace
@@ -993,8 +971,7 @@ extern "C" int disyolo_conv2d_wgrad(const disyolo_conv_desc* d, const void* dy, 
     p.bytesx = (unsigned)((size_t)d->B * d->H * d->W * d->C0 * 2);
     p.bytesy = (unsigned)((size_t)d->B * d->Ho * d->Wo * dy_ld * 2);
     p.out = q3.splits == 1 ? dw : (float*)workspace;
-    static const int dbg = env_int("DISYOLO_WG3_DEBUG", 0);
-    p.debug = dbg;
+    p.debug = 0;
     hipStream_t s = (hipStream_t)stream;
     if (opts & DISYOLO_WGRAD_REDUCE_ONLY) goto reduce3;
     if (q3.s2) {
@@ -1084,8 +1061,7 @@ extern "C" int disyolo_conv_first_wgrad(const float* images, const void* dy, flo
   const int64_t M = (int64_t)B * H * W;
   hipStream_t s = (hipStream_t)stream;
   const int64_t n = 27 * Cout;
-  static const int use_mfma = env_int("DISYOLO_FIRST_WGRAD_MFMA", 1);
-  if (Cout == 32 && use_mfma && M * 64 < (1LL << 31)) {
+  if (Cout == 32 && M * 64 < (1LL << 31)) {
     // the matrix-core form (the layer as the reference builds it: 32 filters, yolo/yolo3_net_pos.py:159)
     const int units_x = ceil_div(W, 128);
     const int nunits = B * H * units_x;

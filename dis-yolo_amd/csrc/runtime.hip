@@ -106,7 +106,7 @@ int dy_record(std::function<int(void*)> fn) {
 // DISYOLO_LANE1_LOW=0 keeps it at normal priority (the cut-list data-parallel step does: its RCCL all-reduces are issued on
 // this lane).  lane 2 carries work that must only fill the other lanes' bubbles (the next step's backbone); lane 3 the
 // data-parallel step's RCCL collectives and the optimizer sweeps behind them (lowest priority like lane 1: the HBM-bound sweeps
-// must not compete with the main lane -- one RCCL rank: 4.22 -> 4.17 ms, the plain step's time; DISYOLO_LANE3_LOW=0: normal).
+// must not compete with the main lane -- one RCCL rank: 4.22 -> 4.17 ms, the plain step's time).
 constexpr int MAXDEV = 16;
 static hipStream_t g_pool_dev[MAXDEV][NLANES] = {};      // one pool per device (the product runs one process per GPU; tests may not)
 static hipStream_t* cur_pool() {
@@ -205,10 +205,8 @@ static bool pool_lane(int i, hipStream_t caller = nullptr) {
   const char* l1 = getenv("DISYOLO_LANE1_LOW");
   const bool lane1_low = !(l1 && l1[0] == '0');
   if (hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess) return false;   // no device (CPU-only build check)
-  // lane 2 (the pipelined step's next-batch backbone): lowest priority as well since round 6 (+1.2 ... +1.5 % on the pipelined step;
-  // DISYOLO_LANE2_LOW=0: normal)
-  const bool lane2_low = !(getenv("DISYOLO_LANE2_LOW") && getenv("DISYOLO_LANE2_LOW")[0] == '0');
-  const bool low = (i == 2 && lane2_low) || (i == 1 && lane1_low) || (i == 3 && !(getenv("DISYOLO_LANE3_LOW") && getenv("DISYOLO_LANE3_LOW")[0] == '0'));
+  // lane 2 (the pipelined step's next-batch backbone): lowest priority as well since round 6 (+1.2 ... +1.5 % on the pipelined step)
+  const bool low = i == 2 || i == 3 || (i == 1 && lane1_low);
   const int prio = low ? least : 0;
   rep.priority = prio;
 #ifndef DY_HOST_ONLY

@@ -751,8 +751,7 @@ def conv2d_wgrad(d: ConvDesc, dy, dy_ld: int, dw, ws: Workspace, opts: int = 0) 
     if TIMER is not None and not (opts & (WGRAD_PARTIAL_ONLY | WGRAD_REDUCE_ONLY)):
         # the partial-sum kernel and the slab reduction as two timed launches (same work, same order)
         kind, tn, ring, splits = conv2d_wgrad_plan(d, opts)
-        waves = 8 if os.environ.get("DISYOLO_WG3_WAVES") == "8" else 4
-        name = ("conv_wgrad3x3_kernel<%d,%d,3,%d,0>" % (tn, ring, waves)) if kind == 1 else ("conv_wgrad_kernel<%d,3>" % tn)
+        name = ("conv_wgrad3x3_kernel<%d,%d,3,4,0>" % (tn, ring)) if kind == 1 else ("conv_wgrad_kernel<%d,3>" % tn)
         if kind == 1 and d.stride == 2:
             name = "conv_wgrad3x3_kernel<64,8,3,4,1>"
         TIMER.run(name, conv_flops(d), lambda: call(opts | WGRAD_PARTIAL_ONLY))
@@ -776,10 +775,6 @@ def conv_first_wgrad(images, dy, dw, ws: Workspace) -> None:
     buf = ws.get(need)
     _check(load().disyolo_conv_first_wgrad(_p(images), _p(dy), _p(dw), B, H, W, cout, _p(buf), buf.numel(), _stream()),
            "conv_first_wgrad")
-
-
-def image_pad8(images, out) -> None:
-    _check(load().disyolo_image_pad8(_p(images), _p(out), images.numel() // 3, _stream()), "image_pad8")
 
 
 def copy2d_f32(src, dst, rows, cols, src_ld, dst_ld) -> None:

@@ -29,6 +29,10 @@ from . import lib as L
 BF16 = torch.bfloat16
 F32 = torch.float32
 
+# Tuned numbers of the recorded step (the A/B runs behind them: profiles/HISTORY.md, "retired switches")
+WGRAD_GROUP = 3                 # consecutive layers whose weight gradients share one main-lane edge (backward: 1 / 2 / 4 / 6 lost)
+OPT_CHUNK_ELEMS = 8_000_000     # variables per optimizer slice (_plan_opt_chunks; 4 ... 32 M measured)
+PIPE_LANE = 2                   # the pipelined step's next-batch backbone runs on this lane (lowest priority, csrc/runtime.hip)
 
 
 class Layer:
@@ -213,14 +217,13 @@ class YOLONet(object):
         # next replay waits, tensor by tensor, for the side-lane work that still reads it (cmdlist slots)
         self._overlap = False
         self._overlap_rec = False      # while such a step is being recorded
-        self._dp_pending = []          # data parallel, exchange in the list: slices exchanged and not yet swept
         self._tail_open = False        # a replay's side lane may still be running: join before anything but the next replay
         self._progs = None      # [parity] -> (list, marks, bwd_end) of the pipelined step
         # conv1 + conv2 as ONE launch wherever both run in inference mode (the locked backbone of stage 1, every inference
         # net): conv1's output -- 170 MB at B = 8, one consumer, unused by the active mask subnet (yolo/yolo3_net_pos.py:163)
         # -- is then never written, and ``by_idx[1].act`` is NOT filled.  Set to False to get every layer's output.
-        self.fuse_first_two = os.environ.get("DISYOLO_FUSE12", "1") != "0"
-        self.fuse_blocks = os.environ.get("DISYOLO_FUSE_BLOCKS", "1") != "0"
+        self.fuse_first_two = True
+        self.fuse_blocks = True
         self.use_side_lane = os.environ.get("DISYOLO_SIDE_LANE", "1") != "0"
         # training-mode batch norm INSIDE the conv launches of the main lane (DISYOLO_CONV_BN_FUSED, csrc/conv_common.h
         # "cluster exchange"): wherever a trainable layer's whole grid is resident at once, its bn_finalize + bn_act_fwd
@@ -237,10 +240,8 @@ class YOLONet(object):
         # data-gradient conv's epilogue ALSO runs the plain column reduction on the same gradient (eager steps only) and
         # appends the relative differences of dx / dgamma / dbeta
         self.bn_fuse_check = None
-        if os.environ.get("DISYOLO_EXP_SKIP_WGRAD") in ("1", "2"):
-            print("disyolo: DISYOLO_EXP_SKIP_WGRAD is set -- weight gradients are NOT computed (timing experiment)", file=sys.stderr)
-        # weight gradients of the last layers of the backward pass stay on the main lane (tuned below)
-        self.tail_on_main = int(os.environ.get("DISYOLO_TAIL_MAIN", "0"))
+        # weight gradients of the last layers of the backward pass stay on the main lane (build_program sets it for the pipelined step)
+        self.tail_on_main = 0
         # backbone_pair (stage 1): the locked backbone -- whose output depends on nothing a step updates -- runs ONCE
         # per TWO batches at batch size 2B (a 576^2 B = 8 layer is a one-round grid: 169 us per image at B = 8, 137 at
         # B = 16), the trainable part steps through the two halves one after the other.  Every image still passes
@@ -412,19 +413,16 @@ class YOLONet(object):
         # device memory gets later allocations on worse-mapped memory (B = 32 inference 4.8 -> 3.9 k img/s after
         # 13 GB of tensors were created and freed, no compute involved: tools/micro/infer_after_alloc.py), and
         # one large region fares better than eighty medium ones
-        use_arena = os.environ.get("DISYOLO_ARENA", "1") != "0"
         need = 0
         batch_of = lambda l: 2 * B if (self.pair and l.idx <= self._pair_P) else B
         for l in self.layers:
             n = batch_of(l) * l.Ho * l.Wo * l.cout
             tb = self.training and (not l.lock) and l.kind != "lin"
             need += ((n * (4 if l.kind == "lin" else 2) + 255) // 256) * 256 * (2 if tb else 1)
-        self._act_arena = torch.zeros(need, dtype=torch.uint8, device=dev) if use_arena else None
+        self._act_arena = torch.zeros(need, dtype=torch.uint8, device=dev)
         cursor = [0]
 
         def zeros4(b, h, w, c, dtype):
-            if self._act_arena is None:
-                return torch.zeros(b, h, w, c, dtype=dtype, device=dev)
             nbytes = b * h * w * c * (4 if dtype == F32 else 2)
             t = self._act_arena[cursor[0]:cursor[0] + nbytes].view(dtype).view(b, h, w, c)
             cursor[0] += ((nbytes + 255) // 256) * 256
@@ -462,9 +460,6 @@ class YOLONet(object):
             self._plan_fp8()
         l1 = self.by_idx[1]
         if self.training and not l1.lock:
-            self._img8 = torch.zeros(B, S, S, 8, dtype=BF16, device=dev)
-            self._dw8 = torch.zeros(3, 3, 8, l1.cout, dtype=F32, device=dev)
-            self._wgrad1_desc = L.make_conv_desc(self._img8, l1.dx, l1.dx, 3, 1)
             l1.stats_rows = L.colstats_rows(B * S * S, l1.cout)
             l1.stats = torch.zeros(l1.stats_rows, l1.cout, 2, dtype=F32, device=dev)
             self._ones32 = torch.ones(l1.cout, dtype=F32, device=dev)
@@ -511,8 +506,7 @@ class YOLONet(object):
                 if l.dx is not None and l.kind != "lin":
                     need = max(need, L.load().disyolo_bn_act_bwd_workspace(B * l.Ho * l.Wo, l.cout))
             if not l1.lock:
-                need = max(need, L.conv2d_wgrad_workspace(self._wgrad1_desc),
-                           L.load().disyolo_conv_first_wgrad_workspace(B, S, S, l1.cout))
+                need = max(need, L.load().disyolo_conv_first_wgrad_workspace(B, S, S, l1.cout))
             self.ws.get(int(need))
             self.ws_aux.get(int(need))
         self.ws_det.get(int(max(L.load().disyolo_detect_workspace(B, S, self.num_class), 1 << 20)))
@@ -715,7 +709,7 @@ class YOLONet(object):
         stream too.)  Data parallel: lane 3 is taken, a plain lowest-priority stream has to do."""
         if self.device.type != "cuda":
             return
-        if self.dp is None and os.environ.get("DISYOLO_FEED_LANE", "1") != "0":
+        if self.dp is None:
             self.feed_stream = self._progs[0][0].lane_stream(L.COMM_LANE, self.device)
             return
         try:
@@ -775,7 +769,6 @@ class YOLONet(object):
                 kw = dict(w=l.wdg, pads=pads, out_hw=(l.H, l.W))
                 # the shallow stride-2 layers (conv2, conv5): data gradient as one 2x2-tap conv over dy (lib.dgrad_s2_quad)
                 if (l.k == 3 and l.stride == 2 and l.H % 2 == 0 and l.W % 2 == 0 and l.pad_t == 0 and l.pad_l == 0
-                        and os.environ.get("DISYOLO_DGRAD_QUAD", "1") != "0"
                         and L.dgrad_s2_quad_ok(self.B, l.Ho, l.Wo, l.cout, l.cin)):
                     if getattr(l, "wq", None) is None:
                         l.wq = torch.zeros(4 * l.cin, 9 * l.cout, dtype=BF16, device=self.device)
@@ -844,10 +837,6 @@ class YOLONet(object):
             else:
                 self._forward_layer(l, is_training)
                 self._fp8_handover(l)
-            hook = getattr(self, "_fwd_hook", None)
-            if hook is not None and hook[0] == l.idx and L.CURRENT_LANE == 0:
-                self._fwd_hook = None
-                hook[1]()
         if self.use_side_lane:
             L.set_lane(0)
             L.lane_sync(1, 0)
@@ -893,7 +882,7 @@ class YOLONet(object):
         # released by the end of the tail: the wait for the whole tail moves up to it (one backbone layer less of overlap)
         self._xstep_waits = {src: s for src, s in self._xstep_slot.items()}
         self._xstep_all_merged = False
-        if self.use_side_lane and self.tail_on_main == 0 and self._xstep_slot and os.environ.get("DISYOLO_XSTEP_MERGE", "1") != "0":
+        if self.use_side_lane and self.tail_on_main == 0 and self._xstep_slot:
             late = [src for src in self._xstep_slot if self._xstep_reader[src] == order[-1]]
             early = [src for src in self._xstep_slot if src not in late]
             self._xstep_waits = {}
@@ -1425,28 +1414,20 @@ class YOLONet(object):
         # lane still runs the detection filter and the mask loss; the mask subnet follows.
         visit = self.backward_order()
         order = [l for l in visit if not l.lock]
-        fuse_bn = os.environ.get("DISYOLO_BN_FUSE", "1") != "0" and not self.sync_bn
-        final_of = self._final_writers(visit) if fuse_bn else {}
+        final_of = {} if self.sync_bn else self._final_writers(visit)
         for l in self.layers:
             l.bwd_part_rows = 0
             l.fused_bwd = False
         # (data parallelism with a cut list: the sweep must follow the bucket's all-reduce -- it stays in optimizer_step;
         # with the exchange in the list the slice's all-reduce and its sweep go to the exchange lane together)
         inl = self.dp is not None and self.dp.inlist
-        overlap_opt = sweep and (self.dp is None or inl) and self.n_params > 0 and os.environ.get("DISYOLO_OPT_OVERLAP", "1") != "0"
+        overlap_opt = sweep and (self.dp is None or inl) and self.n_params > 0
         if overlap_opt:
             if self.opt_chunks is None:
                 self._plan_opt_chunks()
             self._opt_swept = set()
             self._opt_done = [set() for _ in self.opt_chunks]
-            self._dp_pending = []        # (slice, mark of its collective on the exchange lane, layer position): exchanged, not yet swept
-            self._dp_sweep_delay = int(os.environ.get("DISYOLO_DP_SWEEP_DELAY", "2"))
-            # where a slice's sweep runs: "comm" = on the exchange lane right behind the slice's collective (default: a hop
-            # between lanes costs ~15 us, profiles/r05_hw_queues.txt, and the side lane is nearly as busy as the main one),
-            # "side" = back on the side lane DISYOLO_DP_SWEEP_DELAY layers later
-            self._dp_sweep_on_comm = self._dp_sweep_lane() != 1
-        group = max(1, int(os.environ.get("DISYOLO_WGRAD_GROUP", "3")))
-        pending: list = []            # (layer, dx, ld, M, side, pos) whose weight gradients wait for the group's edge
+        pending: list = []            # (layer, dx, ld, M, side) whose weight gradients wait for the group's edge
 
         def flush():
             if not pending:
@@ -1454,7 +1435,7 @@ class YOLONet(object):
             side_g = pending[0][4]
             mark = L.lane_mark(0) if side_g else None         # ONE record on the main lane for the whole group
             waited = False
-            for (pl, pdx, pld, pM, pside, ppos) in pending:
+            for (pl, pdx, pld, pM, pside) in pending:
                 if pside:
                     if not waited:
                         L.lane_wait(mark, 1)
@@ -1462,21 +1443,15 @@ class YOLONet(object):
                     L.set_lane(1)
                 # scratch of the lane the gradient runs on: the side lane's weight gradients own ws_aux; one kept on the main lane
                 # (tail_on_main) must not share it -- the side lane may still be inside an earlier layer's slabs (found in round 6:
-                # with DISYOLO_TAIL_MAIN > 0 the loss differed from run to run)
+                # with tail_on_main > 0 the loss differed from run to run)
                 wsl = self.ws_aux if pside else self.ws
                 if pl.kind == "lin":
                     L.colsum(pl.dx, pl.dbias, pM, pl.cout_pad, pl.cout, wsl)   # bias gradient
                 if pl.idx == 1:
-                    if pl.cout == 32 and os.environ.get("DISYOLO_FIRST_WGRAD_MFMA", "1") != "0":
-                        # the first layer's own kernel: taps as the M axis of the MFMA, the f32 image rounded to bf16 on
-                        # its way into LDS (csrc/conv_wgrad.hip, conv_first_wgrad_mfma_kernel)
-                        L.conv_first_wgrad(self.images, pl.dx, pl.dw, wsl)
-                    else:
-                        # through the im2col kernel: bf16 image padded to 8 channels, K = 9*8 rows of which 27 are real
-                        L.image_pad8(self.images, self._img8)
-                        L.conv2d_wgrad(self._wgrad1_desc, pl.dx, pl.cout, self._dw8, wsl)
-                        L.copy2d_f32(self._dw8, pl.dw, 9, 3 * pl.cout, 8 * pl.cout, 3 * pl.cout)
-                elif os.environ.get("DISYOLO_EXP_SKIP_WGRAD") not in ("1", "2"):     # (experiment: the step without its weight gradients)
+                    # the first layer's own kernel: taps as the M axis of the MFMA, the f32 image rounded to bf16 on
+                    # its way into LDS (csrc/conv_wgrad.hip, conv_first_wgrad_mfma_kernel)
+                    L.conv_first_wgrad(self.images, pl.dx, pl.dw, wsl)
+                else:
                     L.conv2d_wgrad(pl.wgrad_desc, pdx, pld, pl.dw, wsl)
                 if pside:
                     L.set_lane(0)
@@ -1495,29 +1470,23 @@ class YOLONet(object):
                         if inl:
                             # data parallel: the slice's gradients are summed over the ranks first -- the collective goes to
                             # the exchange lane (behind the side lane's weight gradients of the slice; the side lane itself
-                            # goes on with the next layers' weight gradients), and the sweep of a slice is issued a few
-                            # layers later (DISYOLO_DP_SWEEP_DELAY), on the side lane like the single-GPU step's: its
-                            # collective has had those layers' time on the links before the side lane sits behind it
+                            # goes on with the next layers' weight gradients) ...
                             L.lane_wait(L.lane_mark(1), L.COMM_LANE)
                             L.set_lane(L.COMM_LANE)
                             ch = self.opt_chunks[ci]
                             self.dp.exchange_inlist(ci, ch["off"], ch["cnt"])
-                            if self._dp_sweep_on_comm:
-                                # ... and the sweep right behind it on the exchange lane (lowest stream priority, like the side
-                                # lane the single-GPU step sweeps on): the side lane never waits for the links; its mark sits
-                                # behind the group's main-lane edge, so the re-pack is safe
-                                self._sweep_chunk(ci, 1.0 / self.dp.world_size)
-                            else:
-                                self._dp_pending.append((ci, L.lane_mark(L.COMM_LANE), ppos))
+                            # ... and the sweep right behind it on the exchange lane (lowest stream priority, like the side
+                            # lane the single-GPU step sweeps on): the side lane never waits for the links; its mark sits
+                            # behind the group's main-lane edge, so the re-pack is safe.  (A hop between lanes costs ~15 us,
+                            # profiles/r05_hw_queues.txt, and the side lane is nearly as busy as the main one.  One RCCL rank,
+                            # same box, ms per step: plain 4.16-4.18 | this 4.17-4.18 | exchange lane at normal priority 4.22 |
+                            # the sweep back on the side lane two layers later 4.20)
+                            self._sweep_chunk(ci, 1.0 / self.dp.world_size)
                             L.set_lane(0)
                         else:
                             L.set_lane(1)
                             self._sweep_chunk(ci, 1.0)
                             L.set_lane(0)
-                if overlap_opt and inl:
-                    # the sweep of a slice follows its collective DISYOLO_DP_SWEEP_DELAY layers later, on the side lane
-                    while self._dp_pending and ppos - self._dp_pending[0][2] >= self._dp_sweep_delay:
-                        self._dp_sweep_oldest(1, main_waited=pside)
                 if on_layer_done is not None:
                     on_layer_done(pl)
             pending.clear()
@@ -1542,8 +1511,7 @@ class YOLONet(object):
                 sc = self.by_idx[l.shortcut] if l.shortcut is not None else None
                 if sc is not None and sc.grad is None:
                     sc = None
-                fuse_sc = sc is not None and os.environ.get("DISYOLO_SHORTCUT_FUSE", "1") != "0"
-                kw = dict(shortcut_grad=sc.grad, shortcut_accumulate=sc.grad_set) if fuse_sc else {}
+                kw = dict(shortcut_grad=sc.grad, shortcut_accumulate=sc.grad_set) if sc is not None else {}
                 if l.fused_bwd:
                     pass        # l.dx, l.dgamma, l.dbeta came out of the data-gradient conv that made l.grad final (_accumulate_into)
                 elif self.sync_bn:
@@ -1579,8 +1547,6 @@ class YOLONet(object):
                                  self.ws, cfg.ALPHA, **kw)
                 dx, ld = l.dx, l.cout
                 if sc is not None:
-                    if not fuse_sc:
-                        L.add_bf16(l.grad, sc.grad, accumulate=sc.grad_set)
                     sc.grad_set = True
             # the weight gradient is off the critical chain (dx -> dgrad -> next layer's BN
             # backward): in a recorded step it runs on the side lane, overlapping the small
@@ -1590,13 +1556,13 @@ class YOLONet(object):
             # (data parallelism with a CUT list: every weight gradient stays on the side lane -- the bucket all-reduce is ordered
             # after that lane only.  With the exchange in the list the slices whose last weight gradient ran on the main lane are
             # exchanged and swept in optimizer_step, whose exchange lane waits for the main lane, which has joined the side lane)
-            tail = self.tail_on_main if (self.dp is None or (inl and os.environ.get("DISYOLO_DP_TAIL_MAIN", "1") != "0")) else 0
-            side = self.use_side_lane and (pos < len(order) - tail) and os.environ.get("DISYOLO_EXP_SKIP_WGRAD") != "2"
+            tail = self.tail_on_main if (self.dp is None or inl) else 0
+            side = self.use_side_lane and (pos < len(order) - tail)
             # enqueue order = host order: the data-gradient convs (critical chain, main lane) are issued before the
             # weight gradient, which only needs dx.  The edge to the side lane is an event RECORDED ON THE MAIN LANE, and a
             # record costs the recording stream ~3 us (tools/micro/event_cost.hip: a chain of 10-us kernels, 11.0 -> 13.8 us
             # per kernel with a record behind each, 12.0 with one per three): one edge per layer was ~0.1 ms of a 4.1-ms
-            # step.  So the weight gradients of DISYOLO_WGRAD_GROUP consecutive layers share ONE edge, recorded behind the
+            # step.  So the weight gradients of WGRAD_GROUP consecutive layers share ONE edge, recorded behind the
             # group's data-gradient convs; the side lane lags a layer or two more, which nothing waits for.
             for mode, tgt, kw in l.dgrad_descs:
                 if mode == "direct":
@@ -1611,8 +1577,8 @@ class YOLONet(object):
                     up.grad_set = True
             if pending and pending[-1][4] != side:
                 flush()
-            pending.append((l, dx, ld, M, side, pos))
-            if not side or len(pending) >= group:
+            pending.append((l, dx, ld, M, side))
+            if not side or len(pending) >= WGRAD_GROUP:
                 flush()
         flush()
         if not self._overlap_rec:
@@ -1687,7 +1653,7 @@ class YOLONet(object):
     # ---- optimizer: Adam as sweeps over slices of the arena ------------------------------
     def _plan_opt_chunks(self) -> None:
         """Slices of the regularised region [0, n_decay) in layer order, a few million variables each
-        (DISYOLO_OPT_CHUNK_M, default 8).  A slice can be swept as soon as the weight gradients of its
+        (OPT_CHUNK_ELEMS).  A slice can be swept as soon as the weight gradients of its
         layers are final; each slice also owns the re-pack of its layers' bf16 operands and a fixed
         range of the l2 partial sums (so the value of the l2 term does not depend on when it ran)."""
         from .dp import plan_buckets
@@ -1704,12 +1670,11 @@ class YOLONet(object):
         for (_, o, c), (_, o2, _) in zip(spans, spans[1:]):
             assert o + c == o2, "arena must be contiguous in layer order"
         assert not spans or (spans[0][1] == 0 and spans[-1][1] + spans[-1][2] == self.n_decay)
-        elems = int(float(os.environ.get("DISYOLO_OPT_CHUNK_M", "8")) * 1e6)
         self.opt_chunks = []
         self._opt_chunk_of = {}
         parts = 0
         by = {l.idx: l for l in self.layers}
-        for _, off, cnt in plan_buckets(spans, elems):
+        for _, off, cnt in plan_buckets(spans, OPT_CHUNK_ELEMS):
             members = {idx for idx, o, c in spans if off <= o and o + c <= off + cnt}
             jobs = [(by[i].w, by[i].wp, by[i].wdg, by[i].k, by[i].cin, by[i].cout, by[i].cout_pad)
                     for i in sorted(members) if i > 1]
@@ -1735,29 +1700,6 @@ class YOLONet(object):
             ch["pack"].run()
         self._opt_swept.add(ci)
 
-    def _dp_sweep_lane(self) -> int:
-        """data parallel, exchange in the list: the lane a slice's optimizer sweep runs on.  DISYOLO_DP_SWEEP_LANE = "comm"
-        (default): the exchange lane itself, right behind the slice's collective -- the side lane never waits for the links;
-        that lane has the lowest stream priority (DISYOLO_LANE3_LOW=0: normal), so the HBM-bound sweeps do not compete with
-        the main lane, as on the single-GPU step's side lane.  One RCCL rank, same box, ms per step: plain 4.16-4.18 |
-        comm + low priority 4.17-4.18 | comm at normal priority 4.22 | "side" (back on the side lane
-        DISYOLO_DP_SWEEP_DELAY layers later) 4.20 | a third, low-priority lane for the sweeps behind a normal-priority
-        exchange lane 4.15-4.18 against 4.12 for comm + low on another box (one more 15-us hop): not kept."""
-        return 1 if os.environ.get("DISYOLO_DP_SWEEP_LANE", "comm") == "side" else L.COMM_LANE
-
-    def _dp_sweep_oldest(self, lane: int, main_waited: bool = False) -> None:
-        """data parallel, exchange in the list: the optimizer sweep (+ re-pack) of the slice whose collective was issued
-        first, on ``lane`` behind that collective and behind the main lane up to here (the re-pack rewrites operands the
-        main lane's data-gradient convs read)"""
-        ci, mk = self._dp_pending.pop(0)[:2]
-        L.lane_wait(mk, lane)
-        if lane != 0 and not main_waited:         # (main_waited: the lane already sits behind an edge of the main lane that is late enough)
-            L.lane_wait(L.lane_mark(0), lane)
-        prev = L.CURRENT_LANE
-        L.set_lane(lane)
-        self._sweep_chunk(ci, 1.0 / self.dp.world_size)
-        L.set_lane(prev)
-
     def optimizer_step(self, grad_scale: float = 1.0) -> None:
         """tf.train.AdamOptimizer(1e-4).minimize (train_yolo3_mask.py:55) over the arena; the
         l2 regulariser's gradient (l2*w) is folded in for weights and biases.  The step count
@@ -1769,9 +1711,8 @@ class YOLONet(object):
                 self._plan_opt_chunks()
             nt = self.n_params - self.n_decay       # batch-norm gamma / beta: not regularised
             inl = self.dp is not None and self.dp.inlist
-            on_comm = inl and self._dp_sweep_lane() != 1
             cur = L.CURRENT_LANE
-            if inl and on_comm:
+            if inl:
                 # what is left of the exchange and of the optimizer on the exchange lane, in order: each remaining slice's
                 # collective and its sweep, gamma / beta, the finish; this lane then waits for the exchange lane once
                 sl = L.COMM_LANE
@@ -1784,24 +1725,6 @@ class YOLONet(object):
                         self._sweep_chunk(ci, grad_scale)
                 if nt > 0:
                     self.dp.exchange_inlist("tail", self.n_decay, nt)
-            elif inl:
-                # the collectives of everything not exchanged yet (the slices that became final last, gamma / beta) on the
-                # exchange lane, behind what this lane has seen; the sweeps follow on this lane, oldest collective first
-                pend = {p[0] for p in self._dp_pending}
-                L.lane_wait(L.lane_mark(cur), L.COMM_LANE)
-                L.set_lane(L.COMM_LANE)
-                for ci in range(len(self.opt_chunks)):
-                    if ci not in self._opt_swept and ci not in pend:
-                        ch = self.opt_chunks[ci]
-                        self.dp.exchange_inlist(ci, ch["off"], ch["cnt"])
-                        self._dp_pending.append((ci, L.lane_mark(L.COMM_LANE), 0))
-                if nt > 0:
-                    self.dp.exchange_inlist("tail", self.n_decay, nt)
-                tail_mark = L.lane_mark(L.COMM_LANE)
-                L.set_lane(cur)
-                while self._dp_pending:
-                    self._dp_sweep_oldest(cur)
-                L.lane_wait(tail_mark, cur)
             for ci in range(len(self.opt_chunks)):
                 if ci not in self._opt_swept:
                     self._sweep_chunk(ci, grad_scale)
@@ -1812,12 +1735,11 @@ class YOLONet(object):
             L.adam_finish(self.step_dev, self._opt_parts if self.n_decay else None, self._opt_nparts if self.n_decay else 0,
                           self.l2, self.reg_loss if self.n_decay else None,
                           record=(self.losses, self.mask_loss, None if self.n_decay else self.reg_loss, self.loss_ring))
-            if inl and on_comm:
+            if inl:
                 L.set_lane(cur)
                 L.lane_sync(sl, cur)
             self._opt_swept = set()
             self._opt_done = [set() for _ in self.opt_chunks]
-            self._dp_pending = []
             self._reg_fresh = True
 
     LOSS_RING = 1024
@@ -1905,7 +1827,7 @@ class YOLONet(object):
         if pipeline_backbone:
             if graph:
                 raise L.DisyoloError("pipeline_backbone uses the list executor, not a hipGraph")
-            if "DISYOLO_TAIL_MAIN" not in os.environ and (self.dp is None or self.dp.inlist):
+            if self.dp is None or self.dp.inlist:
                 # the pipelined step joins its lanes at the end of every replay: the weight gradients of the LAST two layers of
                 # the backward pass stay on the main lane, which would only wait for them (tail 0 / 1 / 2 / 3 / 4 / 6 / 8 layers:
                 # 3.82 / 3.80 / 3.76 / 3.76 / 3.81 / 3.85 / 3.94 ms per step, profiles/r06_backbone_pipeline.txt)
@@ -1977,34 +1899,17 @@ class YOLONet(object):
                 first = self._pipe_P + 1
             if self.pair and self._half == 1:
                 first = self._pair_P + 1         # (the even step ran the backbone for this half too)
-            pipe_early = parity is not None and os.environ.get("DISYOLO_PIPE_EARLY", "0") == "1"
-
-            def next_backbone():
-                # the next batch's backbone: lowest-priority lane (lane 2)
+            self.compute_losses(det_thresh, first)
+            if parity is not None:
+                # the next batch's backbone on the lowest-priority lane, started once the trunk's forward is done, so it fills
+                # what the backward pass leaves of the CUs
                 self._use_parity(1 - parity)
                 self.images = self._pipe_in[parity]["images"]     # (fed before THIS replay: labels of batch t, images of t + 1)
-                lane = int(os.environ.get("DISYOLO_PIPE_LANE", "2"))
-                L.lane_sync(0, lane)
-                L.set_lane(lane)
+                L.lane_sync(0, PIPE_LANE)
+                L.set_lane(PIPE_LANE)
                 self._forward_prefix(self._pipe_P, True)
                 L.set_lane(0)
                 self._use_parity(parity)
-            if pipe_early:
-                next_backbone()      # (experiment: from the start of the step, beside the heads' forward pass as well)
-            started = [False]
-            fwd_after = int(os.environ.get("DISYOLO_PIPE_FWD_AFTER", "0")) if (parity is not None and not pipe_early) else 0
-            if fwd_after:
-                # (experiment: from behind forward layer DISYOLO_PIPE_FWD_AFTER of the trainable part, a main-lane layer)
-                def early_start():
-                    started[0] = True
-                    next_backbone()
-                self._fwd_hook = (fwd_after, early_start)
-            self.compute_losses(det_thresh, first)
-            self._fwd_hook = None
-            pipe_after = int(os.environ.get("DISYOLO_PIPE_AFTER", "0")) if (parity is not None and self.dp is None) else 0
-            if parity is not None and not pipe_early and pipe_after == 0 and not started[0]:
-                # ... started once the trunk's forward is done, so it fills what the backward pass leaves of the CUs
-                next_backbone()
             if self.dp is not None and not inl:
                 self.dp.begin_step()
 
@@ -2016,17 +1921,6 @@ class YOLONet(object):
                     if bi is not None:
                         marks.append((prog.size(), bi))
                 self.backward(mark)
-            elif pipe_after > 0:
-                # (experiment: the backbone's launches issued behind the first DISYOLO_PIPE_AFTER layers of the backward pass)
-                done = [0]
-
-                def late_start(_l):
-                    done[0] += 1
-                    if done[0] == pipe_after:
-                        next_backbone()
-                self.backward(late_start, sweep=True)
-                if done[0] < pipe_after:
-                    next_backbone()
             else:
                 self.backward(sweep=True)
             bwd_end = prog.size()
@@ -2073,7 +1967,7 @@ class YOLONet(object):
         if self._graph is not None:
             self._graph.replay()
             return
-        if self.dp is None or self.dp.inlist or os.environ.get("DISYOLO_DP_NOSEG") == "1":
+        if self.dp is None or self.dp.inlist:
             self._prog.run(join=not self._overlap)
             self._tail_open = self._overlap
             return

@@ -573,8 +573,8 @@ DGRAD_S2 = [(2, 36, 36, 32, 64, 0, False), (2, 36, 36, 32, 64, 2, True), (1, 40,
 def test_stride2_dgrad_by_parity_classes(dev, B, H, W, Cin, Cout, tile, accumulate):
     """dx of a 3x3 stride-2 conv: a tap reaches an input pixel only where the parities match, so the GEMM tiles are formed
     per output-parity class and skip the 5-8 void taps of their class.  Against autograd (f64), with and without a gradient
-    already in dx (residual = dx: the second consumer of a tensor), and bit for bit against the all-taps order
-    (DISYOLO_DGRAD_PCLS=0 is read once per process, so that comparison lives in tools/; here: values)."""
+    already in dx (residual = dx: the second consumer of a tensor).  (The all-taps order is no longer selectable for
+    these layers, so there is nothing to compare bit for bit; here: values.)"""
     g = torch.Generator().manual_seed(Cin + Cout + H + tile)
     x = torch.randn(B, H, W, Cin, generator=g, dtype=torch.float64, requires_grad=True)
     w = bf16r(torch.randn(3, 3, Cin, Cout, generator=g) / (9 * Cin) ** 0.5)

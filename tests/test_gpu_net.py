@@ -648,7 +648,7 @@ def test_overlapped_tail_replays_without_a_join_in_between(dev, stage, B, S, fee
 def test_recorded_step_keeps_event_packets_off_the_main_lane(dev):
     """An event record or an early-enqueued wait costs its stream ~3 us (tools/micro/event_cost.hip); rounds 1-4 put one
     record per trainable layer on the main lane (35 + 8 waits in stage 1).  The step is designed against these counts:
-    one edge per DISYOLO_WGRAD_GROUP (3) layers' weight gradients, the three head branches, the mask-loss input, the tail;
+    one edge per WGRAD_GROUP (3) layers' weight gradients, the three head branches, the mask-loss input, the tail;
     cross-replay waits merged to two."""
     for stage, max_rec, max_wait in ((1, 16, 4), (2, 34, 3)):
         net = YOLONet(training=True, device=dev, image_size=64, batch_size=2, stage=stage, seed=2)

@@ -1,5 +1,5 @@
 """the batch-norm passes of the big early layers, alone: forward normalise, backward column sums / finalize / apply, against the bytes
-they move (python tools/bench_bn.py; DISYOLO_EXP_BN = 4 / 8 / 16 / 28 skips the column sums / finalize / apply / all three)"""
+they move (python tools/bench_bn.py)"""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
