@@ -4,6 +4,7 @@
 // yolo/yolo3_net_pos.py:465-628, 862-952 (the reference unrolls these per image in Python
 // and runs tf.image.non_max_suppression per class through tf.map_fn).
 #include <array>
+#include <vector>
 #include "common.h"
 #include "runtime.h"
 
@@ -419,6 +420,30 @@ __global__ __launch_bounds__(256) void psroi_assemble_kernel(const float* score,
 // pass, every product and sum rounded to f32 separately -- no FMA, so the > 0.5 decision is the
 // same as the host restatement's), writes the per-detection bit and keeps the class of the last
 // covering detection for the merged class map.
+// THE tap arithmetic and the > 0.5 decision of the paste, shared by the per-image and the batched kernel so the two cannot drift:
+// the bit of pixel (y, x) for one detection, m = its size x size mask, r = its rect row (cy1,cx1,cy2,cx2, y1,x1,y2,x2)
+__device__ __forceinline__ unsigned char paste_bit(const float* m, int size, const int* r, int y, int x) {
+  const int cy1 = r[0], cx1 = r[1], cy2 = r[2], cx2 = r[3], y1 = r[4], x1 = r[5], y2 = r[6], x2 = r[7];
+  const int sh = cy2 - cy1, sw = cx2 - cx1, dh = y2 - y1, dw = x2 - x1;
+  if (!(sh > 0 && sw > 0 && dh > 0 && dw > 0 && y >= y1 && y < y2 && x >= x1 && x < x2)) return 0;
+  float fx = (float)(((double)(x - x1) + 0.5) * ((double)sw / (double)dw) - 0.5);
+  float fy = (float)(((double)(y - y1) + 0.5) * ((double)sh / (double)dh) - 0.5);
+  int sx = (int)floorf(fx), sy = (int)floorf(fy);
+  float ax = __fsub_rn(fx, (float)sx), ay = __fsub_rn(fy, (float)sy);
+  if (sx < 0) { ax = 0.f; sx = 0; }
+  if (sx >= sw - 1) { ax = 0.f; sx = sw - 1; }
+  if (sy < 0) { ay = 0.f; sy = 0; }
+  if (sy >= sh - 1) { ay = 0.f; sy = sh - 1; }
+  const int sx1 = min(sx + 1, sw - 1), sy1 = min(sy + 1, sh - 1);
+  const float* row0 = m + (size_t)(cy1 + sy) * size + cx1;
+  const float* row1 = m + (size_t)(cy1 + sy1) * size + cx1;
+  const float bx = __fsub_rn(1.f, ax), by = __fsub_rn(1.f, ay);
+  const float h0 = __fadd_rn(__fmul_rn(row0[sx], bx), __fmul_rn(row0[sx1], ax));
+  const float h1 = __fadd_rn(__fmul_rn(row1[sx], bx), __fmul_rn(row1[sx1], ax));
+  const float v = __fadd_rn(__fmul_rn(h0, by), __fmul_rn(h1, ay));
+  return v > 0.5f ? 1 : 0;
+}
+
 __global__ __launch_bounds__(256) void mask_paste_kernel(const float* masks, int n, int size, const int* rects,
                                                          const int* classids, int H, int W, unsigned char* full,
                                                          unsigned char* merged) {
@@ -427,33 +452,109 @@ __global__ __launch_bounds__(256) void mask_paste_kernel(const float* masks, int
     const int y = (int)(i / W), x = (int)(i - (int64_t)y * W);
     unsigned char mcls = 0;
     for (int k = 0; k < n; ++k) {
-      const int* r = rects + k * 8;
-      const int cy1 = r[0], cx1 = r[1], cy2 = r[2], cx2 = r[3], y1 = r[4], x1 = r[5], y2 = r[6], x2 = r[7];
-      const int sh = cy2 - cy1, sw = cx2 - cx1, dh = y2 - y1, dw = x2 - x1;
-      unsigned char bit = 0;
-      if (sh > 0 && sw > 0 && dh > 0 && dw > 0 && y >= y1 && y < y2 && x >= x1 && x < x2) {
-        float fx = (float)(((double)(x - x1) + 0.5) * ((double)sw / (double)dw) - 0.5);
-        float fy = (float)(((double)(y - y1) + 0.5) * ((double)sh / (double)dh) - 0.5);
-        int sx = (int)floorf(fx), sy = (int)floorf(fy);
-        float ax = __fsub_rn(fx, (float)sx), ay = __fsub_rn(fy, (float)sy);
-        if (sx < 0) { ax = 0.f; sx = 0; }
-        if (sx >= sw - 1) { ax = 0.f; sx = sw - 1; }
-        if (sy < 0) { ay = 0.f; sy = 0; }
-        if (sy >= sh - 1) { ay = 0.f; sy = sh - 1; }
-        const int sx1 = min(sx + 1, sw - 1), sy1 = min(sy + 1, sh - 1);
-        const float* m = masks + (size_t)k * size * size;
-        const float* row0 = m + (size_t)(cy1 + sy) * size + cx1;
-        const float* row1 = m + (size_t)(cy1 + sy1) * size + cx1;
-        const float bx = __fsub_rn(1.f, ax), by = __fsub_rn(1.f, ay);
-        const float h0 = __fadd_rn(__fmul_rn(row0[sx], bx), __fmul_rn(row0[sx1], ax));
-        const float h1 = __fadd_rn(__fmul_rn(row1[sx], bx), __fmul_rn(row1[sx1], ax));
-        const float v = __fadd_rn(__fmul_rn(h0, by), __fmul_rn(h1, ay));
-        bit = v > 0.5f ? 1 : 0;
-      }
+      const unsigned char bit = paste_bit(masks + (size_t)k * size * size, size, rects + k * 8, y, x);
       if (full) full[(size_t)k * total + i] = bit;
       if (bit) mcls = (unsigned char)(classids[k] + 1);
     }
     merged[i] = mcls;
+  }
+}
+
+// The test loop's paste for a whole batch in ONE launch (MAP.collect_batch): per image (job) the merged class map, the pasted
+// pixel count of every detection, its intersection with every ground-truth instance of its class and -- with a true class map --
+// the 4x4 confusion counts, without ever writing a full-resolution mask.  A block owns PB_CHUNK consecutive pixels of one job
+// (found through the jobs' block0 prefix); a thread owns PB_PX of them, walks the job's detections in order with paste_bit and
+// keeps the n <= 64 bits of a pixel in one 64-bit register.  Every count is an integer: wave ballot + popcount, one LDS add per
+// wave, one global int32 add per block and non-zero counter -- the sums are the same whatever order the adds land in.  The
+// ground-truth instances go through the LDS counters PB_GT at a time, so their number is not bounded.
+// Bound by memory latency, not by bandwidth or arithmetic: a pixel reads ng ground-truth bytes and a few mask taps and writes one
+// byte; the detection walk is a chain of uniform rect loads and a short dependent tap read per covering detection.
+constexpr int PB_T = 256;
+constexpr int PB_PX = 4;
+constexpr int PB_CHUNK = PB_T * PB_PX;
+constexpr int PB_GT = 32;
+constexpr int PB_MAXN = 64;
+
+__global__ __launch_bounds__(PB_T) void mask_paste_iou_batch_kernel(const disyolo_paste_job* jobs, int njobs, int size,
+                                                                    unsigned long long* conf) {
+  __shared__ unsigned int s_area[PB_MAXN];
+  __shared__ unsigned int s_inter[PB_MAXN * PB_GT];
+  __shared__ unsigned int s_conf[16];
+  __shared__ int s_cls[PB_MAXN];
+  int lo = 0, hi = njobs - 1;      // the last job whose first block is <= this block
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (jobs[mid].block0 <= (int)blockIdx.x) lo = mid; else hi = mid - 1;
+  }
+  const disyolo_paste_job j = jobs[lo];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int W = j.image_w, total = j.image_h * j.image_w, n = j.n, ng = j.ng;
+  const int chunk0 = ((int)blockIdx.x - j.block0) * PB_CHUNK;
+  if (tid < PB_MAXN) {
+    s_area[tid] = 0;
+    s_cls[tid] = tid < n ? j.classids[tid] : -1;
+  }
+  if (tid < 16) s_conf[tid] = 0;
+  __syncthreads();
+  unsigned long long bits[PB_PX];
+#pragma unroll
+  for (int p = 0; p < PB_PX; ++p) {
+    const int i = chunk0 + p * PB_T + tid;
+    const bool valid = i < total;
+    const int y = valid ? i / W : 0, x = valid ? i - y * W : 0;
+    unsigned long long b = 0;
+    unsigned char mcls = 0;
+    for (int k = 0; k < n; ++k) {
+      const int* r = j.rects + k * 8;
+      unsigned char bit = 0;
+      // (a crop that leaves the size x size mask would read outside `masks`: such a row pastes nothing)
+      if (valid && r[0] >= 0 && r[1] >= 0 && r[2] <= size && r[3] <= size)
+        bit = paste_bit(j.masks + (size_t)k * size * size, size, r, y, x);
+      if (bit) {
+        b |= 1ull << k;
+        mcls = (unsigned char)(s_cls[k] + 1);
+      }
+      const int c = __popcll(__ballot(bit));
+      if (lane == 0 && c) atomicAdd(&s_area[k], (unsigned)c);
+    }
+    bits[p] = b;
+    if (valid) {
+      j.merged[i] = mcls;
+      if (j.true_map) {
+        const unsigned a = j.true_map[i];
+        if (a < 4 && mcls < 4) atomicAdd(&s_conf[a * 4 + mcls], 1u);
+      }
+    }
+  }
+  __syncthreads();
+  if (tid < n && s_area[tid]) atomicAdd(&j.counts[(size_t)tid * (1 + ng)], (int)s_area[tid]);
+  if (j.true_map && tid < 16 && s_conf[tid]) atomicAdd(&conf[tid], (unsigned long long)s_conf[tid]);
+  for (int g0 = 0; g0 < ng; g0 += PB_GT) {
+    const int gn = min(PB_GT, ng - g0);
+    for (int e = tid; e < n * PB_GT; e += PB_T) s_inter[e] = 0;
+    __syncthreads();
+    for (int gg = 0; gg < gn; ++gg) {
+      const int gc = j.gt_class[g0 + gg];
+      const unsigned char* gp = j.gt + (size_t)(g0 + gg) * total;
+#pragma unroll
+      for (int p = 0; p < PB_PX; ++p) {
+        const int i = chunk0 + p * PB_T + tid;
+        unsigned long long m = 0;
+        if (bits[p] && i < total && gp[i]) m = bits[p];
+        if (__ballot(m != 0) == 0) continue;      // (wave-uniform)
+        for (int k = 0; k < n; ++k) {
+          if (s_cls[k] != gc) continue;           // (block-uniform)
+          const int c = __popcll(__ballot((m >> k) & 1));
+          if (lane == 0 && c) atomicAdd(&s_inter[k * PB_GT + gg], (unsigned)c);
+        }
+      }
+    }
+    __syncthreads();
+    for (int e = tid; e < n * PB_GT; e += PB_T) {
+      const unsigned v = s_inter[e];
+      if (v) atomicAdd(&j.counts[(size_t)(e / PB_GT) * (1 + ng) + 1 + g0 + (e % PB_GT)], (int)v);
+    }
+    __syncthreads();
   }
 }
 
@@ -603,6 +704,47 @@ extern "C" int disyolo_mask_paste(const float* masks, int n, int size, const int
   if (grid > 256 * 16) grid = 256 * 16;
   hipLaunchKernelGGL(mask_paste_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, masks, n, size, (const int*)rects,
                      (const int*)classids, image_h, image_w, (unsigned char*)full_masks, (unsigned char*)merged);
+  DY_CHECK_LAUNCH();
+  return DISYOLO_OK;
+}
+
+extern "C" size_t disyolo_paste_job_size(void) { return sizeof(disyolo_paste_job); }
+
+// validates a HOST table of jobs and lays the jobs' blocks out: block0 = the first block of each job; returns the number of
+// blocks of the launch, or a negative code
+extern "C" int disyolo_paste_job_plan(disyolo_paste_job* jobs, int njobs) {
+  DY_REQUIRE(jobs && njobs > 0, "paste_job_plan: null table or njobs <= 0");
+  int64_t blocks = 0;
+  for (int i = 0; i < njobs; ++i) {
+    const disyolo_paste_job& j = jobs[i];
+    DY_REQUIRE(j.n >= 0 && j.n <= PB_MAXN, "paste job %d: n must be in 0..64 (got %d)", i, j.n);
+    DY_REQUIRE(j.ng >= 0, "paste job %d: ng < 0", i);
+    DY_REQUIRE(j.image_h > 0 && j.image_w > 0 && (int64_t)j.image_h * j.image_w <= (1ll << 30), "paste job %d: bad image size", i);
+    DY_REQUIRE(j.merged, "paste job %d: merged is NULL", i);
+    DY_REQUIRE(j.n == 0 || (j.masks && j.rects && j.classids && j.counts), "paste job %d: null pointer with n > 0", i);
+    DY_REQUIRE(j.ng == 0 || (j.gt && j.gt_class), "paste job %d: null pointer with ng > 0", i);
+    jobs[i].block0 = (int32_t)blocks;
+    blocks += ((int64_t)j.image_h * j.image_w + PB_CHUNK - 1) / PB_CHUNK;
+    DY_REQUIRE(blocks < (1ll << 31), "paste jobs: too many pixels for one launch");
+  }
+  return (int)blocks;
+}
+
+extern "C" int disyolo_mask_paste_iou_batch(const disyolo_paste_job* jobs_host, const disyolo_paste_job* jobs, int njobs, int size,
+                                            int64_t* conf, void* stream) {
+  DY_REQUIRE(jobs_host && jobs && njobs > 0, "mask_paste_iou_batch: null table or njobs <= 0");
+  DY_REQUIRE(size > 0, "mask_paste_iou_batch: size must be > 0");
+  // the host copy is what this call can check and size the grid from; it must be a planned table (disyolo_paste_job_plan)
+  std::vector<disyolo_paste_job> plan(jobs_host, jobs_host + njobs);
+  const int blocks = disyolo_paste_job_plan(plan.data(), njobs);
+  if (blocks < 0) return blocks;
+  for (int i = 0; i < njobs; ++i) {
+    DY_REQUIRE(plan[i].block0 == jobs_host[i].block0, "mask_paste_iou_batch: job %d is not planned (disyolo_paste_job_plan)", i);
+    DY_REQUIRE(!jobs_host[i].true_map || conf, "mask_paste_iou_batch: job %d has a true_map but conf is NULL", i);
+  }
+  DY_RECORD_OR_RUN([=](void* s) { return disyolo_mask_paste_iou_batch(plan.data(), jobs, njobs, size, conf, s); });
+  hipLaunchKernelGGL(mask_paste_iou_batch_kernel, dim3(blocks), dim3(PB_T), 0, (hipStream_t)stream, jobs, njobs, size,
+                     (unsigned long long*)conf);
   DY_CHECK_LAUNCH();
   return DISYOLO_OK;
 }

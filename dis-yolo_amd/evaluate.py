@@ -18,7 +18,7 @@ import torch
 
 from . import config as cfg
 from . import lib as L
-from .postprocess import SegmentationAccuracy, correct_yolo_boxes, paste_detections
+from .postprocess import SegmentationAccuracy, correct_yolo_boxes, paste_detections, paste_rects
 from .voc_eval import voc_eval
 
 
@@ -124,6 +124,141 @@ class MAP(object):
             self._gt_cache[key] = hit
         return hit[0]
 
+    def _gt_image(self, imageid: str, device):
+        """all ground-truth instances of one image for ``collect_batch``: (uint8 [ng,H,W] 0 / 1 stack on the GPU or None, int32
+        [ng] class ids on the GPU or None, {classid: (stack rows of that class in ``recs_mask`` order = voc_eval's ``objs``
+        order, their pixel counts f32 [ngc] on the host)}).  Cached like ``_gt_stack``."""
+        key = ("image", imageid)
+        hit = self._gt_cache.get(key)
+        if hit is None:
+            objs = self.recs_mask[imageid]
+            if not objs:
+                hit = (None, None, {})
+            else:
+                g = np.stack([np.asarray(o["mask"]).astype(float) > 0.5 for o in objs])
+                cls = np.array([o["classid"] for o in objs], np.int32)
+                area = g.reshape(len(objs), -1).sum(1)
+                per_class = {int(c): (np.nonzero(cls == c)[0], area[cls == c].astype(np.float32)) for c in np.unique(cls)}
+                hit = (torch.from_numpy(g.astype(np.uint8)).to(device), torch.from_numpy(cls).to(device), per_class)
+            self._gt_cache[key] = hit
+        return hit
+
+    def _true_map(self, imageid: str, true_map, device) -> torch.Tensor:
+        """a ground-truth class map on the GPU (uint8 [H,W]); host arrays are uploaded once per image id and cached"""
+        if torch.is_tensor(true_map) and true_map.is_cuda:
+            return true_map.to(device, torch.uint8).contiguous()
+        key = ("true_map", imageid)
+        hit = self._gt_cache.get(key)
+        if hit is None:
+            hit = torch.as_tensor(np.ascontiguousarray(true_map)).to(device, torch.uint8).contiguous()
+            self._gt_cache[key] = hit
+        return hit
+
+    def collect_batch(self, imageids: Sequence[str], detections: torch.Tensor, keep: torch.Tensor, masks: torch.Tensor,
+                      detfile: Dict[str, List[Dict]], true_maps: Optional[Sequence] = None,
+                      conf: Optional[torch.Tensor] = None) -> List[torch.Tensor]:
+        """``collect`` for a batch, on the device-resident outputs of ``YOLONet.evaluation_device`` / ``infer``: detections
+        [B,max_det,6], keep [B,max_det], masks [B,max_det,Sm,Sm]; ``imageids`` names the first len(imageids) <= B images
+        (a short last batch leaves the other rows unused).  Per batch: one fetch of detections + keep, the job table on the
+        host, one upload (jobs, rects, class ids), ONE launch (disyolo_mask_paste_iou_batch: merged maps, pixel counts,
+        intersections and -- with ``true_maps`` (one uint8 [H,W] class map per image) and ``conf`` (int64 [16] on the GPU, e.g.
+        ``SegmentationAccuracy.conf``) -- the confusion counts), one fetch of the counts.  Appends to ``detfile`` exactly what
+        ``collect`` appends image by image, in its order (per image, classes ascending, detections in row order); returns the
+        merged class maps (uint8 CUDA [H,W] each).
+
+        The ``ov`` rows are inter / (area_det + area_gt - inter) in f32 from integer counts converted to f32 -- ``collect``'s
+        arithmetic, whose counts are f32 sums; the two agree exactly while an image has fewer than 2^24 pixels (every count is
+        then an integer that f32 holds)."""
+        nb = len(imageids)
+        B, max_det = int(detections.shape[0]), int(detections.shape[1])
+        if nb > B:
+            raise ValueError("collect_batch: %d image ids for a batch of %d" % (nb, B))
+        if nb == 0:
+            return []
+        dev = masks.device
+        if os.environ.get("DISYOLO_EVAL_GPU_IOU", "1") == "0":
+            det, kp = detections.cpu().numpy(), keep.cpu().numpy().astype(bool)
+            out = []
+            for b, imageid in enumerate(imageids):
+                if kp[b].any():
+                    merged = self.collect(imageid, det[b][kp[b]], masks[b][torch.from_numpy(kp[b]).to(dev)], detfile)
+                else:
+                    merged = torch.zeros(*self.sizes[imageid], dtype=torch.uint8, device=dev)
+                if true_maps is not None and conf is not None:
+                    L.confusion16(self._true_map(imageid, true_maps[b], dev), merged, conf)
+                out.append(merged)
+            return out
+        size = int(masks.shape[-1])
+        masks = masks.contiguous()
+        host = torch.cat([detections.reshape(B, -1), keep.reshape(B, -1).to(torch.float32)], 1).cpu().numpy()     # the one fetch
+        det = host[:nb, :max_det * 6].reshape(nb, max_det, 6)
+        kp = host[:nb, max_det * 6:] != 0
+        # ---- the job table, rects and class ids in one host buffer -> one upload
+        jobs = np.zeros(nb, L.PASTE_JOB)
+        off_rects = (jobs.nbytes + 15) // 16 * 16
+        off_cls = off_rects + nb * max_det * 8 * 4
+        hbuf = np.zeros(off_cls + nb * max_det * 4, np.uint8)
+        rects_all = hbuf[off_rects:off_cls].view(np.int32).reshape(nb, max_det, 8)
+        cls_all = hbuf[off_cls:].view(np.int32).reshape(nb, max_det)
+        oks, gts, npix, cnt_off = [], [], 0, [0]
+        for b, imageid in enumerate(imageids):
+            image_h, image_w = self.sizes[imageid]
+            rects, ok = paste_rects(det[b], image_h, image_w, self.net_size, size)
+            ok &= kp[b]
+            rects[~ok] = 0
+            rects_all[b], cls_all[b] = rects, det[b][:, 4].astype(np.int32)
+            oks.append(ok)
+            gts.append(self._gt_image(imageid, dev))
+            ng = 0 if gts[b][0] is None else int(gts[b][0].shape[0])
+            cnt_off.append(cnt_off[-1] + max_det * (1 + ng))
+            npix += int(image_h) * int(image_w)
+        dbuf = torch.empty(hbuf.size, dtype=torch.uint8, device=dev)
+        counts = torch.zeros(cnt_off[-1], dtype=torch.int32, device=dev)
+        merged_all = torch.empty(npix, dtype=torch.uint8, device=dev)
+        out, tms, pix0 = [], [], 0
+        for b, imageid in enumerate(imageids):
+            image_h, image_w = self.sizes[imageid]
+            gt, gt_cls, _ = gts[b]
+            merged = merged_all[pix0:pix0 + image_h * image_w].view(image_h, image_w)
+            pix0 += image_h * image_w
+            out.append(merged)
+            j = jobs[b]
+            j["masks"] = masks.data_ptr() + b * max_det * size * size * 4
+            j["rects"] = dbuf.data_ptr() + off_rects + b * max_det * 32
+            j["classids"] = dbuf.data_ptr() + off_cls + b * max_det * 4
+            j["gt"], j["gt_class"] = (0, 0) if gt is None else (gt.data_ptr(), gt_cls.data_ptr())
+            j["merged"] = merged.data_ptr()
+            if true_maps is not None and conf is not None:
+                tm = self._true_map(imageid, true_maps[b], dev)
+                if tuple(tm.shape) != (image_h, image_w):
+                    raise ValueError("class maps differ in shape: %s vs %s" % (tuple(tm.shape), (image_h, image_w)))
+                tms.append(tm)                       # (kept alive until the launch has been issued on this stream)
+                j["true_map"] = tm.data_ptr()
+            j["counts"] = counts.data_ptr() + cnt_off[b] * 4
+            j["n"], j["ng"] = max_det, 0 if gt is None else int(gt.shape[0])
+            j["image_h"], j["image_w"] = image_h, image_w
+        L.paste_job_plan(jobs)
+        hbuf[:jobs.nbytes] = jobs.view(np.uint8)
+        dbuf.copy_(torch.from_numpy(hbuf))                                                       # the one upload
+        L.mask_paste_iou_batch(jobs, dbuf, size, conf if tms else None)
+        cnt = counts.cpu().numpy()                                                               # the one fetch of the counts
+        for b, imageid in enumerate(imageids):
+            ok, per_class = oks[b], gts[b][2]
+            c_b = cnt[cnt_off[b]:cnt_off[b + 1]].reshape(max_det, -1)
+            cls_b = cls_all[b]
+            for c in sorted({int(v) for v in cls_b[ok]}):
+                rows = np.nonzero(ok & (cls_b == c))[0]
+                if c not in per_class:
+                    ovs = [np.zeros(0, np.float32)] * len(rows)
+                else:
+                    cols, gt_area = per_class[c]
+                    inter = c_b[rows][:, 1 + cols].astype(np.float32)                            # [nd, ng] exact counts
+                    union = c_b[rows, 0].astype(np.float32)[:, None] + gt_area[None, :] - inter
+                    ovs = list((inter / union).astype(np.float32))
+                for k, ov in zip(rows, ovs):
+                    detfile[str(c)].append({"imageid": imageid, "score": float(det[b][k, 5]), "ov": ov})
+        return out
+
     def do_python_eval(self, detdata: List[Dict]):
         """utils/validation_map.py:104-198: detdata = [{'boxes' [n,6], 'masks' [n,S,S] (CUDA tensor or numpy)
         or the scalar 0.0, 'imname'}] in ``index`` order -> [{'thresh', 'AP' [3], 'mAP' [recall, precision, mAP]}]"""
@@ -143,15 +278,15 @@ class MAP(object):
 def evaluate(net, images: Dict[str, np.ndarray], eval_map: MAP, det_thresh: float = cfg.OBJ_THRESHOLD,
              weights_file: Optional[str] = None):
     """calculate_test_map.py:180-347.  ``images``: image id -> RGB uint8 array (or a path to decode);
-    ``net``: a YOLONet built with batch size 1 like the reference's test graph (:354).  Returns
+    ``net``: a YOLONet built with batch size 1 like the reference's test graph (:354), or with a larger one: B images are then
+    letter-boxed into one frame, run as one batch and collected by ``MAP.collect_batch`` (a short last batch runs with the
+    stale frames of the one before left in place).  Returns
     (thresh_out, mask_acc, timing) = ([{'thresh', 'AP', 'mAP'}], [bg, crack, spall, rebar, mIoU] or None,
     {'prediction_s', 'crop_assemble_s', 'per_image_s'})."""
     if weights_file is not None:
         from .checkpoint import restore_net
         restore_net(net, weights_file)                       # saver.restore (:184-185)
-    if net.B != 1:
-        raise ValueError("evaluate() feeds one image at a time (cfg.BATCH_SIZE = 1, calculate_test_map.py:354)")
-    S = net.S
+    S, B = net.S, net.B
     if (not net.training and getattr(net, "_infer_prog", None) is None and os.environ.get("DISYOLO_EVAL_REPLAY", "1") != "0"):
         # an inference net: record forward + detection filter + mask assembly once for this threshold (a hipGraph of one lane);
         # every image is then one replay (YOLONet.evaluation uses the recording when the threshold matches)
@@ -159,6 +294,9 @@ def evaluate(net, images: Dict[str, np.ndarray], eval_map: MAP, det_thresh: floa
     detfile = {str(c): [] for c in eval_map.classid}
     seg = SegmentationAccuracy(net.device) if eval_map.merged is not None else None
     t_pred = t_crop = 0.0
+    if B > 1:
+        t_pred, t_crop = _evaluate_batches(net, images, eval_map, det_thresh, detfile, seg)
+        return _evaluate_result(eval_map, detfile, seg, t_pred, t_crop)
     frame = torch.empty(1, S, S, 3, dtype=torch.float32, device=net.device)
     for index in eval_map.index:
         src = images[index]
@@ -180,7 +318,40 @@ def evaluate(net, images: Dict[str, np.ndarray], eval_map: MAP, det_thresh: floa
             seg.add(eval_map.merged[index], merged)
         torch.cuda.synchronize()
         t_crop += time.time() - t
+    return _evaluate_result(eval_map, detfile, seg, t_pred, t_crop)
+
+
+def _evaluate_result(eval_map: MAP, detfile, seg, t_pred: float, t_crop: float):
     thresh_out = eval_map._ap_table(detfile)
     mask_acc = seg.result() if seg is not None else None
     n = max(len(eval_map.index), 1)
     return thresh_out, mask_acc, {"prediction_s": t_pred, "crop_assemble_s": t_crop, "per_image_s": (t_pred + t_crop) / n}
+
+
+def _evaluate_batches(net, images, eval_map: MAP, det_thresh: float, detfile, seg) -> Tuple[float, float]:
+    """evaluate()'s loop for a net of batch size B > 1: B letter boxes into one frame, one pass of the net, one
+    ``MAP.collect_batch``; the last batch may hold fewer images -- the frames (and clip windows) of the batch before stay in the
+    unused rows, and only the real images get a job.  Returns (prediction seconds, crop + assemble seconds)."""
+    S, B = net.S, net.B
+    t_pred = t_crop = 0.0
+    frame = torch.zeros(B, S, S, 3, dtype=torch.float32, device=net.device)
+    windows = np.tile(np.array([0.0, 0.0, 1.0, 1.0], np.float32), (B, 1))
+    for a in range(0, len(eval_map.index), B):
+        ids = eval_map.index[a:a + B]
+        for i, index in enumerate(ids):
+            src = images[index]
+            rgb = load_image_rgb(src) if isinstance(src, str) else np.asarray(src)
+            assert list(rgb.shape[:2]) == list(eval_map.sizes[index])
+            _, windows[i] = image_read(rgb, S, net.device, out=frame[i])
+        torch.cuda.synchronize()
+        t = time.time()
+        dets, keep, masks = net.evaluation_device(frame, windows, [np.float32(det_thresh)])
+        torch.cuda.synchronize()
+        t_pred += time.time() - t
+        t = time.time()
+        eval_map.collect_batch(ids, dets, keep, masks, detfile,
+                               true_maps=[eval_map.merged[i] for i in ids] if seg is not None else None,
+                               conf=seg.conf if seg is not None else None)
+        torch.cuda.synchronize()
+        t_crop += time.time() - t
+    return t_pred, t_crop

@@ -148,6 +148,9 @@ _SIGS = {
                                      C.c_void_p, C.c_void_p]),
     "disyolo_letterbox": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "disyolo_confusion16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "disyolo_paste_job_size": (C.c_size_t, []),
+    "disyolo_paste_job_plan": (C.c_int, [C.c_void_p, C.c_int]),
+    "disyolo_mask_paste_iou_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "disyolo_adam_step": (C.c_int, [C.c_void_p] * 4 + [C.c_int64, C.c_int64] + [C.c_float] * 5 + [C.c_int64, C.c_float,
                                                                                              C.c_void_p]),
     "disyolo_adam_step_dev": (C.c_int, [C.c_void_p] * 4 + [C.c_int64, C.c_int64] + [C.c_float] * 5 + [C.c_void_p, C.c_float,
@@ -220,6 +223,9 @@ def load() -> C.CDLL:
         if lib.disyolo_conv_desc_size() != C.sizeof(ConvDesc):
             raise DisyoloError("%s was built from a different include/disyolo.h (conv descriptor %d bytes, this "
                                "binding %d): rebuild it" % (LIB_PATH, lib.disyolo_conv_desc_size(), C.sizeof(ConvDesc)))
+        if lib.disyolo_paste_job_size() != PASTE_JOB.itemsize:
+            raise DisyoloError("%s was built from a different include/disyolo.h (paste job %d bytes, this binding %d): "
+                               "rebuild it" % (LIB_PATH, lib.disyolo_paste_job_size(), PASTE_JOB.itemsize))
         _lib = lib
     return _lib
 
@@ -898,6 +904,37 @@ def mask_paste(masks, rects, classids, image_h: int, image_w: int, full_masks, m
     _check(load().disyolo_mask_paste(_p(masks) if n else None, n, int(masks.shape[-1]) if n else 1, _p(rects) if n else None,
                                      _p(classids) if n else None, image_h, image_w, _p(full_masks), _p(merged), _stream()),
            "mask_paste")
+
+
+PASTE_JOB = np.dtype([("masks", np.uint64), ("rects", np.uint64), ("classids", np.uint64), ("gt", np.uint64), ("gt_class", np.uint64),
+                      ("merged", np.uint64), ("true_map", np.uint64), ("counts", np.uint64), ("n", np.int32), ("ng", np.int32),
+                      ("image_h", np.int32), ("image_w", np.int32), ("block0", np.int32), ("reserved", np.int32)])
+assert PASTE_JOB.itemsize == 88      # (disyolo_paste_job, include/disyolo.h)
+
+
+def paste_job_plan(jobs) -> int:
+    """jobs: numpy array of PASTE_JOB records (host); checks them and fills ``block0``; returns the launch's block count"""
+    if jobs.dtype != PASTE_JOB or not jobs.flags["C_CONTIGUOUS"] or jobs.ndim != 1:
+        raise DisyoloError("paste_job_plan: jobs must be a contiguous 1-d array of PASTE_JOB records")
+    rc = load().disyolo_paste_job_plan(jobs.ctypes.data, int(jobs.shape[0]))
+    if rc < 0:
+        _check(rc, "paste_job_plan")
+    return rc
+
+
+def mask_paste_iou_batch(jobs, jobs_dev, size: int, conf=None) -> None:
+    """jobs: the planned PASTE_JOB records on the host; jobs_dev: a uint8 CUDA tensor that starts with the same bytes (uploaded by
+    the caller on this stream); conf: int64 [16] CUDA or None.  One launch for all jobs (disyolo_mask_paste_iou_batch)."""
+    if jobs.dtype != PASTE_JOB or not jobs.flags["C_CONTIGUOUS"] or jobs.ndim != 1:
+        raise DisyoloError("mask_paste_iou_batch: jobs must be a contiguous 1-d array of PASTE_JOB records")
+    _need(jobs_dev, torch.uint8, "jobs_dev")
+    if jobs_dev.numel() < jobs.nbytes:
+        raise DisyoloError("mask_paste_iou_batch: %d jobs do not fit %d bytes" % (jobs.shape[0], jobs_dev.numel()))
+    if conf is not None:
+        _need(conf, torch.int64, "conf")
+        _need_shape(conf, (16,), "conf")
+    _check(load().disyolo_mask_paste_iou_batch(jobs.ctypes.data, _p(jobs_dev), int(jobs.shape[0]), int(size), _p(conf), _stream()),
+           "mask_paste_iou_batch")
 
 
 def letterbox(rgb_u8, out, size: int):

@@ -1136,11 +1136,9 @@ class YOLONet(object):
                  for i in (75, 67, 59)]
         return preds, self.detections, self.by_idx[self.score_layer].act
 
-    def evaluation(self, images, clip_window, det_thresh=cfg.OBJ_THRESHOLD, masks_on_device: bool = False):
-        """``sess.run(net.evaluation)`` (val_test, yolo/yolo3_net_pos.py:862-938): returns
-        [det_box, det_mask]: per image an [n,6] array and an [n,S/2,S/2] array (scalar 0.0
-        when the image has no valid detection, :933).  ``masks_on_device``: det_mask entries stay
-        CUDA tensors (10 MB per image at 30 detections -- what postprocess.paste_detections takes)."""
+    def evaluation_device(self, images, clip_window, det_thresh=cfg.OBJ_THRESHOLD):
+        """the device half of ``evaluation``: network + detection filter + mask assembly on a batch; returns the fixed-shape
+        outputs where they are, (detections [B,30,6], keep [B,30], masks [B,30,Sm,Sm]) -- what MAP.collect_batch takes"""
         thr = float(np.asarray(det_thresh).reshape(-1)[0])
         if (not self.training and getattr(self, "_infer_prog", None) is not None and getattr(self, "_infer_thresh", None) == thr
                 and not self.pair):
@@ -1154,6 +1152,14 @@ class YOLONet(object):
                 self.masks = torch.zeros(self.B, cfg.MAX_DETECTION, Sm, Sm, dtype=F32, device=self.device)
             L.psroi_assemble(self.by_idx[self.score_layer].act, self.detections, self.B, cfg.MAX_DETECTION, Sm, self.k, self.masks,
                              self.keep)
+        return self.detections, self.keep, self.masks
+
+    def evaluation(self, images, clip_window, det_thresh=cfg.OBJ_THRESHOLD, masks_on_device: bool = False):
+        """``sess.run(net.evaluation)`` (val_test, yolo/yolo3_net_pos.py:862-938): returns
+        [det_box, det_mask]: per image an [n,6] array and an [n,S/2,S/2] array (scalar 0.0
+        when the image has no valid detection, :933).  ``masks_on_device``: det_mask entries stay
+        CUDA tensors (10 MB per image at 30 detections -- what postprocess.paste_detections takes)."""
+        self.evaluation_device(images, clip_window, det_thresh)
         keep = self.keep.cpu().numpy().astype(bool)
         det = self.detections.cpu().numpy()
         det_box, det_mask = [], []

@@ -44,6 +44,20 @@ def correct_yolo_boxes(boxes_yxyx: np.ndarray, image_h: int, image_w: int, net_h
                      corner(b[:, 3], x_off, x_scale, image_w), corner(b[:, 2], y_off, y_scale, image_h)], axis=1)
 
 
+def paste_rects(box: np.ndarray, image_h: int, image_w: int, net_size: int, map_size: int) -> Tuple[np.ndarray, np.ndarray]:
+    """The rect arithmetic of the paste (calculate_test_map.py:244-251) for an [n,6] detection array (normalised y1,x1,y2,x2,
+    class, score) on an image_h x image_w image, a net_size letter box and map_size x map_size masks: (rects int32 [n,8] =
+    cy1,cx1,cy2,cx2 on the mask map, y1,x1,y2,x2 in the image -- what disyolo_mask_paste takes --, ok bool [n]); the rows with an
+    empty crop or destination are not ``ok`` and have zero rects."""
+    box = np.asarray(box, np.float32).reshape(-1, 6)
+    dst = correct_yolo_boxes(box[:, :4], image_h, image_w, net_size, net_size)          # x1,y1,x2,y2
+    crop = np.around(box[:, :4] * np.float32(map_size)).astype(np.int32)                   # y1,x1,y2,x2 on the map
+    rects = np.concatenate([crop, dst[:, [1, 0, 3, 2]]], axis=1).astype(np.int32)          # cy1,cx1,cy2,cx2,y1,x1,y2,x2
+    ok = ((dst[:, 3] - dst[:, 1]) * (dst[:, 2] - dst[:, 0]) > 0) & (crop[:, 2] > crop[:, 0]) & (crop[:, 3] > crop[:, 1])
+    rects[~ok] = 0
+    return rects, ok
+
+
 def paste_detections(det_box, det_mask, image_h: int, image_w: int, net_size: int,
                      want_full: bool = True) -> Tuple[List[Dict], torch.Tensor]:
     """One image of ``evaluation``'s result -> (entries, merged) like the reference loop body
@@ -58,11 +72,7 @@ def paste_detections(det_box, det_mask, image_h: int, image_w: int, net_size: in
         return [], merged
     box = box.reshape(-1, 6).astype(np.float32)
     n, size = box.shape[0], int(det_mask.shape[-1])
-    dst = correct_yolo_boxes(box[:, :4], image_h, image_w, net_size, net_size)          # x1,y1,x2,y2
-    crop = np.around(box[:, :4] * np.float32(size)).astype(np.int32)                       # y1,x1,y2,x2 on the map
-    rects = np.concatenate([crop, dst[:, [1, 0, 3, 2]]], axis=1).astype(np.int32)          # cy1,cx1,cy2,cx2,y1,x1,y2,x2
-    ok = ((dst[:, 3] - dst[:, 1]) * (dst[:, 2] - dst[:, 0]) > 0) & (crop[:, 2] > crop[:, 0]) & (crop[:, 3] > crop[:, 1])
-    rects[~ok] = 0
+    rects, ok = paste_rects(box, image_h, image_w, net_size, size)
     rects_d = torch.from_numpy(rects).to(dev)
     cls_d = torch.from_numpy(box[:, 4].astype(np.int32)).to(dev)
     full = torch.empty(n, image_h, image_w, dtype=torch.uint8, device=dev) if want_full else None

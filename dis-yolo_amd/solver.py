@@ -146,6 +146,15 @@ class Solver(object):
         num_val, B = len(imageidsval), self.net.B
         if num_val % B:
             self.log("Please manually change the number of validation data.")      # :123-124
+        if hasattr(self.eval, "collect_batch"):
+            # the evaluator takes a batch's outputs where they are (evaluate.MAP): nothing is gathered or copied per image
+            assert list(imageidsval[:num_val // B * B]) == list(self.eval.index)       # (do_python_eval's two asserts)
+            detfile = {str(c): [] for c in self.eval.classid}
+            for v in range(num_val // B):
+                a, b = B * v, B * v + B
+                dets, keep, masks = self.net.evaluation_device(imagesval[a:b], window_vals[a:b], [np.float32(cfg.OBJ_THRESHOLD)])
+                self.eval.collect_batch(list(imageidsval[a:b]), dets, keep, masks, detfile)
+            return self.eval._ap_table(detfile)[0]
         detect = []
         for v in range(num_val // B):
             a, b = B * v, B * v + B

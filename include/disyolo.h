@@ -444,6 +444,38 @@ int disyolo_psroi_assemble(const float* score, const float* detections, int B, i
 int disyolo_mask_paste(const float* masks, int n, int size, const int32_t* rects,
                        const int32_t* classids, int image_h, int image_w, uint8_t* full_masks,
                        uint8_t* merged, void* stream);
+/* the same paste for a whole batch of images in ONE launch, with the counts the mask AP and the mIoU need instead of the
+ * full-resolution masks (which are never written).  One job per image:
+ *   masks / rects / classids / image_h / image_w / merged: as in disyolo_mask_paste, n <= 64 rows; a row whose rect is all zero
+ *     (not kept, empty crop or destination) contributes nothing, and so does a row whose crop leaves the size x size mask;
+ *   gt uint8 [ng][image_h][image_w] (0 / 1) with gt_class int32 [ng]: the image's ground-truth instances, ng >= 0, no upper bound;
+ *   true_map uint8 [image_h][image_w] or NULL: when given, the 4x4 confusion counts of (true_map, merged) are added to `conf`
+ *     (int64 [16], disyolo_confusion16's layout and rule: values >= 4 are ignored) in the same pass;
+ *   counts int32 [n][1 + ng], ZEROED BY THE CALLER: column 0 receives the detection's pasted pixel count, column 1 + g its
+ *     intersection with instance g when gt_class[g] == classids[k]; other pairs stay zero.
+ * Integer adds only: the values are the same in every run.  An image has at most 2^30 pixels.
+ * The table exists twice: a HOST copy, which disyolo_paste_job_plan checks and completes (block0 = the job's first block in the
+ * launch; it returns the number of blocks or a negative code), and the same bytes on the DEVICE (`jobs`), uploaded by the caller
+ * after planning -- with the rects and class ids in the same copy if it likes.  The launch checks the host copy again (it never
+ * reads device memory on the host) and fails with an error code, before any launch, on n > 64, a NULL table, njobs <= 0,
+ * size <= 0, an unplanned table, or a true_map without conf. */
+typedef struct disyolo_paste_job {
+  const float* masks;        /* f32 [n][size][size] */
+  const int32_t* rects;      /* [n][8] */
+  const int32_t* classids;   /* [n] */
+  const uint8_t* gt;         /* [ng][image_h][image_w], NULL when ng == 0 */
+  const int32_t* gt_class;   /* [ng] */
+  uint8_t* merged;           /* out [image_h][image_w] */
+  const uint8_t* true_map;   /* [image_h][image_w] or NULL */
+  int32_t* counts;           /* out [n][1 + ng] */
+  int32_t n, ng, image_h, image_w;
+  int32_t block0, reserved;  /* block0: written by disyolo_paste_job_plan */
+} disyolo_paste_job;
+/* sizeof(disyolo_paste_job) as this library was built (88): a binding checks its mirror against it */
+size_t disyolo_paste_job_size(void);
+int disyolo_paste_job_plan(disyolo_paste_job* jobs_host, int njobs);
+int disyolo_mask_paste_iou_batch(const disyolo_paste_job* jobs_host, const disyolo_paste_job* jobs, int njobs, int size,
+                                 int64_t* conf, void* stream);
 /* image_read of the test / validation drivers (calculate_test_map.py:149-176; utils/val_data.py:36-63):
  * rgb uint8 [image_h, image_w, 3] (device) -> out f32 [size, size, 3] (device): aspect-preserving
  * bilinear resize (cv2.resize INTER_LINEAR on the float32 image) centred in the letter box, padding
