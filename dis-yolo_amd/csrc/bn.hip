@@ -328,6 +328,48 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const uint4* dy, cons
   }
 }
 
+// backward of a LOCKED layer's y = leaky(x*scale + shift) (moving statistics folded into scale / shift: no batch-statistics
+// terms, yolo/yolo3_net_pos.py:76-81): dx = scale * (dy * leaky'(z)).  Element-wise, 6 B per element (8-10 B with the
+// shortcut's gradient riding along); dx may be dy (each vector is read before it is written, by the same thread)
+__global__ __launch_bounds__(256) void bn_frozen_bwd_kernel(const uint4* dy, const uint4* x, const float* scale,
+                                                            const float* shift, uint4* dx, int64_t nvec, int C, float alpha,
+                                                            uint4* sc_grad, int sc_accumulate) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  const int chunks = C >> 3;
+  const int cstep = (int)(stride % chunks);
+  int ch = (int)(((int64_t)blockIdx.x * blockDim.x + threadIdx.x) % chunks);
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nvec; i += stride) {
+    const int c0 = ch << 3;
+    ch += cstep;
+    if (ch >= chunks) ch -= chunks;
+    float g[8], vx[8], sc[8], sh[8];
+    const uint4 dyv = dy[i];
+    unpack8(dyv, g);
+    if (sc_grad) {
+      // the residual shortcut's gradient (+)= dy, as in bn_bwd_apply_kernel (the arithmetic of disyolo_add_bf16)
+      uint4 o = dyv;
+      if (sc_accumulate) {
+        float a[8], b[8];
+        unpack8(dyv, a);
+        unpack8(sc_grad[i], b);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) a[k] += b[k];
+        o = pack8(a);
+      }
+      sc_grad[i] = o;
+    }
+    unpack8(x[i], vx);
+    load8(scale + c0, sc);
+    load8(shift + c0, sh);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      const float z = vx[k] * sc[k] + sh[k];
+      g[k] = sc[k] * (g[k] * (z > 0.f ? 1.f : alpha));
+    }
+    dx[i] = pack8(g);
+  }
+}
+
 // dst[b,y,x,c] (+)= sum over the 2x2 block of src[b,2y+dy,2x+dx,c_off+c]
 __global__ __launch_bounds__(256) void upsample2x_bwd_kernel(const bf16* src, bf16* dst, int B, int Hs, int Ws, int srcC,
                                                              int c_off, int C, int accumulate) {
@@ -488,6 +530,21 @@ extern "C" int disyolo_bn_act_bwd_partials(const void* dy, const void* x, const 
   const int64_t nvec = rows * C / 8;
   hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(grid_for(nvec)), dim3(256), 0, s, (const uint4*)dy, (const uint4*)x,
                      scale, shift, c1, c2, (uint4*)dx, nvec, C, alpha, (uint4*)shortcut_grad, shortcut_accumulate);
+  DY_CHECK_LAUNCH();
+  return DISYOLO_OK;
+}
+
+// backward of a locked (frozen) batch-normalised layer: moving statistics, no batch-statistics terms, no parameter gradients
+extern "C" int disyolo_bn_frozen_bwd(const void* dy, const void* x, const float* scale, const float* shift, void* dx,
+                                     int64_t rows, int C, float alpha, void* shortcut_grad, int shortcut_accumulate,
+                                     void* stream) {
+  DY_REQUIRE(dy && x && scale && shift && dx, "bn_frozen_bwd: null pointer");
+  DY_REQUIRE(rows > 0 && C > 0 && C % 8 == 0, "bn_frozen_bwd: bad shape (rows > 0, C %% 8 == 0)");
+  DY_REQUIRE(shortcut_grad != dx && shortcut_grad != dy && shortcut_grad != x, "bn_frozen_bwd: shortcut_grad aliases an operand");
+  DY_RECORD_OR_RUN([=](void* s) { return disyolo_bn_frozen_bwd(dy, x, scale, shift, dx, rows, C, alpha, shortcut_grad, shortcut_accumulate, s); });
+  const int64_t nvec = rows * C / 8;
+  hipLaunchKernelGGL(bn_frozen_bwd_kernel, dim3(grid_for(nvec)), dim3(256), 0, (hipStream_t)stream, (const uint4*)dy,
+                     (const uint4*)x, scale, shift, (uint4*)dx, nvec, C, alpha, (uint4*)shortcut_grad, shortcut_accumulate);
   DY_CHECK_LAUNCH();
   return DISYOLO_OK;
 }

@@ -123,6 +123,7 @@ _SIGS = {
                                             C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
     "disyolo_bn_act_bwd": (C.c_int, [C.c_void_p] * 9 + [C.c_int64, C.c_int, C.c_float, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t,
                                                        C.c_void_p]),
+    "disyolo_bn_frozen_bwd": (C.c_int, [C.c_void_p] * 5 + [C.c_int64, C.c_int, C.c_float, C.c_void_p, C.c_int, C.c_void_p]),
     "disyolo_upsample2x_bwd": (C.c_int, [C.c_void_p] * 2 + [C.c_int] * 7 + [C.c_void_p]),
     "disyolo_colsum_workspace": (C.c_size_t, [C.c_int64, C.c_int]),
     "disyolo_colsum": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_size_t,
@@ -892,6 +893,13 @@ def bn_act_bwd(dy, x, scale, shift, mean, rstd, dx, dgamma, dbeta, rows, C_, ws:
     _check(load().disyolo_bn_act_bwd(_p(dy), _p(x), _p(scale), _p(shift), _p(mean), _p(rstd), _p(dx), _p(dgamma),
                                      _p(dbeta), rows, C_, alpha, _p(shortcut_grad), int(shortcut_accumulate), _p(buf),
                                      buf.numel(), _stream()), "bn_act_bwd")
+
+
+def bn_frozen_bwd(dy, x, scale, shift, dx, rows, C_, alpha=0.1, shortcut_grad=None, shortcut_accumulate=False) -> None:
+    """backward of a locked layer's leaky(x*scale + shift) with the folded moving statistics: dx = scale * dy * leaky'(z);
+    ``dx`` may be ``dy``; ``shortcut_grad`` as in bn_act_bwd"""
+    _check(load().disyolo_bn_frozen_bwd(_p(dy), _p(x), _p(scale), _p(shift), _p(dx), rows, C_, alpha, _p(shortcut_grad),
+                                        int(shortcut_accumulate), _stream()), "bn_frozen_bwd")
 
 
 def mask_paste(masks, rects, classids, image_h: int, image_w: int, full_masks, merged) -> None:

@@ -41,7 +41,7 @@ class Layer:
                  "act", "stats", "stats_rows", "desc", "grad", "grad_set", "need_grad", "dw", "dbias", "dgamma",
                  "dbeta", "dx", "pad_t", "pad_l", "dgrad_descs", "wgrad_desc", "cout_pad",
                  "act8", "w8", "s_w", "s_out", "escale", "desc8", "dual16", "bn_sums", "bwd_local", "bwd_global", "bwd_part", "bwd_part_rows", "wq",
-                 "csync", "fused_fwd", "csync_bwd", "fused_bwd")
+                 "csync", "fused_fwd", "csync_bwd", "fused_bwd", "passthru")
 
     def __init__(self, idx, cin, cout, k, stride, kind, src, src_up=None, shortcut=None):
         self.idx, self.cin, self.cout, self.k, self.stride, self.kind = idx, cin, cout, k, stride, kind
@@ -199,10 +199,18 @@ class YOLONet(object):
             self.ws_aux = L.Workspace(self.device)      # scratch of the side lane (weight gradients)
             self.ws_det = L.Workspace(self.device)      # scratch of the detection filter (either lane)
         self._reg_fresh = False
-        # lock map: stage 1 = conv1-52 locked (shipped source), stage 2 = all trainable
-        self.lock = dict(lock) if lock is not None else {i: (stage == 1 and i <= 52) for i in range(1, self.score_layer + 1)}
+        # lock map (the per-layer ``lock`` argument of conv_bn / conv, yolo/yolo3_net_pos.py:71-146): stage 1 = conv1-52
+        # locked (shipped source), stage 2 = all trainable; ``lock`` overlays the stage's map, layer by layer -- any map
+        self.lock = {i: (stage == 1 and i <= 52) for i in range(1, self.score_layer + 1)}
+        for i, v in (lock or {}).items():
+            if isinstance(i, bool) or not isinstance(i, (int, np.integer)) or not 1 <= i <= self.score_layer:
+                raise ValueError("lock: %r is not a layer of this net (1..%d)" % (i, self.score_layer))
+            self.lock[int(i)] = bool(v)
         self.layers = build_topology(self.num_class, self.k, self.mask_stride)
         self.by_idx = {l.idx: l for l in self.layers}
+        self._mark_pass_through()
+        if self.dtype == "fp8":
+            self._check_fp8_lock()
         self._lr = float(cfg.LEARNING_RATE)
         self.lr_dev = None       # device copy read by the optimizer kernel (set in _init_params)
         self.dp = None  # set by enable_data_parallel
@@ -342,6 +350,25 @@ class YOLONet(object):
     def trainable_names(self) -> List[str]:
         return list(self.arena_slices)
 
+    def _mark_pass_through(self) -> None:
+        """``needs_grad_into[i]``: a trainable layer sits at or upstream of layer i's output (0 = the image).  A LOCKED layer
+        of a training net with such an input is "pass-through": it trains nothing, but the loss gradient crosses it on its
+        way to the trainable layers upstream (TF autodiff does that unasked).  It runs like a trainable layer in inference
+        mode -- conv -> raw, bn_act_fwd with the folded moving statistics -- and keeps raw, dx and its flipped weights for
+        the backward pass (bn_frozen_bwd + the ordinary data-gradient convs)."""
+        up_to = {0: False}
+        for l in self.layers:
+            l.lock = self.lock[l.idx]
+            ins = [i for i in (l.src, l.src_up, l.shortcut) if i is not None]
+            into = any(up_to[i] for i in ins)
+            l.passthru = bool(self.training and l.lock and into)
+            up_to[l.idx] = into or (not l.lock)
+        self._needs_grad_into = up_to
+
+    def pass_through_layers(self) -> List[int]:
+        """locked layers the backward pass crosses (empty for the reference's two stages)"""
+        return [l.idx for l in self.layers if l.passthru]
+
     @property
     def learning_rate(self) -> float:
         """AdamOptimizer(learning_rate) (train_yolo3_mask.py:38,55).  The optimizer kernel reads it from
@@ -393,22 +420,7 @@ class YOLONet(object):
             l.Ho, l.pad_t = L.same_pads(H, l.k, l.stride)
             l.Wo, l.pad_l = L.same_pads(W, l.k, l.stride)
             spatial[l.idx] = (l.Ho, l.Wo)
-        has_trainable_upto = {0: False}
-        for l in self.layers:
-            up = has_trainable_upto[l.src]
-            if l.src_up is not None:
-                up = up or has_trainable_upto[l.src_up]
-            if l.shortcut is not None:
-                up = up or has_trainable_upto[l.shortcut]
-            has_trainable_upto[l.idx] = up or (not l.lock)
-        self._needs_grad_into = {i: v for i, v in has_trainable_upto.items()}
-        if self.training:
-            for l in self.layers:
-                ups = [l.src] + ([l.src_up] if l.src_up is not None else [])
-                if l.lock and any(has_trainable_upto[u] for u in ups):
-                    raise NotImplementedError(
-                        "layer %d is locked but has trainable layers upstream; only the reference's two stages "
-                        "(conv1-52 locked, or nothing locked) are supported (yolo/yolo3_net_pos.py:155-156)" % l.idx)
+        has_trainable_upto = self._needs_grad_into       # (_mark_pass_through)
         # activation tensors are views into ONE allocation: a process that has allocated and freed a lot of
         # device memory gets later allocations on worse-mapped memory (B = 32 inference 4.8 -> 3.9 k img/s after
         # 13 GB of tensors were created and freed, no compute involved: tools/micro/infer_after_alloc.py), and
@@ -417,7 +429,7 @@ class YOLONet(object):
         batch_of = lambda l: 2 * B if (self.pair and l.idx <= self._pair_P) else B
         for l in self.layers:
             n = batch_of(l) * l.Ho * l.Wo * l.cout
-            tb = self.training and (not l.lock) and l.kind != "lin"
+            tb = self.training and (not l.lock or l.passthru) and l.kind != "lin"      # (keeps its conv output: l.raw)
             need += ((n * (4 if l.kind == "lin" else 2) + 255) // 256) * 256 * (2 if tb else 1)
         self._act_arena = torch.zeros(need, dtype=torch.uint8, device=dev)
         cursor = [0]
@@ -435,23 +447,24 @@ class YOLONet(object):
                 l.act = zeros4(B, l.Ho, l.Wo, l.cout, F32)
             else:
                 l.act = zeros4(batch_of(l), l.Ho, l.Wo, l.cout, BF16)
-                l.raw = zeros4(B, l.Ho, l.Wo, l.cout, BF16) if train_bn else None
+                l.raw = zeros4(B, l.Ho, l.Wo, l.cout, BF16) if (train_bn or l.passthru) else None
             if l.idx > 1:
                 K = l.k * l.k * l.cin
                 l.wp = torch.zeros(l.cout, K, dtype=BF16, device=dev)
             # (a batch-normalised layer of 16 * odd channels -- m = 1's conv82 / conv83 -- keeps its own width: its gradient is
             # the 16-channel source of its data-gradient conv, which the conv takes as it is)
             l.cout_pad = l.cout if (l.cout % 32 == 0 or (l.kind != "lin" and l.cout % 16 == 0)) else ((l.cout + 31) // 32) * 32
-            if self.training and not l.lock:
+            if self.training and (not l.lock or l.passthru or l.kind == "lin"):
                 # gradient wrt this layer's conv output (bf16, row pitch cout_pad: GRAD_LD for the heads and for conv82 up to
-                # k_map = 5, 64 for the 49 score maps of k_map = 7)
+                # k_map = 5, 64 for the 49 score maps of k_map = 7).  The four linear layers own it locked or not: the loss
+                # kernels write it
                 if l.kind == "lin":
                     l.dx = torch.zeros(B, l.Ho, l.Wo, l.cout_pad, dtype=BF16, device=dev)
                 else:
                     l.dx = torch.zeros(B, l.Ho, l.Wo, l.cout, dtype=BF16, device=dev)
             if self.training and has_trainable_upto[l.idx] and l.kind != "lin":
                 l.grad = torch.zeros(B, l.Ho, l.Wo, l.cout, dtype=BF16, device=dev)
-            needs_dgrad = self.training and (not l.lock) and l.idx > 1 and (
+            needs_dgrad = self.training and (not l.lock or l.passthru) and l.idx > 1 and (
                 has_trainable_upto[l.src] or (l.src_up is not None and has_trainable_upto[l.src_up]))
             if needs_dgrad:
                 l.wdg = torch.zeros(l.cin, l.k * l.k * l.cout_pad, dtype=BF16, device=dev)
@@ -503,7 +516,7 @@ class YOLONet(object):
             for l in self.layers:
                 if l.wgrad_desc is not None:
                     need = max(need, L.conv2d_wgrad_workspace(l.wgrad_desc))
-                if l.dx is not None and l.kind != "lin":
+                if l.dx is not None and l.kind != "lin" and not l.lock:
                     need = max(need, L.load().disyolo_bn_act_bwd_workspace(B * l.Ho * l.Wo, l.cout))
             if not l1.lock:
                 need = max(need, L.load().disyolo_conv_first_wgrad_workspace(B, S, S, l1.cout))
@@ -523,8 +536,23 @@ class YOLONet(object):
     FP8_DUAL = (4, 9, 26, 43, 52)     # outputs that bf16 layers consume too (skip2..5, the trunk's end)
 
     def _fp8_layers(self):
-        """layers that run in fp8: conv FP8_FROM..52 when they are in inference mode (locked, or an inference net)"""
-        return [l for l in self.layers if self.FP8_FROM <= l.idx <= self.FP8_UPTO and (l.lock or not self.training)]
+        """layers that run in fp8: conv FP8_FROM..52 when they are in inference mode and no gradient crosses them (an
+        inference net, or the locked prefix of a training net)"""
+        P = self._backbone_prefix() if self.training else self.FP8_UPTO
+        return [l for l in self.layers if self.FP8_FROM <= l.idx <= min(self.FP8_UPTO, P)]
+
+    def _check_fp8_lock(self) -> None:
+        """a training net runs fp8 only in its gradient-free locked prefix: a lock map that would start the fp8 chain and
+        then break it (a trainable or pass-through layer inside FP8_FROM..52) is refused -- no mixed chain"""
+        if not self.training:
+            return
+        P = self._backbone_prefix()
+        if self.FP8_FROM <= P < self.FP8_UPTO:
+            l = self.by_idx[P + 1]
+            raise ValueError("dtype='fp8': layer %d is %s, but conv%d-%d in front of it would run in fp8; the fp8 path covers "
+                             "conv%d-%d only as one gradient-free locked prefix (lock them all, or use dtype='bf16')"
+                             % (l.idx, "pass-through (locked behind a trainable layer)" if l.lock else "trainable",
+                                self.FP8_FROM, P, self.FP8_FROM, self.FP8_UPTO))
 
     def _plan_fp8(self) -> None:
         dev = self.device
@@ -619,6 +647,10 @@ class YOLONet(object):
                                                                 decay=cfg.BN_DECAY, eps=cfg.BN_EPSILON, sync=l.csync),
                                                   alpha=cfg.ALPHA)
                         l.fused_fwd = True
+            elif l.passthru:
+                # a locked layer the backward pass crosses: the conv output is kept (l.raw), the folded moving statistics and
+                # the activation follow in bn_act_fwd -- never part of a fused launch, no statistics, no moving-average update
+                l.desc = L.make_conv_desc(x0, l.wp, l.raw, l.k, l.stride, x1=x1)
             else:
                 l.desc = L.make_conv_desc(x0, l.wp, l.act, l.k, l.stride, x1=x1, scale=l.scale, shift=l.shift,
                                           residual=res, leaky=True, alpha=cfg.ALPHA)
@@ -860,7 +892,7 @@ class YOLONet(object):
         self._xstep_slot, self._xstep_reader = {}, {}
         slot = 0
         for l in self.layers:
-            if l.idx <= P:
+            if l.idx <= P or l.lock:      # (a locked layer has no weight gradient: nothing of it reads its inputs on the side lane)
                 continue
             for src in (l.src, l.src_up, l.shortcut):
                 if src is not None and 1 <= src <= P:
@@ -873,7 +905,7 @@ class YOLONet(object):
             raise L.DisyoloError("overlap_tail: too many backbone outputs feed trainable layers")
         order = [x.idx for x in self.backward_order() if not x.lock]
         for src in self._xstep_slot:
-            readers = [x.idx for x in self.layers if x.idx > P and src in (x.src, x.src_up, x.shortcut)]
+            readers = [x.idx for x in self.layers if x.idx > P and not x.lock and src in (x.src, x.src_up, x.shortcut)]
             self._xstep_reader[src] = max(readers, key=order.index)
         # where the next replay's main lane waits.  A wait that is enqueued before its event has completed costs the waiting
         # stream ~3 us whether or not it ever blocks (tools/micro/event_cost.hip), so the waits are merged: the side lane is
@@ -935,8 +967,11 @@ class YOLONet(object):
                 L.quant_fp8(q.act, q.act8, q.s_out)
 
     def _inference_mode(self, idxs, is_training: bool) -> bool:
-        """every one of these layers normalises with its folded moving statistics in this pass"""
-        return all(self.by_idx[i].kind == "lin" or not (is_training and self.training and not self.by_idx[i].lock) for i in idxs)
+        """every one of these layers normalises with its folded moving statistics in this pass and need not keep its conv
+        output (a pass-through layer does in a training pass: it stays out of every fused launch)"""
+        train = is_training and self.training
+        return all(not (train and self.by_idx[i].passthru) and (self.by_idx[i].kind == "lin" or not (train and not self.by_idx[i].lock))
+                   for i in idxs)
 
     def _fusion_plan(self, is_training: bool, first: int, last: int):
         """layer index -> fused launch that replaces the layer (None: covered by a later entry).  Groups of layers whose
@@ -1011,6 +1046,9 @@ class YOLONet(object):
             return
         if l.kind == "lin":
             L.conv2d_fwd(l.desc)
+        elif l.passthru and is_training:
+            L.conv2d_fwd(l.desc)                       # raw conv; the moving statistics are folded in scale / shift
+            L.bn_act_fwd(l.raw, l.scale, l.shift, res, l.act, M, l.cout, cfg.ALPHA)
         elif train_bn:
             L.conv2d_fwd(l.desc)                       # raw conv + per-channel partial sums
             if l.fused_fwd and L.TUNER is None:
@@ -1018,9 +1056,10 @@ class YOLONet(object):
             self._bn_finalize(l, M)
             L.bn_act_fwd(l.raw, l.scale, l.shift, res, l.act, M, l.cout, cfg.ALPHA)
         else:
-            if self.training and not l.lock:
+            if self.training and (not l.lock or l.passthru):
                 # a training-mode plan evaluated with is_training=False: moving statistics
-                L.bn_fold(l.gamma, l.beta, l.mm, l.mv, cfg.BN_EPSILON, l.scale, l.shift)
+                if not l.lock:
+                    L.bn_fold(l.gamma, l.beta, l.mm, l.mv, cfg.BN_EPSILON, l.scale, l.shift)
                 d = L.make_conv_desc(self._input_of(l, l.src), l.wp, l.act, l.k, l.stride,
                                      x1=self._input_of(l, l.src_up) if l.src_up is not None else None,
                                      scale=l.scale, shift=l.shift, residual=res, leaky=True, alpha=cfg.ALPHA)
@@ -1391,7 +1430,7 @@ class YOLONet(object):
         data-gradient conv straight into it, "up" = through the 2x upsampling, "add" = a shortcut's add)"""
         last: Dict[int, Tuple[int, str]] = {}
         for l in visit:
-            if l.lock:
+            if l.lock and not l.passthru:
                 continue
             if l.kind != "lin" and l.shortcut is not None and self.by_idx[l.shortcut].grad is not None:
                 last[l.shortcut] = (l.idx, "add")
@@ -1502,13 +1541,24 @@ class YOLONet(object):
             if l.idx == self.score_layer and getattr(self, "_mask_loss_pending", False):
                 L.lane_wait(self._mask_mark, 0)          # dscore comes from the side lane
                 self._mask_loss_pending = False
-            if l.lock:
-                # locked layers still pass gradients through their residual add only in
-                # stage 2; in stage 1 nothing upstream is trainable
-                continue
+            if l.lock and not l.passthru:
+                continue                  # nothing upstream trains: no gradient crosses this layer
             M = B * l.Ho * l.Wo
             if l.kind == "lin":
                 dx, ld = l.dx, l.cout_pad
+            elif l.lock:
+                # a locked layer on the gradient's way (yolo/yolo3_net_pos.py:76-81: moving statistics, nothing to train):
+                # d conv = g * leaky'(z) * scale with the raw / scale / shift its forward used; the shortcut's source gets g
+                if not l.grad_set:
+                    raise L.DisyoloError("layer %d received no gradient" % l.idx)
+                sc = self.by_idx[l.shortcut] if l.shortcut is not None else None
+                if sc is not None and sc.grad is None:
+                    sc = None
+                kw = dict(shortcut_grad=sc.grad, shortcut_accumulate=sc.grad_set) if sc is not None else {}
+                L.bn_frozen_bwd(l.grad, l.raw, l.scale, l.shift, l.dx, M, l.cout, cfg.ALPHA, **kw)
+                dx, ld = l.dx, l.cout
+                if sc is not None:
+                    sc.grad_set = True
             else:
                 if not l.grad_set:
                     raise L.DisyoloError("layer %d received no gradient" % l.idx)
@@ -1581,6 +1631,8 @@ class YOLONet(object):
                     up = tgt
                     L.upsample2x_bwd(kw["tmp"], up.grad, B, l.H, l.W, up.cout, 0, up.cout, accumulate=up.grad_set)
                     up.grad_set = True
+            if l.lock:
+                continue                  # no weight gradient, no optimizer slice, no re-pack
             if pending and pending[-1][4] != side:
                 flush()
             pending.append((l, dx, ld, M, side))

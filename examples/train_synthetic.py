@@ -2,7 +2,7 @@
 Solver (recorded pipelined step: the next batch's backbone and its data loading beside the current step) -> TF-format checkpoint -> reload into an
 inference net -> detections + instance masks for one image.
 
-    python examples/train_synthetic.py [--steps 40] [--size 192] [--batch 4] [--out /tmp/disyolo_example]
+    python examples/train_synthetic.py [--steps 40] [--size 192] [--batch 4] [--out /tmp/disyolo_example] [--lock 62-64]
 
 It mirrors what the reference's ``train_yolo3_mask.py:237-248`` (train) and ``calculate_test_map.py`` (test) do
 with a real dataset; swap ``synthetic_labels`` for ``disyolo_amd.pre_process.load_verify_contour(path, 'train')``
@@ -42,6 +42,18 @@ def synthetic_labels(rng, n):
     return out
 
 
+def parse_lock(text):
+    """"5-9,62-64" -> {5: True, ..., 9: True, 62: True, 63: True, 64: True}; a leading "!" unlocks ("!40-52": train conv40-52
+    in stage 1).  The reference's per-layer ``lock`` argument (yolo/yolo3_net_pos.py:71-146) over the stage's map."""
+    lock = {}
+    for part in filter(None, (p.strip() for p in (text or "").split(","))):
+        value = not part.startswith("!")
+        lo, _, hi = part.lstrip("!").partition("-")
+        for i in range(int(lo), int(hi or lo) + 1):
+            lock[i] = value
+    return lock
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=40)
@@ -52,6 +64,7 @@ def main():
                     help="position-sensitive mask grid (k x k score maps, cfg.K_MAP)")
     ap.add_argument("--mask-stride", type=int, default=cfg.MASK_STRIDE, choices=(4, 2, 1),
                     help="mask subnet: score maps at size/4, size/2 (cfg.MASK_STRIDE) or size (m = 1/4, 1/2, 1)")
+    ap.add_argument("--lock", default="", help="layer ranges to lock on top of stage 1, e.g. 5-9,62-64 (\"!40-52\" unlocks)")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     rng = np.random.RandomState(0)
@@ -60,7 +73,9 @@ def main():
     # --- train: stage 1 (conv1-52 locked), batches built on the GPU from the polygon records
     data = defect_train(labels, batch_size=args.batch, image_size=args.size, device=dev, rng=np.random.RandomState(1))
     net = YOLONet(training=True, device=dev, image_size=args.size, batch_size=args.batch, stage=1, seed=0, k_map=args.k_map,
-                  mask_stride=args.mask_stride)
+                  mask_stride=args.mask_stride, lock=parse_lock(args.lock))
+    if net.pass_through_layers():
+        print("locked layers the gradient crosses:", net.pass_through_layers())
     solver = Solver(net, data, output_dir=args.out, max_iter=args.steps, summary_iter=max(1, args.steps // 4),
                     save_iter=args.steps, log=print)
     hist = solver.train()

@@ -356,6 +356,16 @@ int disyolo_bn_act_bwd_partials(const void* dy, const void* x, const float* scal
                                 float* dbeta, int64_t rows, int C, float alpha, const float* partials,
                                 int part_rows, void* shortcut_grad, int shortcut_accumulate, void* workspace,
                                 size_t workspace_bytes, void* stream);
+/* backward of a LOCKED layer (conv_bn / res_conv_bn with lock=True, yolo/yolo3_net_pos.py:76-81,134-136,148-151): the
+ * layer normalises with its moving statistics even in training, so with scale = gamma*rsqrt(moving_var+eps),
+ * shift = beta - moving_mean*scale (disyolo_bn_fold) and z = x*scale + shift its backward has no batch-statistics
+ * terms and no parameter gradients:  dx = bf16(scale_c * (dy * (z > 0 ? 1 : alpha))), f32 math on bf16 [rows,C]
+ * operands.  x is the layer's conv output (the pre-activation decides the branch, not the stored activation, which
+ * for a residual layer has the shortcut folded in).  shortcut_grad / shortcut_accumulate as in disyolo_bn_act_bwd.
+ * dx == dy (in place) is allowed; shortcut_grad must alias none of dy, x, dx.  No workspace; C % 8 == 0. */
+int disyolo_bn_frozen_bwd(const void* dy, const void* x, const float* scale, const float* shift, void* dx,
+                          int64_t rows, int C, float alpha, void* shortcut_grad, int shortcut_accumulate,
+                          void* stream);
 
 /* ---- small data-movement ops of the backward pass ---- */
 /* dst[b,y,x,c] = sum of the 2x2 block of src (gradient of resize_nearest_neighbor x2),
