@@ -429,13 +429,27 @@ def save_net(net, prefix: str) -> None:
     save_checkpoint(prefix, {k: v.detach().cpu().numpy() for k, v in net.params.items()})
 
 
-def restore_net(net, prefix: str, stage1_include: bool = False) -> List[str]:
+def restore_net(net, prefix: str, stage1_include: bool = False, reinit_mismatched_heads: bool = False) -> List[str]:
     """stage1_include=True: ``assign_from_checkpoint_fn(include, ignore_missing_vars=True)`` -- variables in
     the include list that the file holds (shape mismatches raise, as TF does); False: ``Saver.restore`` of
     every variable (a missing one raises).  Shapes are checked first: a file that both lacks variables and holds one at
-    another shape (another mask_stride or k_map) raises the ValueError naming that variable.  Returns the restored names."""
+    another shape (another mask_stride or k_map) raises the ValueError naming that variable.  Returns the restored names.
+
+    reinit_mismatched_heads=True starts a new class list from a checkpoint of another one: the weights and biases of the
+    three detection heads (conv59 / 67 / 75) whose last dimension differs from the graph's are skipped and keep their
+    initialisers; any other mismatch still raises.  The skipped names are left in ``net.restore_skipped`` (empty otherwise)."""
     names = stage1_include_names() if stage1_include else list(net.params)
     got = load_checkpoint(prefix, names)
+    skipped = []
+    if reinit_mismatched_heads:
+        heads = ["yolo/convolutional%d/%s" % (i, leaf) for i in (59, 67, 75) for leaf in ("weights", "biases")]
+        for n in heads:
+            if (n in got and n in net.params and tuple(got[n].shape) != tuple(net.params[n].shape)
+                    and tuple(got[n].shape[:-1]) == tuple(net.params[n].shape[:-1])):
+                skipped.append(n)
+                del got[n]
+        names = [n for n in names if n not in skipped]
+    net.restore_skipped = skipped
     # shapes first: a checkpoint of another mask subnet (mask_stride) or grid (k_map) both lacks variables and holds some
     # at another shape -- the error names the first such variable
     for n, a in got.items():

@@ -165,60 +165,19 @@ __device__ __forceinline__ int greedy_nms_global(int n, const int* list, const f
   return nk;
 }
 
-__global__ __launch_bounds__(NMS_T) void nms_class_kernel(const float4* boxes, const float* scores, const int* classes,
-                                                          int NC, int C, float thr, float nms_thr, int max_det,
-                                                          int* list_g, float* live_g, int* kept_idx, float* kept_sc,
-                                                          int* kept_n) {
-  const int b = blockIdx.x / C, c = blockIdx.x - b * C, tid = threadIdx.x;
-  const int lane = tid & 63, wv = tid >> 6;
-  boxes += (size_t)b * NC;
-  scores += (size_t)b * NC;
-  classes += (size_t)b * NC;
-  int* list = list_g + (size_t)blockIdx.x * NC;
-  float* live_glob = live_g + (size_t)blockIdx.x * NC;
-  kept_idx += (size_t)blockIdx.x * max_det;
-  kept_sc += (size_t)blockIdx.x * max_det;
-  __shared__ int s_wcnt[2][NMS_CB][NMS_W];
+// The greedy loop over one (image, class) list, shared by the kernel that compacts its own list (<= 16 classes) and the one
+// that takes a segment of the bucketed list (more classes): list[0..n) holds candidate indices in ascending order, scores /
+// boxes are the image's, live_glob has room for n floats.  All NMS_T threads of the block call it; kept_idx / kept_sc receive
+// the survivors in selection order and the count is returned to every thread.
+__device__ __forceinline__ int greedy_nms_block(const int n, const int* list, const float4* boxes, const float* scores,
+                                                float* live_glob, const float nms_thr, const int max_det, int* kept_idx,
+                                                float* kept_sc) {
+  const int tid = threadIdx.x, wv = tid >> 6;
   __shared__ float s_ws[2][NMS_W];
   __shared__ int s_wp[2][NMS_W];
   __shared__ float4 s_wb[2][NMS_W];
   __shared__ int s_kidx[64];
   __shared__ float s_ksc[64];
-  // ---- ordered compaction: wave ballots; eight rounds of 1,024 candidates per barrier, their 16 loads in flight together
-  //      (a round per barrier is a load round trip + a store drain each: 60 us for the 20 rounds of a 576^2 image even when
-  //      nothing passes the threshold)
-  int total = 0;
-  for (int base = 0, bt = 0; base < NC; base += NMS_T * NMS_CB, ++bt) {
-    bool f[NMS_CB];
-    unsigned long long mask[NMS_CB];
-#pragma unroll
-    for (int j = 0; j < NMS_CB; ++j) {
-      const int i = base + j * NMS_T + tid;
-      const int ii = i < NC ? i : 0;
-      const float sv = scores[ii];
-      const int cv = classes[ii];
-      f[j] = (i < NC) && (sv > thr) && (cv == c);
-    }
-#pragma unroll
-    for (int j = 0; j < NMS_CB; ++j) {
-      mask[j] = __ballot(f[j]);
-      if (lane == 0) s_wcnt[bt & 1][j][wv] = __popcll(mask[j]);
-    }
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < NMS_CB; ++j) {
-      int off = total;
-#pragma unroll
-      for (int w = 0; w < NMS_W; ++w) {
-        const int cw = s_wcnt[bt & 1][j][w];
-        if (w < wv) off += cw;
-        total += cw;
-      }
-      if (f[j]) list[off + __popcll(mask[j] & ((1ull << lane) - 1ull))] = base + j * NMS_T + tid;
-    }
-  }
-  __syncthreads();  // list[] (global) written by this block, read below by all its threads
-  const int n = total;
   int nk = 0;
   if (n <= NMS_K * NMS_T) {
     float sc[NMS_K];
@@ -312,7 +271,210 @@ __global__ __launch_bounds__(NMS_T) void nms_class_kernel(const float4* boxes, c
     __syncthreads();
     nk = greedy_nms_global(n, list, boxes, live_glob, nms_thr, max_det, kept_idx, kept_sc, s_ws[0], s_wp[0]);
   }
+  return nk;
+}
+
+__global__ __launch_bounds__(NMS_T) void nms_class_kernel(const float4* boxes, const float* scores, const int* classes,
+                                                          int NC, int C, float thr, float nms_thr, int max_det,
+                                                          int* list_g, float* live_g, int* kept_idx, float* kept_sc,
+                                                          int* kept_n) {
+  const int b = blockIdx.x / C, c = blockIdx.x - b * C, tid = threadIdx.x;
+  const int lane = tid & 63, wv = tid >> 6;
+  boxes += (size_t)b * NC;
+  scores += (size_t)b * NC;
+  classes += (size_t)b * NC;
+  int* list = list_g + (size_t)blockIdx.x * NC;
+  float* live_glob = live_g + (size_t)blockIdx.x * NC;
+  kept_idx += (size_t)blockIdx.x * max_det;
+  kept_sc += (size_t)blockIdx.x * max_det;
+  __shared__ int s_wcnt[2][NMS_CB][NMS_W];
+  // ---- ordered compaction: wave ballots; eight rounds of 1,024 candidates per barrier, their 16 loads in flight together
+  //      (a round per barrier is a load round trip + a store drain each: 60 us for the 20 rounds of a 576^2 image even when
+  //      nothing passes the threshold)
+  int total = 0;
+  for (int base = 0, bt = 0; base < NC; base += NMS_T * NMS_CB, ++bt) {
+    bool f[NMS_CB];
+    unsigned long long mask[NMS_CB];
+#pragma unroll
+    for (int j = 0; j < NMS_CB; ++j) {
+      const int i = base + j * NMS_T + tid;
+      const int ii = i < NC ? i : 0;
+      const float sv = scores[ii];
+      const int cv = classes[ii];
+      f[j] = (i < NC) && (sv > thr) && (cv == c);
+    }
+#pragma unroll
+    for (int j = 0; j < NMS_CB; ++j) {
+      mask[j] = __ballot(f[j]);
+      if (lane == 0) s_wcnt[bt & 1][j][wv] = __popcll(mask[j]);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < NMS_CB; ++j) {
+      int off = total;
+#pragma unroll
+      for (int w = 0; w < NMS_W; ++w) {
+        const int cw = s_wcnt[bt & 1][j][w];
+        if (w < wv) off += cw;
+        total += cw;
+      }
+      if (f[j]) list[off + __popcll(mask[j] & ((1ull << lane) - 1ull))] = base + j * NMS_T + tid;
+    }
+  }
+  __syncthreads();  // list[] (global) written by this block, read below by all its threads
+  const int nk = greedy_nms_block(total, list, boxes, scores, live_glob, nms_thr, max_det, kept_idx, kept_sc);
   if (tid == 0) kept_n[blockIdx.x] = nk;
+}
+
+// ---- more than 16 classes: one ordered pass per image buckets the candidates by class, the greedy loop runs per segment ----
+// bucket_class_kernel, one block per image: pass 1 counts the candidates with score > thr per class (LDS histogram, integer
+// adds), an exclusive scan gives the class offsets, pass 2 walks the candidates again in index order, NMS_T at a time, and
+// scatters their indices: inside a wave the lanes of one class rank themselves with a ballot per distinct class, the waves'
+// per-class counts go through LDS, so a class's segment stays in candidate-index order (ties are decided by position).
+// Work and memory are B NC, whatever the class count.
+constexpr int WD_MAXC = 80;
+
+__global__ __launch_bounds__(NMS_T) void bucket_class_kernel(const float* scores, const int* classes, int NC, int C, float thr,
+                                                             int* list_g, int* off_g) {
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  scores += (size_t)b * NC;
+  classes += (size_t)b * NC;
+  int* list = list_g + (size_t)b * NC;
+  __shared__ int s_cur[WD_MAXC];            // next free position of each class
+  __shared__ int s_wc[NMS_W][WD_MAXC];      // this tile's candidates per (wave, class)
+  if (tid < C) s_cur[tid] = 0;
+  for (int e = tid; e < NMS_W * WD_MAXC; e += NMS_T) (&s_wc[0][0])[e] = 0;
+  __syncthreads();
+  for (int i = tid; i < NC; i += NMS_T) {
+    const int cv = classes[i];
+    if (scores[i] > thr && cv >= 0 && cv < C) atomicAdd(&s_cur[cv], 1);
+  }
+  __syncthreads();
+  if (tid == 0) {
+    int o = 0;
+    for (int c = 0; c < C; ++c) {
+      const int n = s_cur[c];
+      s_cur[c] = o;
+      off_g[b * (WD_MAXC + 1) + c] = o;
+      o += n;
+    }
+    for (int c = C; c <= WD_MAXC; ++c) off_g[b * (WD_MAXC + 1) + c] = o;
+  }
+  __syncthreads();
+  for (int base = 0; base < NC; base += NMS_T) {
+    const int i = base + tid;
+    const int ii = i < NC ? i : 0;
+    const int cv = classes[ii];
+    const bool f = i < NC && scores[ii] > thr && cv >= 0 && cv < C;
+    int rank = 0;
+    unsigned long long todo = __ballot(f);
+    while (todo) {                               // (wave-uniform) one round per distinct class among the wave's candidates
+      const int c0 = __shfl(cv, __ffsll((long long)todo) - 1, 64);
+      const unsigned long long m = __ballot(f && cv == c0);
+      if (f && cv == c0) rank = __popcll(m & ((1ull << lane) - 1ull));
+      if (lane == 0) s_wc[wv][c0] = __popcll(m);
+      todo &= ~m;
+    }
+    __syncthreads();
+    if (f) {
+      int off = s_cur[cv] + rank;
+      for (int w = 0; w < wv; ++w) off += s_wc[w][cv];
+      list[off] = i;
+    }
+    __syncthreads();
+    if (tid < C) {
+      int n = 0;
+#pragma unroll
+      for (int w = 0; w < NMS_W; ++w) {
+        n += s_wc[w][tid];
+        s_wc[w][tid] = 0;
+      }
+      s_cur[tid] += n;
+    }
+    __syncthreads();
+  }
+}
+
+__global__ __launch_bounds__(NMS_T) void nms_segment_kernel(const float4* boxes, const float* scores, int NC, int C,
+                                                            float nms_thr, int max_det, const int* list_g, const int* off_g,
+                                                            float* live_g, int* kept_idx, float* kept_sc, int* kept_n) {
+  const int b = blockIdx.x / C, c = blockIdx.x - b * C;
+  const int o0 = off_g[b * (WD_MAXC + 1) + c], n = off_g[b * (WD_MAXC + 1) + c + 1] - o0;
+  if (n <= 0) {                                  // (block-uniform) an empty class
+    if (threadIdx.x == 0) kept_n[blockIdx.x] = 0;
+    return;
+  }
+  const int nk = greedy_nms_block(n, list_g + (size_t)b * NC + o0, boxes + (size_t)b * NC, scores + (size_t)b * NC,
+                                  live_g + (size_t)b * NC + o0, nms_thr, max_det, kept_idx + (size_t)blockIdx.x * max_det,
+                                  kept_sc + (size_t)blockIdx.x * max_det);
+  if (threadIdx.x == 0) kept_n[blockIdx.x] = nk;
+}
+
+// k-way merge of the classes' kept lists, each already in selection order (score descending, ties by lower candidate index):
+// max_det rounds of "best head among the C lists" with the same tie rule; one wave per image, a lane holds the heads of
+// classes lane and lane + 64.  Up to 80 * max_det survivors, none of them in LDS.
+__global__ __launch_bounds__(64) void nms_merge_kway_kernel(const float4* boxes, const int* classes, int NC, int C,
+                                                            int max_det, const int* kept_idx, const float* kept_sc,
+                                                            const int* kept_n, float* det, int* det_count) {
+  const int b = blockIdx.x, lane = threadIdx.x;
+  boxes += (size_t)b * NC;
+  classes += (size_t)b * NC;
+  for (int r = lane; r < max_det * 6; r += 64) det[(size_t)b * max_det * 6 + r] = 0.f;
+  __syncthreads();
+  int hn[2], hp[2], hi[2];
+  float hs[2];
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const int c = lane + 64 * j;
+    hn[j] = c < C ? kept_n[b * C + c] : 0;
+    hp[j] = 0;
+    hs[j] = -1.f;
+    hi[j] = 0x7fffffff;
+    if (hn[j] > 0) {
+      hs[j] = kept_sc[((size_t)b * C + c) * max_det];
+      hi[j] = kept_idx[((size_t)b * C + c) * max_det];
+    }
+  }
+  int nd = 0;
+  for (; nd < max_det; ++nd) {
+    const int mine = nms_better(hs[1], hi[1], hs[0], hi[0]) ? 1 : 0;
+    float ws = mine ? hs[1] : hs[0];
+    int wi = mine ? hi[1] : hi[0];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const float v2 = __shfl_xor(ws, o, 64);
+      const int p2 = __shfl_xor(wi, o, 64);
+      if (nms_better(v2, p2, ws, wi)) {
+        ws = v2;
+        wi = p2;
+      }
+    }
+    if (!(ws > 0.f)) break;                      // every list is used up (kept scores are > thr >= 0); uniform exit
+    if (lane == 0) {
+      float* o = det + ((size_t)b * max_det + nd) * 6;
+      const float4 bx = boxes[wi];
+      o[0] = bx.x;
+      o[1] = bx.y;
+      o[2] = bx.z;
+      o[3] = bx.w;
+      o[4] = (float)classes[wi];
+      o[5] = ws;
+    }
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      if (hi[j] == wi && hs[j] > 0.f) {          // candidate indices are unique: exactly one head advances
+        const int c = lane + 64 * j;
+        ++hp[j];
+        hs[j] = -1.f;
+        hi[j] = 0x7fffffff;
+        if (hp[j] < hn[j]) {
+          hs[j] = kept_sc[((size_t)b * C + c) * max_det + hp[j]];
+          hi[j] = kept_idx[((size_t)b * C + c) * max_det + hp[j]];
+        }
+      }
+    }
+  }
+  if (lane == 0) det_count[b] = nd;
 }
 
 __global__ __launch_bounds__(64) void nms_merge_kernel(const float4* boxes, const int* classes, int NC, int C,
@@ -610,6 +772,22 @@ __global__ __launch_bounds__(256) void confusion16_kernel(const unsigned char* t
   if (threadIdx.x < 16 && h[threadIdx.x]) atomicAdd(&conf[threadIdx.x], (unsigned long long)h[threadIdx.x]);
 }
 
+// the same counts for any number of labels (background + up to 80 classes): nlabel^2 LDS counters (26 KB at 81 labels)
+constexpr int CONF_MAXL = 81;
+__global__ __launch_bounds__(256) void confusion_n_kernel(const unsigned char* t, const unsigned char* p, int64_t n, int nl,
+                                                          unsigned long long* conf) {
+  __shared__ unsigned int h[CONF_MAXL * CONF_MAXL];
+  for (int e = threadIdx.x; e < nl * nl; e += 256) h[e] = 0;
+  __syncthreads();
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const int a = t[i], b = p[i];
+    if (a < nl && b < nl) atomicAdd(&h[a * nl + b], 1u);
+  }
+  __syncthreads();
+  for (int e = threadIdx.x; e < nl * nl; e += 256)
+    if (h[e]) atomicAdd(&conf[e], (unsigned long long)h[e]);
+}
+
 }  // namespace
 
 extern "C" size_t disyolo_detect_workspace(int B, int S, int num_class) {
@@ -617,7 +795,11 @@ extern "C" size_t disyolo_detect_workspace(int B, int S, int num_class) {
   const int g1 = S / 32;
   const size_t NC = 3 * (size_t)(16 * g1 * g1 + 4 * g1 * g1 + g1 * g1);
   // boxes (16 B) + scores + classes, per-class list + live, per-class kept (idx, score, n)
-  return (size_t)B * NC * (16 + 4 + 4) + (size_t)B * num_class * NC * 8 + (size_t)B * num_class * (64 * 8 + 4) + 256;
+  if (num_class <= 16)
+    return (size_t)B * NC * (16 + 4 + 4) + (size_t)B * num_class * NC * 8 + (size_t)B * num_class * (64 * 8 + 4) + 256;
+  // the same prefix, ONE bucketed list + live per image, the class offsets, per-class kept (idx, score, n)
+  return (size_t)B * NC * (16 + 4 + 4) + (size_t)B * NC * 8 + (size_t)B * (WD_MAXC + 1) * 4 +
+         (size_t)B * num_class * (64 * 8 + 4) + 256;
 }
 
 extern "C" int disyolo_detect(const float* logits3, const float* logits2, const float* logits1, int B, int S,
@@ -626,8 +808,9 @@ extern "C" int disyolo_detect(const float* logits3, const float* logits2, const 
                               size_t workspace_bytes, void* stream) {
   DY_REQUIRE(logits3 && logits2 && logits1 && anchors_host && clip_window && detections && det_count,
              "detect: null pointer");
-  DY_REQUIRE(B > 0 && S > 0 && S % 32 == 0 && num_class > 0 && num_class <= 16, "detect: bad sizes");
-  DY_REQUIRE(max_det > 0 && max_det <= 64 && num_class * max_det <= MAX_KEEP, "detect: max_det must be <= 64");
+  DY_REQUIRE(B > 0 && S > 0 && S % 32 == 0 && num_class > 0 && num_class <= WD_MAXC, "detect: bad sizes");
+  DY_REQUIRE(max_det > 0 && max_det <= 64 && (num_class > 16 || num_class * max_det <= MAX_KEEP),
+             "detect: max_det must be <= 64");
   DY_REQUIRE(obj_thresh >= 0.f, "detect: obj_thresh must be >= 0");
   if (!workspace || workspace_bytes < disyolo_detect_workspace(B, S, num_class)) {
     disyolo_set_error("detect: workspace too small");
@@ -662,12 +845,32 @@ extern "C" int disyolo_detect(const float* logits3, const float* logits2, const 
   p.boxes = (float4*)ws;                  ws += (size_t)B * c0 * 16;
   p.scores = (float*)ws;                  ws += (size_t)B * c0 * 4;
   p.classes = (int*)ws;                   ws += (size_t)B * c0 * 4;
+  hipStream_t st = (hipStream_t)stream;
+  if (num_class > 16) {
+    int* list = (int*)ws;                 ws += (size_t)B * c0 * 4;
+    float* live = (float*)ws;             ws += (size_t)B * c0 * 4;
+    int* off = (int*)ws;                  ws += (size_t)B * (WD_MAXC + 1) * 4;
+    int* kept_idx = (int*)ws;             ws += (size_t)B * num_class * 64 * 4;
+    float* kept_sc = (float*)ws;          ws += (size_t)B * num_class * 64 * 4;
+    int* kept_n = (int*)ws;
+    hipLaunchKernelGGL(decode_score_kernel, dim3(ceil_div(c0, 256), B), dim3(256), 0, st, p);
+    DY_CHECK_LAUNCH();
+    hipLaunchKernelGGL(bucket_class_kernel, dim3(B), dim3(NMS_T), 0, st, p.scores, p.classes, c0, num_class, obj_thresh,
+                       list, off);
+    DY_CHECK_LAUNCH();
+    hipLaunchKernelGGL(nms_segment_kernel, dim3(B * num_class), dim3(NMS_T), 0, st, p.boxes, p.scores, c0, num_class,
+                       nms_thresh, max_det, list, off, live, kept_idx, kept_sc, kept_n);
+    DY_CHECK_LAUNCH();
+    hipLaunchKernelGGL(nms_merge_kway_kernel, dim3(B), dim3(64), 0, st, p.boxes, p.classes, c0, num_class, max_det,
+                       kept_idx, kept_sc, kept_n, detections, det_count);
+    DY_CHECK_LAUNCH();
+    return DISYOLO_OK;
+  }
   int* list = (int*)ws;                   ws += (size_t)B * num_class * c0 * 4;
   float* live = (float*)ws;               ws += (size_t)B * num_class * c0 * 4;
   int* kept_idx = (int*)ws;               ws += (size_t)B * num_class * 64 * 4;
   float* kept_sc = (float*)ws;            ws += (size_t)B * num_class * 64 * 4;
   int* kept_n = (int*)ws;
-  hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(decode_score_kernel, dim3(ceil_div(c0, 256), B), dim3(256), 0, st, p);
   DY_CHECK_LAUNCH();
   hipLaunchKernelGGL(nms_class_kernel, dim3(B * num_class), dim3(NMS_T), 0, st, p.boxes, p.scores, p.classes, c0,
@@ -785,6 +988,19 @@ extern "C" int disyolo_confusion16(const uint8_t* true_map, const uint8_t* pred_
   int grid = (int)((n + 255) / 256);
   if (grid > 1024) grid = 1024;
   hipLaunchKernelGGL(confusion16_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, true_map, pred_map, n,
+                     (unsigned long long*)conf);
+  DY_CHECK_LAUNCH();
+  return DISYOLO_OK;
+}
+
+extern "C" int disyolo_confusion_n(const uint8_t* true_map, const uint8_t* pred_map, int64_t n, int nlabel, int64_t* conf,
+                                   void* stream) {
+  DY_REQUIRE(true_map && pred_map && conf && n > 0, "confusion_n: bad args");
+  DY_REQUIRE(nlabel >= 2 && nlabel <= CONF_MAXL, "confusion_n: nlabel must be in 2..81 (got %d)", nlabel);
+  DY_RECORD_OR_RUN([=](void* s) { return disyolo_confusion_n(true_map, pred_map, n, nlabel, conf, s); });
+  int grid = (int)((n + 255) / 256);
+  if (grid > 1024) grid = 1024;
+  hipLaunchKernelGGL(confusion_n_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, true_map, pred_map, n, nlabel,
                      (unsigned long long*)conf);
   DY_CHECK_LAUNCH();
   return DISYOLO_OK;

@@ -153,6 +153,164 @@ __global__ __launch_bounds__(256) void yolo_loss_kernel(YoloLoss3 P) {
   yolo_loss_body(P.p[s], bx, P.gx[s]);
 }
 
+// ---- class lists past the 32-channel rows: 3 (5 + C) <= ld <= 256, 1 <= C <= 80 ----
+// The arithmetic of yolo_loss_body, organised for rows of up to 85 floats.  A block still owns 256 consecutive (cell, anchor)
+// rows of one image and writes one partial row, so the partial layout and the final sum are the old ones.  Its rows are one
+// contiguous span of 256 D floats in logits and in labels: the block walks it in four chunks of WL_ROWS rows, each copied
+// into LDS by all threads with consecutive lanes on consecutive floats (a thread-per-row walk would put 4 D bytes between
+// lanes).  Four adjacent lanes then share a row: each takes the classes c = q (mod 4) and the true boxes k = q (mod 4), and
+// the four combine the maxima and sums through lane shuffles in a fixed order -- never the row in a per-thread array.  The
+// gradients replace the logits in LDS and leave as bf16 rows of `ld` channels, a wave per row, lanes along the channels.
+constexpr int WL_ROWS = 64;
+constexpr int WL_MAXD = 85;
+
+__device__ __forceinline__ float quad_max(float v) {
+  v = fmaxf(v, __shfl_xor(v, 1, 64));
+  return fmaxf(v, __shfl_xor(v, 2, 64));
+}
+__device__ __forceinline__ float quad_sum(float v) {   // (v0 + v1) + (v2 + v3) in every lane of the quad
+  v += __shfl_xor(v, 1, 64);
+  return v + __shfl_xor(v, 2, 64);
+}
+
+__device__ __forceinline__ void yolo_loss_wide_body(const YoloLossParams& p, const int ld, const int bx, const int gx) {
+  __shared__ float s_tb[64 * 4];
+  __shared__ float s_red[4][5];
+  __shared__ float s_t[WL_ROWS * WL_MAXD];   // logits of the chunk, then their gradients
+  __shared__ float s_l[WL_ROWS * WL_MAXD];   // labels of the chunk
+  const int b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  for (int i = tid; i < p.G * 4; i += 256) {
+    const int gidx = i >> 2, k = i & 3;
+    s_tb[i] = p.true_boxes[((size_t)b * p.G + gidx) * 5 + k];
+  }
+  const int D = 5 + p.C;
+  const int ncell = p.g * p.g, nrow = ncell * 3;
+  const float gf = (float)p.g, net = (float)p.S;
+  const int r = tid >> 2, q = tid & 3;
+  float l_obj = 0.f, l_noobj = 0.f, l_cls = 0.f, l_xy = 0.f, l_wh = 0.f;
+  for (int ch = 0; ch < 256 / WL_ROWS; ++ch) {
+    const int row0 = bx * 256 + ch * WL_ROWS;          // (block-uniform)
+    if (row0 >= nrow) break;
+    const int nr = min(WL_ROWS, nrow - row0);
+    const size_t base = ((size_t)b * nrow + row0) * D;
+    __syncthreads();                                   // the previous chunk's rows are written out; s_tb is complete
+    for (int e = tid; e < nr * D; e += 256) {
+      s_t[e] = p.logits[base + e];
+      s_l[e] = p.labels[base + e];
+    }
+    __syncthreads();
+    if (r < nr) {                                      // (the four lanes of a quad agree)
+      const int idx = row0 + r;
+      const int a = idx % 3, cell = idx / 3;
+      const int x = cell % p.g, y = cell / p.g;
+      float* t = s_t + r * D;
+      const float* lab = s_l + r * D;
+      const float t0 = t[0], t1 = t[1], t2 = t[2], t3 = t[3], conf = t[4];
+      const float sx = sigmoidf_(t0), sy = sigmoidf_(t1);
+      const float bxc = ((float)x + sx) / gf, byc = ((float)y + sy) / gf;
+      const float bw = expf(t2) * p.aw[a] / net, bh = expf(t3) * p.ah[a] / net;
+      const float pminx = bxc - bw / 2.f, pmaxx = bxc + bw / 2.f, pminy = byc - bh / 2.f, pmaxy = byc + bh / 2.f;
+      const float parea = bw * bh;
+      float best = 0.f;
+      for (int k = q; k < p.G; k += 4) {
+        const float txc = s_tb[k * 4 + 0], tyc = s_tb[k * 4 + 1], tw = s_tb[k * 4 + 2], th = s_tb[k * 4 + 3];
+        const float iw = fmaxf(fminf(pmaxx, txc + tw / 2.f) - fmaxf(pminx, txc - tw / 2.f), 0.f);
+        const float ih = fmaxf(fminf(pmaxy, tyc + th / 2.f) - fmaxf(pminy, tyc - th / 2.f), 0.f);
+        const float inter = iw * ih;
+        const float uni = fmaxf(parea + tw * th - inter, 1e-10f);
+        const float iou = fminf(fmaxf(inter / uni, 0.f), 1.f);
+        best = fmaxf(best, iou);
+      }
+      best = quad_max(best);
+      const float ignore = best < p.ignore_thresh ? 1.f : 0.f;
+      const float obj = lab[4];
+      const float ce = sigmoid_ce(obj, conf);
+      const float sconf = sigmoidf_(conf);
+      // class: sparse softmax CE against argmax(label[5:]) (first max): this lane's classes, then the quad's
+      int tc = 0x7fffffff;
+      float lm = -INFINITY, mx = -INFINITY;
+      for (int c = q; c < p.C; c += 4) {
+        const float lv = lab[5 + c];
+        if (lv > lm || tc == 0x7fffffff) {
+          lm = lv;
+          tc = c;
+        }
+        mx = fmaxf(mx, t[5 + c]);
+      }
+#pragma unroll
+      for (int o = 1; o <= 2; o <<= 1) {
+        const float lm2 = __shfl_xor(lm, o, 64);
+        const int tc2 = __shfl_xor(tc, o, 64);
+        if (tc2 != 0x7fffffff && (tc == 0x7fffffff || lm2 > lm || (lm2 == lm && tc2 < tc))) {
+          lm = lm2;
+          tc = tc2;
+        }
+      }
+      mx = quad_max(mx);
+      float den = 0.f;
+      for (int c = q; c < p.C; c += 4) den += expf(t[5 + c] - mx);
+      den = quad_sum(den);
+      const float lse = mx + logf(den);
+      const float ttc = t[5 + tc];                     // read before any lane of the quad overwrites it
+      const float tcx = lab[0] * gf - (float)x, tcy = lab[1] * gf - (float)y;
+      const float ttw = fminf(fmaxf(logf(lab[2] * net / p.aw[a]), -100.f), 100.f);
+      const float tth = fminf(fmaxf(logf(lab[3] * net / p.ah[a]), -100.f), 100.f);
+      const float whs = 2.f - lab[2] * lab[3];
+      const float whs2 = whs * whs * p.coord_scale;
+      const float dx_ = obj * (sx - tcx), dy_ = obj * (sy - tcy);
+      const float dw_ = obj * (t2 - ttw), dh_ = obj * (t3 - tth);
+      for (int c = q; c < p.C; c += 4) {
+        const float pr = expf(t[5 + c] - lse);
+        t[5 + c] = obj * p.class_scale * (pr - (c == tc ? 1.f : 0.f)) * p.inv_B;
+      }
+      if (q == 0) {
+        l_obj += obj * ce * p.obj_scale;
+        l_noobj += ignore * (1.f - obj) * ce * p.noobj_scale;
+        l_cls += obj * (lse - ttc) * p.class_scale;
+        l_xy += (dx_ * dx_ + dy_ * dy_) * whs2;
+        l_wh += (dw_ * dw_ + dh_ * dh_) * whs2;
+        t[0] = 2.f * obj * dx_ * whs2 * sx * (1.f - sx) * p.inv_B;
+        t[1] = 2.f * obj * dy_ * whs2 * sy * (1.f - sy) * p.inv_B;
+        t[2] = 2.f * obj * dw_ * whs2 * p.inv_B;
+        t[3] = 2.f * obj * dh_ * whs2 * p.inv_B;
+        t[4] = (obj * p.obj_scale + ignore * (1.f - obj) * p.noobj_scale) * (sconf - obj) * p.inv_B;
+      }
+    }
+    __syncthreads();
+    for (int rr = wv; rr < nr; rr += 4) {
+      const int idx = row0 + rr;
+      const int a = idx % 3, cell = idx / 3;
+      bf16* o = p.dlogits + ((size_t)b * ncell + cell) * ld;
+      for (int k = lane; k < D; k += 64) o[a * D + k] = (bf16)s_t[rr * D + k];
+      if (a == 2)
+        for (int k = 3 * D + lane; k < ld; k += 64) o[k] = (bf16)0.f;
+    }
+  }
+  l_obj = wave_sum(l_obj);
+  l_noobj = wave_sum(l_noobj);
+  l_cls = wave_sum(l_cls);
+  l_xy = wave_sum(l_xy);
+  l_wh = wave_sum(l_wh);
+  if (lane == 0) {
+    float* rd = s_red[wv];
+    rd[0] = l_obj; rd[1] = l_noobj; rd[2] = l_cls; rd[3] = l_xy; rd[4] = l_wh;
+  }
+  __syncthreads();
+  if (tid < 5) p.partial[((size_t)blockIdx.y * gx + bx) * 5 + tid] = s_red[0][tid] + s_red[1][tid] + s_red[2][tid] + s_red[3][tid];
+}
+__global__ __launch_bounds__(256) void yolo_loss_wide_kernel(YoloLoss3 P, int ld) {
+  int bx = blockIdx.x, s = 0;
+  if (bx >= P.gx[0]) {
+    bx -= P.gx[0];
+    s = 1;
+    if (bx >= P.gx[1]) {
+      bx -= P.gx[1];
+      s = 2;
+    }
+  }
+  yolo_loss_wide_body(P.p[s], ld, bx, P.gx[s]);
+}
+
 __device__ __forceinline__ double wave_sum_d(double v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
@@ -437,29 +595,11 @@ extern "C" size_t disyolo_yolo_loss_workspace(int B, int S, int num_class) {
   return blocks * 5 * sizeof(float);
 }
 
-extern "C" int disyolo_yolo_loss(const float* const logits[3], const float* const labels[3], const float* true_boxes,
-                                 int max_boxes, int B, int S, int num_class, const float* anchors_host,
-                                 float ignore_thresh, const float scales[4], void* const dlogits[3], float* losses,
-                                 void* workspace, size_t workspace_bytes, void* stream) {
-  DY_REQUIRE(logits && labels && true_boxes && anchors_host && scales && dlogits && losses, "yolo_loss: null pointer");
-  DY_REQUIRE(B > 0 && S > 0 && S % 32 == 0 && num_class > 0 && 3 * (5 + num_class) <= DL_LD && num_class <= 11,
-             "yolo_loss: bad sizes");
-  DY_REQUIRE(max_boxes > 0 && max_boxes <= 64, "yolo_loss: max_boxes must be in 1..64");
-  if (!workspace || workspace_bytes < disyolo_yolo_loss_workspace(B, S, num_class)) {
-    disyolo_set_error("yolo_loss: workspace too small");
-    return DISYOLO_E_WORKSPACE;
-  }
-  {
-    std::array<float, 18> anc;
-    for (int i = 0; i < 18; ++i) anc[i] = anchors_host[i];
-    std::array<float, 4> sc4 = {scales[0], scales[1], scales[2], scales[3]};
-    std::array<const float*, 3> lg = {logits[0], logits[1], logits[2]}, lb = {labels[0], labels[1], labels[2]};
-    std::array<void*, 3> dl = {dlogits[0], dlogits[1], dlogits[2]};
-    DY_RECORD_OR_RUN([=](void* s) {
-      return disyolo_yolo_loss(lg.data(), lb.data(), true_boxes, max_boxes, B, S, num_class, anc.data(), ignore_thresh,
-                               sc4.data(), dl.data(), losses, workspace, workspace_bytes, s);
-    });
-  }
+// the launch both entry points share: ld = 0 is the 32-channel kernel of disyolo_yolo_loss, ld > 0 the wide one
+static int yolo_loss_launch(const float* const logits[3], const float* const labels[3], const float* true_boxes,
+                            int max_boxes, int B, int S, int num_class, int ld, const float* anchors_host,
+                            float ignore_thresh, const float scales[4], void* const dlogits[3], float* losses,
+                            void* workspace, void* stream) {
   hipStream_t st = (hipStream_t)stream;
   const int g1 = S / 32;
   const int gs[3] = {4 * g1, 2 * g1, g1};
@@ -486,12 +626,74 @@ extern "C" int disyolo_yolo_loss(const float* const logits[3], const float* cons
     nblk[s] = P.gx[s] * B;
     part += (size_t)nblk[s] * 5;
   }
-  hipLaunchKernelGGL(yolo_loss_kernel, dim3(P.gx[0] + P.gx[1] + P.gx[2], B), dim3(256), 0, st, P);
+  if (ld)
+    hipLaunchKernelGGL(yolo_loss_wide_kernel, dim3(P.gx[0] + P.gx[1] + P.gx[2], B), dim3(256), 0, st, P, ld);
+  else
+    hipLaunchKernelGGL(yolo_loss_kernel, dim3(P.gx[0] + P.gx[1] + P.gx[2], B), dim3(256), 0, st, P);
   DY_CHECK_LAUNCH();
   hipLaunchKernelGGL(yolo_loss_final_kernel, dim3(1), dim3(320), 0, st, (const float*)workspace,
                      nblk[0] + nblk[1] + nblk[2], 1.f / (float)B, losses);
   DY_CHECK_LAUNCH();
   return DISYOLO_OK;
+}
+
+extern "C" int disyolo_yolo_loss(const float* const logits[3], const float* const labels[3], const float* true_boxes,
+                                 int max_boxes, int B, int S, int num_class, const float* anchors_host,
+                                 float ignore_thresh, const float scales[4], void* const dlogits[3], float* losses,
+                                 void* workspace, size_t workspace_bytes, void* stream) {
+  DY_REQUIRE(logits && labels && true_boxes && anchors_host && scales && dlogits && losses, "yolo_loss: null pointer");
+  DY_REQUIRE(B > 0 && S > 0 && S % 32 == 0 && num_class > 0 && 3 * (5 + num_class) <= DL_LD && num_class <= 11,
+             "yolo_loss: bad sizes");
+  DY_REQUIRE(max_boxes > 0 && max_boxes <= 64, "yolo_loss: max_boxes must be in 1..64");
+  if (!workspace || workspace_bytes < disyolo_yolo_loss_workspace(B, S, num_class)) {
+    disyolo_set_error("yolo_loss: workspace too small");
+    return DISYOLO_E_WORKSPACE;
+  }
+  {
+    std::array<float, 18> anc;
+    for (int i = 0; i < 18; ++i) anc[i] = anchors_host[i];
+    std::array<float, 4> sc4 = {scales[0], scales[1], scales[2], scales[3]};
+    std::array<const float*, 3> lg = {logits[0], logits[1], logits[2]}, lb = {labels[0], labels[1], labels[2]};
+    std::array<void*, 3> dl = {dlogits[0], dlogits[1], dlogits[2]};
+    DY_RECORD_OR_RUN([=](void* s) {
+      return disyolo_yolo_loss(lg.data(), lb.data(), true_boxes, max_boxes, B, S, num_class, anc.data(), ignore_thresh,
+                               sc4.data(), dl.data(), losses, workspace, workspace_bytes, s);
+    });
+  }
+  return yolo_loss_launch(logits, labels, true_boxes, max_boxes, B, S, num_class, 0, anchors_host, ignore_thresh, scales,
+                          dlogits, losses, workspace, stream);
+}
+
+extern "C" int disyolo_yolo_loss_wide(const float* const logits[3], const float* const labels[3], const float* true_boxes,
+                                      int max_boxes, int B, int S, int num_class, int dlogits_ld,
+                                      const float* anchors_host, float ignore_thresh, const float scales[4],
+                                      void* const dlogits[3], float* losses, void* workspace, size_t workspace_bytes,
+                                      void* stream) {
+  DY_REQUIRE(logits && labels && true_boxes && anchors_host && scales && dlogits && losses,
+             "yolo_loss_wide: null pointer");
+  DY_REQUIRE(B > 0 && S > 0 && S % 32 == 0 && num_class >= 1 && num_class <= WL_MAXD - 5,
+             "yolo_loss_wide: bad sizes (num_class must be in 1..80, got %d)", num_class);
+  DY_REQUIRE(dlogits_ld % 32 == 0 && dlogits_ld >= 3 * (5 + num_class) && dlogits_ld <= 256,
+             "yolo_loss_wide: bad sizes (dlogits_ld must be a multiple of 32 in [3 (5 + num_class), 256], got %d)",
+             dlogits_ld);
+  DY_REQUIRE(max_boxes > 0 && max_boxes <= 64, "yolo_loss_wide: max_boxes must be in 1..64");
+  if (!workspace || workspace_bytes < disyolo_yolo_loss_workspace(B, S, num_class)) {
+    disyolo_set_error("yolo_loss_wide: workspace too small");
+    return DISYOLO_E_WORKSPACE;
+  }
+  {
+    std::array<float, 18> anc;
+    for (int i = 0; i < 18; ++i) anc[i] = anchors_host[i];
+    std::array<float, 4> sc4 = {scales[0], scales[1], scales[2], scales[3]};
+    std::array<const float*, 3> lg = {logits[0], logits[1], logits[2]}, lb = {labels[0], labels[1], labels[2]};
+    std::array<void*, 3> dl = {dlogits[0], dlogits[1], dlogits[2]};
+    DY_RECORD_OR_RUN([=](void* s) {
+      return disyolo_yolo_loss_wide(lg.data(), lb.data(), true_boxes, max_boxes, B, S, num_class, dlogits_ld, anc.data(),
+                                    ignore_thresh, sc4.data(), dl.data(), losses, workspace, workspace_bytes, s);
+    });
+  }
+  return yolo_loss_launch(logits, labels, true_boxes, max_boxes, B, S, num_class, dlogits_ld, anchors_host, ignore_thresh,
+                          scales, dlogits, losses, workspace, stream);
 }
 
 extern "C" int disyolo_shuffle_perm(int32_t* perm_det, int n_det, int32_t* perm_gt, int n_gt, int B, uint32_t seed,

@@ -53,10 +53,13 @@ class MAP(object):
       index:     list of image ids in evaluation order."""
 
     def __init__(self, recs_mask: Dict[str, List[Dict]], sizes: Dict[str, Sequence[int]], index: Sequence[str],
-                 merged: Optional[Dict[str, np.ndarray]] = None, net_size: int = cfg.TEST_SIZE):
-        self.num_class = len(cfg.CLASSES)
+                 merged: Optional[Dict[str, np.ndarray]] = None, net_size: int = cfg.TEST_SIZE,
+                 classes: Optional[Sequence[str]] = None):
+        from .net import check_classes
+        self.classes = check_classes(cfg.CLASSES if classes is None else classes)
+        self.num_class = len(self.classes)
         self.classid = list(range(self.num_class))
-        self.class_to_ind = dict(zip(cfg.CLASSES, range(self.num_class)))
+        self.class_to_ind = dict(zip(self.classes, range(self.num_class)))
         self.recs_mask, self.sizes, self.index, self.merged = recs_mask, sizes, list(index), merged
         self.net_size = net_size
         self.groundtruth = [recs_mask, merged, sizes, self.index]
@@ -154,6 +157,18 @@ class MAP(object):
             self._gt_cache[key] = hit
         return hit
 
+    def _add_confusion(self, true_map: torch.Tensor, merged: torch.Tensor, conf: torch.Tensor) -> None:
+        """the confusion counts of one image into ``conf``: int64 [16] for 3 classes, [(C + 1)^2] for any other list"""
+        if conf.numel() != (self.num_class + 1) ** 2:
+            raise ValueError("conf holds %d counts; a list of %d classes needs %d" %
+                             (conf.numel(), self.num_class, (self.num_class + 1) ** 2))
+        if tuple(true_map.shape) != tuple(merged.shape):
+            raise ValueError("class maps differ in shape: %s vs %s" % (tuple(true_map.shape), tuple(merged.shape)))
+        if self.num_class == 3:
+            L.confusion16(true_map, merged, conf)
+        else:
+            L.confusion_n(true_map, merged.contiguous(), conf, self.num_class + 1)
+
     def collect_batch(self, imageids: Sequence[str], detections: torch.Tensor, keep: torch.Tensor, masks: torch.Tensor,
                       detfile: Dict[str, List[Dict]], true_maps: Optional[Sequence] = None,
                       conf: Optional[torch.Tensor] = None) -> List[torch.Tensor]:
@@ -185,11 +200,13 @@ class MAP(object):
                 else:
                     merged = torch.zeros(*self.sizes[imageid], dtype=torch.uint8, device=dev)
                 if true_maps is not None and conf is not None:
-                    L.confusion16(self._true_map(imageid, true_maps[b], dev), merged, conf)
+                    self._add_confusion(self._true_map(imageid, true_maps[b], dev), merged, conf)
                 out.append(merged)
             return out
         size = int(masks.shape[-1])
         masks = masks.contiguous()
+        # the paste's own confusion counts are the 4x4 table of 3 classes; any other class list counts after the launch
+        fused_conf = self.num_class == 3
         host = torch.cat([detections.reshape(B, -1), keep.reshape(B, -1).to(torch.float32)], 1).cpu().numpy()     # the one fetch
         det = host[:nb, :max_det * 6].reshape(nb, max_det, 6)
         kp = host[:nb, max_det * 6:] != 0
@@ -233,14 +250,18 @@ class MAP(object):
                 if tuple(tm.shape) != (image_h, image_w):
                     raise ValueError("class maps differ in shape: %s vs %s" % (tuple(tm.shape), (image_h, image_w)))
                 tms.append(tm)                       # (kept alive until the launch has been issued on this stream)
-                j["true_map"] = tm.data_ptr()
+                if fused_conf:
+                    j["true_map"] = tm.data_ptr()
             j["counts"] = counts.data_ptr() + cnt_off[b] * 4
             j["n"], j["ng"] = max_det, 0 if gt is None else int(gt.shape[0])
             j["image_h"], j["image_w"] = image_h, image_w
         L.paste_job_plan(jobs)
         hbuf[:jobs.nbytes] = jobs.view(np.uint8)
         dbuf.copy_(torch.from_numpy(hbuf))                                                       # the one upload
-        L.mask_paste_iou_batch(jobs, dbuf, size, conf if tms else None)
+        L.mask_paste_iou_batch(jobs, dbuf, size, conf if (tms and fused_conf) else None)
+        if tms and not fused_conf:
+            for tm, merged in zip(tms, out):
+                self._add_confusion(tm, merged, conf)
         cnt = counts.cpu().numpy()                                                               # the one fetch of the counts
         for b, imageid in enumerate(imageids):
             ok, per_class = oks[b], gts[b][2]
@@ -282,7 +303,8 @@ def evaluate(net, images: Dict[str, np.ndarray], eval_map: MAP, det_thresh: floa
     letter-boxed into one frame, run as one batch and collected by ``MAP.collect_batch`` (a short last batch runs with the
     stale frames of the one before left in place).  Returns
     (thresh_out, mask_acc, timing) = ([{'thresh', 'AP', 'mAP'}], [bg, crack, spall, rebar, mIoU] or None,
-    {'prediction_s', 'crop_assemble_s', 'per_image_s'})."""
+    {'prediction_s', 'crop_assemble_s', 'per_image_s'}).  The class list is ``eval_map``'s (``MAP(classes=...)``, the net's must
+    have as many): one AP per class, and mask_acc = background, one IoU per class, their mean."""
     if weights_file is not None:
         from .checkpoint import restore_net
         restore_net(net, weights_file)                       # saver.restore (:184-185)
@@ -292,7 +314,9 @@ def evaluate(net, images: Dict[str, np.ndarray], eval_map: MAP, det_thresh: floa
         # every image is then one replay (YOLONet.evaluation uses the recording when the threshold matches)
         net.build_infer_program(float(det_thresh), graph=True)
     detfile = {str(c): [] for c in eval_map.classid}
-    seg = SegmentationAccuracy(net.device) if eval_map.merged is not None else None
+    if getattr(net, "num_class", eval_map.num_class) != eval_map.num_class:
+        raise ValueError("evaluate: the net has %d classes, the MAP %d" % (net.num_class, eval_map.num_class))
+    seg = SegmentationAccuracy(net.device, eval_map.num_class) if eval_map.merged is not None else None
     t_pred = t_crop = 0.0
     if B > 1:
         t_pred, t_crop = _evaluate_batches(net, images, eval_map, det_thresh, detfile, seg)

@@ -134,6 +134,8 @@ _SIGS = {
     "disyolo_yolo_loss_workspace": (C.c_size_t, [C.c_int] * 3),
     "disyolo_yolo_loss": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p, C.c_float] +
                           [C.c_void_p] * 4 + [C.c_size_t, C.c_void_p]),
+    "disyolo_yolo_loss_wide": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p, C.c_float] +
+                               [C.c_void_p] * 4 + [C.c_size_t, C.c_void_p]),
     "disyolo_shuffle_perm": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p]),
     "disyolo_mask_rois": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p] + [C.c_int] * 4 +
                           [C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -149,6 +151,7 @@ _SIGS = {
                                      C.c_void_p, C.c_void_p]),
     "disyolo_letterbox": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "disyolo_confusion16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "disyolo_confusion_n": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p]),
     "disyolo_paste_job_size": (C.c_size_t, []),
     "disyolo_paste_job_plan": (C.c_int, [C.c_void_p, C.c_int]),
     "disyolo_mask_paste_iou_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
@@ -1016,6 +1019,17 @@ def confusion16(true_map, pred_map, conf) -> None:
     _check(load().disyolo_confusion16(_p(true_map), _p(pred_map), true_map.numel(), _p(conf), _stream()), "confusion16")
 
 
+def confusion_n(true_map, pred_map, conf, nlabel: int) -> None:
+    """adds the nlabel x nlabel confusion counts of two uint8 CUDA class maps to conf (int64 [nlabel * nlabel], CUDA)"""
+    _need(true_map, torch.uint8, "true_map")
+    _need(pred_map, torch.uint8, "pred_map")
+    _need(conf, torch.int64, "conf")
+    if true_map.numel() != pred_map.numel() or conf.numel() != nlabel * nlabel:
+        raise DisyoloError("confusion_n: shape mismatch")
+    _check(load().disyolo_confusion_n(_p(true_map), _p(pred_map), true_map.numel(), nlabel, _p(conf), _stream()),
+           "confusion_n")
+
+
 def upsample2x_bwd(src, dst, B, Hs, Ws, src_C, c_off, C_, accumulate=False) -> None:
     _check(load().disyolo_upsample2x_bwd(_p(src), _p(dst), B, Hs, Ws, src_C, c_off, C_, int(accumulate), _stream()),
            "upsample2x_bwd")
@@ -1048,6 +1062,20 @@ def yolo_loss(logits, labels, true_boxes, max_boxes, B, S, num_class, anchors_ho
     sc = (C.c_float * 4)(*[float(v) for v in scales])
     _check(load().disyolo_yolo_loss(lg, lb, _p(true_boxes), max_boxes, B, S, num_class, anc, ignore_thresh, sc, dl,
                                     _p(losses), _p(buf), buf.numel(), _stream()), "yolo_loss")
+
+
+def yolo_loss_wide(logits, labels, true_boxes, max_boxes, B, S, num_class, dlogits_ld, anchors_host, ignore_thresh, scales,
+                   dlogits, losses, ws: Workspace) -> None:
+    """yolo_loss for rows past 32 channels: dlogits bf16 [B, g, g, dlogits_ld] per scale"""
+    need = load().disyolo_yolo_loss_workspace(B, S, num_class)
+    buf = ws.get(need)
+    anc = (C.c_float * 18)(*[float(v) for v in anchors_host])
+    lg = (C.c_void_p * 3)(*[_p(t) for t in logits])
+    lb = (C.c_void_p * 3)(*[_p(t) for t in labels])
+    dl = (C.c_void_p * 3)(*[_p(t) for t in dlogits])
+    sc = (C.c_float * 4)(*[float(v) for v in scales])
+    _check(load().disyolo_yolo_loss_wide(lg, lb, _p(true_boxes), max_boxes, B, S, num_class, dlogits_ld, anc, ignore_thresh,
+                                         sc, dl, _p(losses), _p(buf), buf.numel(), _stream()), "yolo_loss_wide")
 
 
 def shuffle_perm(perm_det, perm_gt, B, seed, step_counter) -> None:

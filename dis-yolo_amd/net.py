@@ -142,14 +142,33 @@ def var_name(i: int, leaf: str) -> str:
     return "yolo/convolutional%d/%s" % (i, leaf)
 
 
+MAX_CLASSES = 80     # what the loss, filter and confusion kernels cover (the reference's starting weights: COCO, 80)
+
+
+def check_classes(classes) -> List[str]:
+    """a class list as the net, the loader and the evaluator take it: 1 to 80 distinct non-empty strings"""
+    if isinstance(classes, (str, bytes)):
+        raise ValueError("classes must be a sequence of 1 to %d names, not one string" % MAX_CLASSES)
+    names = list(classes)
+    if not 1 <= len(names) <= MAX_CLASSES:
+        raise ValueError("classes must hold 1 to %d names (got %d)" % (MAX_CLASSES, len(names)))
+    if any(not isinstance(n, str) or not n for n in names):
+        raise ValueError("classes must be non-empty strings (1 to %d of them)" % MAX_CLASSES)
+    if len(set(names)) != len(names):
+        raise ValueError("classes must be distinct (1 to %d names)" % MAX_CLASSES)
+    return names
+
+
 class YOLONet(object):
     def __init__(self, training: bool = False, device=None, image_size: Optional[int] = None,
                  batch_size: Optional[int] = None, stage: int = 1, lock: Optional[Dict[int, bool]] = None,
                  seed: int = 0, xavier_locked: bool = True, plan_only: bool = False, dtype: str = "bf16",
-                 backbone_pair: bool = False, k_map: Optional[int] = None, mask_stride: Optional[int] = None):
+                 backbone_pair: bool = False, k_map: Optional[int] = None, mask_stride: Optional[int] = None,
+                 classes: Optional[Sequence[str]] = None):
         # 1. parameters (yolo/yolo3_net_pos.py:15-38)
         self.batchsize = int(batch_size if batch_size is not None else cfg.BATCH_SIZE)
-        self.classes = cfg.CLASSES
+        # the class list (CLASSES of yolo/config.py): cfg.CLASSES unless given; it sizes the three heads
+        self.classes = check_classes(cfg.CLASSES if classes is None else classes)
         self.num_class = len(self.classes)
         self.anchors = np.asarray(cfg.ANCHORS, dtype=np.float32)
         self.num_anchor = 3
@@ -1354,10 +1373,15 @@ class YOLONet(object):
         self._mask_mark = L.lane_mark(1) if side else -1
         if side:
             L.set_lane(0)
-        L.yolo_loss([h.act for h in heads], self.labels, self.true_boxes, cfg.MAX_BOX_PER_IMAGE, self.B, self.S,
-                    self.num_class, self.anchors.reshape(-1), cfg.IGNORE_THRESH,
-                    (self.object_scale, self.noobject_scale, self.class_scale, self.coord_scale),
-                    [h.dx for h in heads], self.losses, self.ws)
+        scales = (self.object_scale, self.noobject_scale, self.class_scale, self.coord_scale)
+        if self.output_depth > L.GRAD_LD:      # rows past 32 channels (more than 5 classes): the heads' own pitch
+            L.yolo_loss_wide([h.act for h in heads], self.labels, self.true_boxes, cfg.MAX_BOX_PER_IMAGE, self.B, self.S,
+                             self.num_class, heads[0].cout_pad, self.anchors.reshape(-1), cfg.IGNORE_THRESH, scales,
+                             [h.dx for h in heads], self.losses, self.ws)
+        else:
+            L.yolo_loss([h.act for h in heads], self.labels, self.true_boxes, cfg.MAX_BOX_PER_IMAGE, self.B, self.S,
+                        self.num_class, self.anchors.reshape(-1), cfg.IGNORE_THRESH, scales,
+                        [h.dx for h in heads], self.losses, self.ws)
         self._mask_loss_pending = side
 
     def _accumulate_into(self, tgt: Layer, desc_kw: dict, dx: torch.Tensor, cin_eff: int, k: int, in_div: int,

@@ -89,18 +89,27 @@ class SegmentationAccuracy:
     """the mIoU block of ``evaluate`` (calculate_test_map.py:303-346): accumulate the pixel confusion
     counts of (ground-truth class map, merged detection map) pairs on the GPU, image by image."""
 
-    def __init__(self, device):
-        self.conf = torch.zeros(16, dtype=torch.int64, device=device)
+    def __init__(self, device, num_class: int = 3):
+        # background + num_class labels; 3 classes keep the 4x4 table the batched paste fills in its own pass
+        if not 1 <= int(num_class) <= 80:
+            raise ValueError("num_class must be in 1..80 (got %r)" % (num_class,))
+        self.num_class = int(num_class)
+        self.nlabel = self.num_class + 1
+        self.conf = torch.zeros(self.nlabel * self.nlabel, dtype=torch.int64, device=device)
 
     def add(self, true_map, pred_map: torch.Tensor) -> None:
         t = torch.as_tensor(true_map).to(self.conf.device, torch.uint8).contiguous()
         p = pred_map.to(self.conf.device, torch.uint8).contiguous()
         if t.shape != p.shape:
             raise ValueError("class maps differ in shape: %s vs %s" % (tuple(t.shape), tuple(p.shape)))
-        L.confusion16(t, p, self.conf)
+        if self.num_class == 3:
+            L.confusion16(t, p, self.conf)
+        else:
+            L.confusion_n(t, p, self.conf, self.nlabel)
 
     def result(self) -> List[float]:
-        """[bg_iou, crack_iou, spall_iou, rebar_iou, miou]"""
-        c = self.conf.cpu().numpy().reshape(4, 4).astype(np.float64)
-        ious = [c[k, k] / (c[k, :].sum() + c[:, k].sum() - c[k, k]) for k in range(4)]
+        """[bg_iou, crack_iou, spall_iou, rebar_iou, miou]; with another class list: background, one IoU per class, the mean"""
+        n = self.nlabel
+        c = self.conf.cpu().numpy().reshape(n, n).astype(np.float64)
+        ious = [c[k, k] / (c[k, :].sum() + c[:, k].sum() - c[k, k]) for k in range(n)]
         return ious + [float(np.mean(ious))]

@@ -86,6 +86,12 @@ class Solver(object):
         if lr_schedule not in ("faithful", "intended"):
             raise ValueError("lr_schedule must be 'faithful' or 'intended'")
         self.net, self.data, self.eval, self.val_data = net, data, evalu, val_data
+        # one class list for the whole run: the loader's target grids and the MAP's tables are sized by theirs
+        for what, obj in (("data", data), ("evalu", evalu)):
+            n = getattr(obj, "num_class", None)
+            if n is not None and n != net.num_class:
+                raise ValueError("Solver: the net has %d classes but %s has %d; build all three with the same class list"
+                                 % (net.num_class, what, n))
         self.start_iter = 1
         self.max_iter = cfg.MAX_ITER if max_iter is None else max_iter
         self.summary_iter = cfg.SUMMARY_ITER if summary_iter is None else summary_iter

@@ -67,15 +67,18 @@ class defect_train(object):
 
     def __init__(self, labels: List[Dict], batch_size: Optional[int] = None, image_size: Optional[int] = None, device=None,
                  rng: Optional[np.random.RandomState] = None, flipped: Optional[bool] = None,
-                 blur_noise_light: Optional[bool] = None, cache_bytes: int = 16 << 30):
+                 blur_noise_light: Optional[bool] = None, cache_bytes: int = 16 << 30,
+                 classes: Optional[Sequence[str]] = None):
         self.batch_size = cfg.BATCH_SIZE if batch_size is None else batch_size
         self.image_size = cfg.IMAGE_SIZE if image_size is None else image_size
         self.base_grid = self.image_size // 32
         self.max_box_per_image = cfg.MAX_BOX_PER_IMAGE
         self.anchors = cfg.ANCHORS
         self.num_anchor = 3
-        self.num_class = len(cfg.CLASSES)
-        self.class_to_ind = dict(zip(cfg.CLASSES, range(self.num_class)))
+        from .net import check_classes
+        self.classes = check_classes(cfg.CLASSES if classes is None else classes)     # cfg.CLASSES unless given
+        self.num_class = len(self.classes)
+        self.class_to_ind = dict(zip(self.classes, range(self.num_class)))
         self.flipped = cfg.FLIPPED if flipped is None else flipped
         self.blur_noise_light = cfg.BLUR_NOISE_LIGHT if blur_noise_light is None else blur_noise_light
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)

@@ -3,6 +3,7 @@ Solver (recorded pipelined step: the next batch's backbone and its data loading 
 inference net -> detections + instance masks for one image.
 
     python examples/train_synthetic.py [--steps 40] [--size 192] [--batch 4] [--out /tmp/disyolo_example] [--lock 62-64]
+                                       [--classes crack,spall,rebar,stain,joint,void]
 
 It mirrors what the reference's ``train_yolo3_mask.py:237-248`` (train) and ``calculate_test_map.py`` (test) do
 with a real dataset; swap ``synthetic_labels`` for ``disyolo_amd.pre_process.load_verify_contour(path, 'train')``
@@ -23,9 +24,10 @@ from disyolo_amd.solver import Solver  # noqa: E402
 from disyolo_amd.train_data import defect_train  # noqa: E402
 
 
-def synthetic_labels(rng, n):
+def synthetic_labels(rng, n, classes=None):
     """n records in the layout of the reference's ground-truth cache: an RGB image, one class name and one list of
     polygons ('out' = outline, 'in' = hole) per instance"""
+    classes = cfg.CLASSES if classes is None else classes
     out = []
     for _ in range(n):
         h, w = rng.randint(200, 320), rng.randint(200, 320)
@@ -37,7 +39,7 @@ def synthetic_labels(rng, n):
             t = np.sort(rng.uniform(0, 2 * np.pi, rng.randint(6, 10)))
             polys.append([{"type": "out", "all_points_x": np.clip(cx + rx * np.cos(t), 0, w - 1).astype(int).tolist(),
                            "all_points_y": np.clip(cy + ry * np.sin(t), 0, h - 1).astype(int).tolist()}])
-            names.append(cfg.CLASSES[rng.randint(0, len(cfg.CLASSES))])
+            names.append(classes[rng.randint(0, len(classes))])
         out.append({"image": image, "class_names": names, "polygons": polys})
     return out
 
@@ -65,15 +67,19 @@ def main():
     ap.add_argument("--mask-stride", type=int, default=cfg.MASK_STRIDE, choices=(4, 2, 1),
                     help="mask subnet: score maps at size/4, size/2 (cfg.MASK_STRIDE) or size (m = 1/4, 1/2, 1)")
     ap.add_argument("--lock", default="", help="layer ranges to lock on top of stage 1, e.g. 5-9,62-64 (\"!40-52\" unlocks)")
+    ap.add_argument("--classes", default=",".join(cfg.CLASSES),
+                    help="comma-separated class list, 1 to 80 names (cfg.CLASSES): it sizes the heads, the targets and the metric")
     args = ap.parse_args()
+    classes = [c.strip() for c in args.classes.split(",")]
     dev = torch.device("cuda:0")
     rng = np.random.RandomState(0)
-    labels = synthetic_labels(rng, 16)
+    labels = synthetic_labels(rng, 16, classes)
 
     # --- train: stage 1 (conv1-52 locked), batches built on the GPU from the polygon records
-    data = defect_train(labels, batch_size=args.batch, image_size=args.size, device=dev, rng=np.random.RandomState(1))
+    data = defect_train(labels, batch_size=args.batch, image_size=args.size, device=dev, rng=np.random.RandomState(1),
+                        classes=classes)
     net = YOLONet(training=True, device=dev, image_size=args.size, batch_size=args.batch, stage=1, seed=0, k_map=args.k_map,
-                  mask_stride=args.mask_stride, lock=parse_lock(args.lock))
+                  mask_stride=args.mask_stride, lock=parse_lock(args.lock), classes=classes)
     if net.pass_through_layers():
         print("locked layers the gradient crosses:", net.pass_through_layers())
     solver = Solver(net, data, output_dir=args.out, max_iter=args.steps, summary_iter=max(1, args.steps // 4),
@@ -86,7 +92,7 @@ def main():
     prefix = checkpoint.latest_checkpoint(os.path.join(args.out, "checkpoint"))
     print("restoring", prefix)
     inf = YOLONet(training=False, device=dev, image_size=args.size, batch_size=1, stage=1, seed=123, k_map=args.k_map,
-                  mask_stride=args.mask_stride)
+                  mask_stride=args.mask_stride, classes=classes)
     checkpoint.restore_net(inf, prefix)
     rec = labels[0]
     from disyolo_amd.evaluate import image_read

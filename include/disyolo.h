@@ -382,7 +382,11 @@ int disyolo_colsum(const void* x, float* out, int64_t rows, int C, int out_C, vo
 /* logits: three f32 tensors [B,g,g,3,5+C] in the reference's scale order (S/8, S/16, S/32
  * grids).  anchors: host pointer to 18 floats (w,h)x9 in pixels.  Writes detections f32
  * [B,max_det,6] rows (y1,x1,y2,x2,classid,score), score-descending, zero padded, and
- * det_count int32 [B].  workspace: disyolo_detect_workspace bytes. */
+ * det_count int32 [B].  workspace: disyolo_detect_workspace bytes; it starts with the decode results
+ * boxes float4 [B][NC], scores f32 [B][NC], classes i32 [B][NC] (NC candidates per image).
+ * 1 <= num_class <= 80, max_det <= 64.  Up to 16 classes a block per (image, class) compacts its own
+ * candidate list; above 16 one pass per image buckets the candidates by class and the greedy NMS runs
+ * per class segment, so work and workspace do not grow with B*num_class*NC. */
 size_t disyolo_detect_workspace(int B, int S, int num_class);
 int disyolo_detect(const float* logits3, const float* logits2, const float* logits1, int B, int S,
                    int num_class, const float* anchors_host, const float* clip_window,
@@ -400,6 +404,16 @@ int disyolo_yolo_loss(const float* const logits[3], const float* const labels[3]
                       const float* anchors_host, float ignore_thresh, const float scales[4],
                       void* const dlogits[3], float* losses, void* workspace,
                       size_t workspace_bytes, void* stream);
+/* the same loss for class lists whose rows do not fit 32 channels: 1 <= num_class <= 80, dlogits bf16
+ * [B,g,g,dlogits_ld] per scale with dlogits_ld a multiple of 32, 3*(5+num_class) <= dlogits_ld <= 256 (the
+ * head conv's padded channel count); channels [3*(5+num_class), dlogits_ld) are written as zeros.  Same
+ * loss terms, losses[8] and workspace (disyolo_yolo_loss_workspace) as disyolo_yolo_loss; one launch for the
+ * three scales plus the fixed-order final sum, the same bits in every run. */
+int disyolo_yolo_loss_wide(const float* const logits[3], const float* const labels[3],
+                           const float* true_boxes, int max_boxes, int B, int S, int num_class,
+                           int dlogits_ld, const float* anchors_host, float ignore_thresh,
+                           const float scales[4], void* const dlogits[3], float* losses,
+                           void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- position-sensitive RoI assembly (yolo/yolo3_net_pos.py:750-938) ---- */
 /* RoI selection for the mask loss (:757-796): detections [B,max_det,6], true_boxes [B,G,5],
@@ -498,6 +512,11 @@ int disyolo_letterbox(const uint8_t* rgb, int image_h, int image_w, float* out, 
  * and forms IoU_c = n_cc / (row_c + column_c - n_cc) at the end. */
 int disyolo_confusion16(const uint8_t* true_map, const uint8_t* pred_map, int64_t n, int64_t* conf,
                         void* stream);
+/* the same counts for nlabel labels (0 = background, 1..nlabel-1 = classes; 2 <= nlabel <= 81): adds to
+ * conf int64 [nlabel*nlabel], conf[true*nlabel + pred]; values >= nlabel are ignored.  Integer adds only;
+ * nlabel = 4 gives disyolo_confusion16's numbers. */
+int disyolo_confusion_n(const uint8_t* true_map, const uint8_t* pred_map, int64_t n, int nlabel,
+                        int64_t* conf, void* stream);
 
 /* ---- optimizer (tf.train.AdamOptimizer.minimize, train_yolo3_mask.py:55) ---- */
 /* TF-form Adam on a flat f32 arena; elements [0, n_decay) also receive the gradient of the
