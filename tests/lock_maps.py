@@ -15,11 +15,20 @@ MAPS: Dict[str, Tuple[int, List[int]]] = {
     "stage1_hole": (2, list(range(1, 53)) + [62, 63, 64]),
     "m1_hole": (1, list(range(1, 53)) + [83, 84]),
 }
+# the same holes in the m = 1/4 and m = 1 nets: the rows of tests/option_matrix.py use them (the per-map tests above run MAPS)
+STRIDE_MAPS: Dict[str, Tuple[int, List[int]]] = {
+    "frozen_heads_m4": (4, list(range(53, 76))),
+    "stage1_hole_m4": (4, list(range(1, 53)) + [62, 63, 64]),
+    "odd_m4": (4, list(range(1, SCORE_LAYER[4] + 1, 2))),
+    "frozen_heads_m1": (1, list(range(53, 76))),
+    "stage1_hole_m1": (1, list(range(1, 53)) + [62, 63, 64]),
+    "odd_m1": (1, list(range(1, SCORE_LAYER[1] + 1, 2))),
+}
 
 
 def lock_of(name: str) -> Tuple[int, Dict[int, bool]]:
     """(mask_stride, full lock map) of a named map"""
-    m, locked = MAPS[name]
+    m, locked = MAPS[name] if name in MAPS else STRIDE_MAPS[name]
     return m, {i: (i in locked) for i in range(1, SCORE_LAYER[m] + 1)}
 
 

@@ -434,8 +434,14 @@ def class_ground_truth(shapes, seed, C):
 def test_evaluate_with_a_6_class_map(dev):
     """two synthetic images, a net and a MAP of 6 classes: 6 AP rows and background + 6 IoUs + their mean, both equal to the
     host computation (voc_eval on the pasted masks, numpy confusion counts)"""
+    check_evaluate_with_a_6_class_map(dev)
+
+
+def check_evaluate_with_a_6_class_map(dev, **net_options):
+    """the body of the test above; ``net_options`` are further YOLONet arguments (tests/test_gpu_option_matrix.py runs it with
+    another k_map and mask_stride)"""
     S_, B, thr, C = 96, 2, 0.05, 6
-    net = YOLONet(training=False, device=dev, image_size=S_, batch_size=B, stage=1, seed=0, classes=names(C))
+    net = YOLONet(training=False, device=dev, image_size=S_, batch_size=B, stage=1, seed=0, classes=names(C), **net_options)
     randomize_heads(net, 7)
     images, recs, sizes, merged, index = class_ground_truth([(70, 120), (96, 96)], 33, C)
     emap = E.MAP(recs, sizes, index, merged, net_size=S_, classes=names(C))

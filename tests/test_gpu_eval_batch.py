@@ -132,7 +132,7 @@ def randomize_heads(net, seed, gain=6.0, bias_std=0.5):
     (the initial heads give near-zero logits: one class, tied scores)"""
     g = torch.Generator().manual_seed(seed)
     with torch.no_grad():
-        for i in (59, 67, 75, 82):
+        for i in (59, 67, 75, net.score_layer):
             net.params["yolo/convolutional%d/weights" % i].mul_(gain)
             b = net.params["yolo/convolutional%d/biases" % i]
             b.copy_((torch.randn(b.shape, generator=g) * bias_std).to(b.device))

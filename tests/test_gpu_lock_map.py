@@ -20,6 +20,7 @@ from disyolo_amd import config as cfg
 from disyolo_amd import lib as L
 from disyolo_amd.net import YOLONet
 from lock_maps import MAPS, lock_of, pass_through
+from net_setup import perturb_variables
 
 pytestmark = pytest.mark.gpu
 
@@ -149,24 +150,7 @@ def make_net(dev, name, B=2, S=64, seed=1, lock=None, m=None, perturb="scale", *
     if name is not None:
         m, lock = lock_of(name)
     net = YOLONet(training=True, device=dev, image_size=S, batch_size=B, lock=lock, mask_stride=m, seed=seed, **kw)
-    g = torch.Generator().manual_seed(7919 + seed)
-    with torch.no_grad():
-        for i in (59, 67, 75, net.score_layer):
-            net.params["yolo/convolutional%d/weights" % i].mul_(6.0)
-            b = net.params["yolo/convolutional%d/biases" % i]
-            b.copy_((torch.randn(b.shape, generator=g) * 0.5).to(b.device))
-        # (gamma 1, beta 0, moving mean 0, variance 1 fold to scale ~1, shift 0, which any mix-up of the coefficients would
-        # survive): every channel its own scale, an eighth of them negative.  The oracle reads the same variables.
-        for l in net.layers:
-            if l.passthru and l.kind != "lin":
-                rnd = lambda: torch.rand(l.cout, generator=g)
-                gamma = (0.6 + 0.8 * rnd()) * torch.where(rnd() < 0.125, -1.0, 1.0)
-                leaves = [("gamma", gamma), ("moving_variance", 0.5 + rnd())]
-                if perturb == "all":
-                    leaves += [("beta", 0.3 * torch.randn(l.cout, generator=g)), ("moving_mean", 0.2 * torch.randn(l.cout, generator=g))]
-                for leaf, val in leaves:
-                    t = net.params["yolo/convolutional%d/BatchNorm/%s" % (l.idx, leaf)]
-                    t.copy_(val.to(t.device))
+    perturb_variables(net, seed, perturb)
     net.refresh_weights()
     return net
 
