@@ -74,11 +74,12 @@ __device__ __forceinline__ Taps taps(int d, int dn, int sn) {
   return Taps{s, min(s + 1, sn - 1), a};
 }
 
-// destination pixel (y, x) of the S x S training image -> position in the resized image, or outside (pad):
+// destination pixel (y, x) of the SH x SW training image (net_h x net_w) -> position in the resized image, or outside (pad):
 // the resized image (new_w x new_h) is placed with its corner at (dx, dy) (negative = cropped), then flipped
-__device__ __forceinline__ bool locate(int y, int x, int S, int new_w, int new_h, int dx, int dy, int flip, int* ry, int* rx) {
-  if (flip == 2) x = S - 1 - x;     // horizontal flip: image[:, ::-1]
-  if (flip == 3) y = S - 1 - y;     // vertical flip
+__device__ __forceinline__ bool locate(int y, int x, int SH, int SW, int new_w, int new_h, int dx, int dy, int flip, int* ry,
+                                       int* rx) {
+  if (flip == 2) x = SW - 1 - x;    // horizontal flip: image[:, ::-1]
+  if (flip == 3) y = SH - 1 - y;    // vertical flip
   *ry = y - dy;
   *rx = x - dx;
   return *ry >= 0 && *ry < new_h && *rx >= 0 && *rx < new_w;
@@ -86,12 +87,12 @@ __device__ __forceinline__ bool locate(int y, int x, int S, int new_w, int new_h
 
 // uint8 image: OpenCV's 8-bit bilinear path works in fixed point -- coefficients rounded to 11 bits,
 // horizontal pass in int, vertical pass (b0*S0 + b1*S1 + 2^21) >> 22
-__device__ __forceinline__ void place_image_px(const unsigned char* src, int H, int W, unsigned char* dst, int S, int new_w, int new_h,
-                                               int dx, int dy, int flip, int64_t i) {
-  const int y = (int)(i / S), x = (int)(i - (int64_t)y * S);
+__device__ __forceinline__ void place_image_px(const unsigned char* src, int H, int W, unsigned char* dst, int SH, int SW, int new_w,
+                                               int new_h, int dx, int dy, int flip, int64_t i) {
+  const int y = (int)(i / SW), x = (int)(i - (int64_t)y * SW);
   int ry, rx;
   unsigned char v[3] = {127, 127, 127};
-  if (locate(y, x, S, new_w, new_h, dx, dy, flip, &ry, &rx)) {
+  if (locate(y, x, SH, SW, new_w, new_h, dx, dy, flip, &ry, &rx)) {
     const Taps tx = taps(rx, new_w, W), ty = taps(ry, new_h, H);
     const int ax1 = (int)rintf(tx.a * 2048.f), ax0 = 2048 - ax1;
     const int ay1 = (int)rintf(ty.a * 2048.f), ay0 = 2048 - ay1;
@@ -106,20 +107,20 @@ __device__ __forceinline__ void place_image_px(const unsigned char* src, int H, 
 #pragma unroll
   for (int c = 0; c < 3; ++c) dst[i * 3 + c] = v[c];
 }
-__global__ __launch_bounds__(256) void place_image_kernel(const unsigned char* src, int H, int W, unsigned char* dst, int S,
+__global__ __launch_bounds__(256) void place_image_kernel(const unsigned char* src, int H, int W, unsigned char* dst, int SH, int SW,
                                                           int new_w, int new_h, int dx, int dy, int flip) {
-  const int64_t total = (int64_t)S * S;
+  const int64_t total = (int64_t)SH * SW;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x)
-    place_image_px(src, H, W, dst, S, new_w, new_h, dx, dy, flip, i);
+    place_image_px(src, H, W, dst, SH, SW, new_w, new_h, dx, dy, flip, i);
 }
 
 // float mask (0/1 bytes in, treated as float32): float bilinear path, pad 0, np.around (half to even) -> bool
-__device__ __forceinline__ void place_mask_px(const unsigned char* src, int H, int W, unsigned char* dst, int S, int new_w, int new_h,
-                                              int dx, int dy, int flip, int64_t i) {
-  const int y = (int)(i / S), x = (int)(i - (int64_t)y * S);
+__device__ __forceinline__ void place_mask_px(const unsigned char* src, int H, int W, unsigned char* dst, int SH, int SW, int new_w,
+                                              int new_h, int dx, int dy, int flip, int64_t i) {
+  const int y = (int)(i / SW), x = (int)(i - (int64_t)y * SW);
   int ry, rx;
   float v = 0.f;
-  if (locate(y, x, S, new_w, new_h, dx, dy, flip, &ry, &rx)) {
+  if (locate(y, x, SH, SW, new_w, new_h, dx, dy, flip, &ry, &rx)) {
     const Taps tx = taps(rx, new_w, W), ty = taps(ry, new_h, H);
     const float bx = __fsub_rn(1.f, tx.a), by = __fsub_rn(1.f, ty.a);
     const float h0 = __fadd_rn(__fmul_rn((float)src[(size_t)ty.s0 * W + tx.s0], bx), __fmul_rn((float)src[(size_t)ty.s0 * W + tx.s1], tx.a));
@@ -128,32 +129,33 @@ __device__ __forceinline__ void place_mask_px(const unsigned char* src, int H, i
   }
   dst[i] = rintf(v) != 0.f ? 1 : 0;
 }
-__global__ __launch_bounds__(256) void place_mask_kernel(const unsigned char* src, int H, int W, unsigned char* dst, int S,
+__global__ __launch_bounds__(256) void place_mask_kernel(const unsigned char* src, int H, int W, unsigned char* dst, int SH, int SW,
                                                          int new_w, int new_h, int dx, int dy, int flip) {
-  const int64_t total = (int64_t)S * S;
+  const int64_t total = (int64_t)SH * SW;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x)
-    place_mask_px(src, H, W, dst, S, new_w, new_h, dx, dy, flip, i);
+    place_mask_px(src, H, W, dst, SH, SW, new_w, new_h, dx, dy, flip, i);
 }
 
 // a whole batch's placements in ONE launch (round 6: the loader's ~25 per-image / per-instance launches were its GPU time):
 // blockIdx.y = job; the per-pixel arithmetic is the single-job kernels' own
-__global__ __launch_bounds__(256) void place_batch_kernel(const disyolo_place_job* jobs, int S) {
+__global__ __launch_bounds__(256) void place_batch_kernel(const disyolo_place_job* jobs, int SH, int SW) {
   const disyolo_place_job j = jobs[blockIdx.y];
-  const int64_t total = (int64_t)S * S;
+  const int64_t total = (int64_t)SH * SW;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
     if (j.is_mask)
-      place_mask_px(j.src, j.image_h, j.image_w, j.dst, S, j.new_w, j.new_h, j.dx, j.dy, j.flip, i);
+      place_mask_px(j.src, j.image_h, j.image_w, j.dst, SH, SW, j.new_w, j.new_h, j.dx, j.dy, j.flip, i);
     else
-      place_image_px(j.src, j.image_h, j.image_w, j.dst, S, j.new_w, j.new_h, j.dx, j.dy, j.flip, i);
+      place_image_px(j.src, j.image_h, j.image_w, j.dst, SH, SW, j.new_w, j.new_h, j.dx, j.dy, j.flip, i);
   }
 }
 
 // add_salt_pepper_noise (:511-525): im[rows, cols, :] = 1 for the salt coordinates, then 0 for the pepper ones
-__global__ void salt_pepper_kernel(unsigned char* img, int S, const int* rows, const int* cols, int nsalt, int npepper) {
+__global__ void salt_pepper_kernel(unsigned char* img, int SH, int SW, const int* rows, const int* cols, int nsalt, int npepper) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= nsalt + npepper) return;
   const unsigned char v = i < nsalt ? 1 : 0;
-  unsigned char* p = img + ((size_t)rows[i] * S + cols[i]) * 3;
+  if ((unsigned)rows[i] >= (unsigned)SH || (unsigned)cols[i] >= (unsigned)SW) return;   // (a coordinate outside the image)
+  unsigned char* p = img + ((size_t)rows[i] * SW + cols[i]) * 3;
   p[0] = v; p[1] = v; p[2] = v;
 }
 
@@ -204,19 +206,19 @@ __global__ __launch_bounds__(256) void change_light_kernel(unsigned char* img, i
 // "full" = three taps, "right" / "left" = the centre and one neighbour), normalised; pixels outside the image count as
 // 255 (pyblur's LinearMotionBlur: scipy.signal.convolve2d(img, kernel, mode='same', fillvalue=255.0)), result truncated
 // to uint8
-__global__ __launch_bounds__(256) void motion_blur3_kernel(const unsigned char* src, unsigned char* dst, int S, int dyA, int dxA,
-                                                           int use_a, int use_b) {
-  const int64_t total = (int64_t)S * S;
+__global__ __launch_bounds__(256) void motion_blur3_kernel(const unsigned char* src, unsigned char* dst, int SH, int SW, int dyA,
+                                                           int dxA, int use_a, int use_b) {
+  const int64_t total = (int64_t)SH * SW;
   const float wgt = 1.f / (float)(1 + use_a + use_b);
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-    const int y = (int)(i / S), x = (int)(i - (int64_t)y * S);
+    const int y = (int)(i / SW), x = (int)(i - (int64_t)y * SW);
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
       // taps in the (flipped) kernel's row-major order: the "b" end first when it lies above / left of the centre
       float acc = 0.f;
       const int ya = y + dyA, xa = x + dxA, yb = y - dyA, xb = x - dxA;
-      const float va = (ya >= 0 && ya < S && xa >= 0 && xa < S) ? (float)src[((size_t)ya * S + xa) * 3 + c] : 255.f;
-      const float vb = (yb >= 0 && yb < S && xb >= 0 && xb < S) ? (float)src[((size_t)yb * S + xb) * 3 + c] : 255.f;
+      const float va = (ya >= 0 && ya < SH && xa >= 0 && xa < SW) ? (float)src[((size_t)ya * SW + xa) * 3 + c] : 255.f;
+      const float vb = (yb >= 0 && yb < SH && xb >= 0 && xb < SW) ? (float)src[((size_t)yb * SW + xb) * 3 + c] : 255.f;
       if (use_a) acc += va * wgt;
       acc += (float)src[i * 3 + c] * wgt;
       if (use_b) acc += vb * wgt;
@@ -250,53 +252,78 @@ extern "C" int disyolo_polygon_mask(const float* px, const float* py, const int3
 
 extern "C" int disyolo_aug_place(const uint8_t* src, int is_mask, int image_h, int image_w, uint8_t* dst, int size, int new_w,
                                  int new_h, int dx, int dy, int flip, void* stream) {
-  DY_REQUIRE(src && dst && image_h > 0 && image_w > 0 && size > 0 && new_w > 0 && new_h > 0 && flip >= 1 && flip <= 3,
+  return disyolo_aug_place_hw(src, is_mask, image_h, image_w, dst, size, size, new_w, new_h, dx, dy, flip, stream);
+}
+
+extern "C" int disyolo_aug_place_hw(const uint8_t* src, int is_mask, int image_h, int image_w, uint8_t* dst, int net_h, int net_w,
+                                    int new_w, int new_h, int dx, int dy, int flip, void* stream) {
+  DY_REQUIRE(src && dst && image_h > 0 && image_w > 0 && net_h > 0 && net_w > 0 && new_w > 0 && new_h > 0 && flip >= 1 && flip <= 3,
              "aug_place: bad args");
-  DY_RECORD_OR_RUN([=](void* s) { return disyolo_aug_place(src, is_mask, image_h, image_w, dst, size, new_w, new_h, dx, dy, flip, s); });
-  const int g = grid_for((int64_t)size * size);
+  DY_RECORD_OR_RUN([=](void* s) {
+    return disyolo_aug_place_hw(src, is_mask, image_h, image_w, dst, net_h, net_w, new_w, new_h, dx, dy, flip, s);
+  });
+  const int g = grid_for((int64_t)net_h * net_w);
   if (is_mask)
-    hipLaunchKernelGGL(place_mask_kernel, dim3(g), dim3(256), 0, (hipStream_t)stream, src, image_h, image_w, dst, size, new_w, new_h, dx, dy, flip);
+    hipLaunchKernelGGL(place_mask_kernel, dim3(g), dim3(256), 0, (hipStream_t)stream, src, image_h, image_w, dst, net_h, net_w, new_w, new_h, dx, dy, flip);
   else
-    hipLaunchKernelGGL(place_image_kernel, dim3(g), dim3(256), 0, (hipStream_t)stream, src, image_h, image_w, dst, size, new_w, new_h, dx, dy, flip);
+    hipLaunchKernelGGL(place_image_kernel, dim3(g), dim3(256), 0, (hipStream_t)stream, src, image_h, image_w, dst, net_h, net_w, new_w, new_h, dx, dy, flip);
   DY_CHECK_LAUNCH();
   return DISYOLO_OK;
 }
 
 extern "C" int disyolo_aug_place_batch(const disyolo_place_job* jobs, int njobs, int size, void* stream) {
-  DY_REQUIRE(jobs && njobs > 0 && njobs <= 65535 && size > 0, "aug_place_batch: bad args");
-  DY_RECORD_OR_RUN([=](void* s) { return disyolo_aug_place_batch(jobs, njobs, size, s); });
-  int gx = grid_for((int64_t)size * size);
+  return disyolo_aug_place_batch_hw(jobs, njobs, size, size, stream);
+}
+
+extern "C" int disyolo_aug_place_batch_hw(const disyolo_place_job* jobs, int njobs, int net_h, int net_w, void* stream) {
+  DY_REQUIRE(jobs && njobs > 0 && njobs <= 65535 && net_h > 0 && net_w > 0, "aug_place_batch: bad args");
+  DY_RECORD_OR_RUN([=](void* s) { return disyolo_aug_place_batch_hw(jobs, njobs, net_h, net_w, s); });
+  int gx = grid_for((int64_t)net_h * net_w);
   if (gx > 512) gx = 512;     // (grid-stride: the jobs of a batch fill the chip between them)
-  hipLaunchKernelGGL(place_batch_kernel, dim3(gx, njobs), dim3(256), 0, (hipStream_t)stream, jobs, size);
+  hipLaunchKernelGGL(place_batch_kernel, dim3(gx, njobs), dim3(256), 0, (hipStream_t)stream, jobs, net_h, net_w);
   DY_CHECK_LAUNCH();
   return DISYOLO_OK;
 }
 
 extern "C" int disyolo_aug_salt_pepper(uint8_t* image, int size, const int32_t* rows, const int32_t* cols, int nsalt, int npepper,
                                        void* stream) {
-  DY_REQUIRE(image && rows && cols && size > 0 && nsalt >= 0 && npepper >= 0, "aug_salt_pepper: bad args");
-  DY_RECORD_OR_RUN([=](void* s) { return disyolo_aug_salt_pepper(image, size, rows, cols, nsalt, npepper, s); });
+  return disyolo_aug_salt_pepper_hw(image, size, size, rows, cols, nsalt, npepper, stream);
+}
+
+extern "C" int disyolo_aug_salt_pepper_hw(uint8_t* image, int net_h, int net_w, const int32_t* rows, const int32_t* cols, int nsalt,
+                                          int npepper, void* stream) {
+  DY_REQUIRE(image && rows && cols && net_h > 0 && net_w > 0 && nsalt >= 0 && npepper >= 0, "aug_salt_pepper: bad args");
+  DY_RECORD_OR_RUN([=](void* s) { return disyolo_aug_salt_pepper_hw(image, net_h, net_w, rows, cols, nsalt, npepper, s); });
   const int n = nsalt + npepper;
   if (n == 0) return DISYOLO_OK;
   // two launches keep the reference's order: all salt writes, then all pepper writes
-  if (nsalt) hipLaunchKernelGGL(salt_pepper_kernel, dim3((nsalt + 255) / 256), dim3(256), 0, (hipStream_t)stream, image, size, rows, cols, nsalt, 0);
-  if (npepper) hipLaunchKernelGGL(salt_pepper_kernel, dim3((npepper + 255) / 256), dim3(256), 0, (hipStream_t)stream, image, size, rows + nsalt, cols + nsalt, 0, npepper);
+  if (nsalt) hipLaunchKernelGGL(salt_pepper_kernel, dim3((nsalt + 255) / 256), dim3(256), 0, (hipStream_t)stream, image, net_h, net_w, rows, cols, nsalt, 0);
+  if (npepper) hipLaunchKernelGGL(salt_pepper_kernel, dim3((npepper + 255) / 256), dim3(256), 0, (hipStream_t)stream, image, net_h, net_w, rows + nsalt, cols + nsalt, 0, npepper);
   DY_CHECK_LAUNCH();
   return DISYOLO_OK;
 }
 
 extern "C" int disyolo_aug_change_light(uint8_t* image, int size, double coeff, void* stream) {
-  DY_REQUIRE(image && size > 0 && coeff >= 0.0, "aug_change_light: bad args");
-  DY_RECORD_OR_RUN([=](void* s) { return disyolo_aug_change_light(image, size, coeff, s); });
-  hipLaunchKernelGGL(change_light_kernel, dim3(grid_for((int64_t)size * size)), dim3(256), 0, (hipStream_t)stream, image, (int64_t)size * size, coeff);
+  return disyolo_aug_change_light_hw(image, size, size, coeff, stream);
+}
+
+extern "C" int disyolo_aug_change_light_hw(uint8_t* image, int net_h, int net_w, double coeff, void* stream) {
+  DY_REQUIRE(image && net_h > 0 && net_w > 0 && coeff >= 0.0, "aug_change_light: bad args");
+  DY_RECORD_OR_RUN([=](void* s) { return disyolo_aug_change_light_hw(image, net_h, net_w, coeff, s); });
+  hipLaunchKernelGGL(change_light_kernel, dim3(grid_for((int64_t)net_h * net_w)), dim3(256), 0, (hipStream_t)stream, image, (int64_t)net_h * net_w, coeff);
   DY_CHECK_LAUNCH();
   return DISYOLO_OK;
 }
 
 extern "C" int disyolo_aug_motion_blur3(const uint8_t* src, uint8_t* dst, int size, int angle, int line_type, void* stream) {
-  DY_REQUIRE(src && dst && src != dst && size > 0 && (angle == 0 || angle == 45 || angle == 90 || angle == 135) && line_type >= 0 && line_type <= 2,
+  return disyolo_aug_motion_blur3_hw(src, dst, size, size, angle, line_type, stream);
+}
+
+extern "C" int disyolo_aug_motion_blur3_hw(const uint8_t* src, uint8_t* dst, int net_h, int net_w, int angle, int line_type,
+                                           void* stream) {
+  DY_REQUIRE(src && dst && src != dst && net_h > 0 && net_w > 0 && (angle == 0 || angle == 45 || angle == 90 || angle == 135) && line_type >= 0 && line_type <= 2,
              "aug_motion_blur3: bad args (angle 0/45/90/135, line_type 0 full / 1 right / 2 left)");
-  DY_RECORD_OR_RUN([=](void* s) { return disyolo_aug_motion_blur3(src, dst, size, angle, line_type, s); });
+  DY_RECORD_OR_RUN([=](void* s) { return disyolo_aug_motion_blur3_hw(src, dst, net_h, net_w, angle, line_type, s); });
   // the "right" end of the 3x3 line in kernel coordinates (row down): pyblur's LineDictionary anchors
   // {0: [1,0,1,2], 45: [2,0,0,2], 90: [0,1,2,1], 135: [0,0,2,2]} = (row0, col0, row1, col1); 'right' keeps the SECOND
   // anchor (the first is replaced by the centre), 'left' the first: 0: +x, 45: up-right, 90: DOWN, 135: DOWN-right.
@@ -307,8 +334,8 @@ extern "C" int disyolo_aug_motion_blur3(const uint8_t* src, uint8_t* dst, int si
   const int dyA = angle == 0 ? 0 : (angle == 45 ? -1 : 1);
   const int use_a = line_type != 2, use_b = line_type != 1;
   // a convolution flips the kernel: the tap at kernel offset (+dy,+dx) reads the pixel at (-dy,-dx)
-  hipLaunchKernelGGL(motion_blur3_kernel, dim3(grid_for((int64_t)size * size)), dim3(256), 0, (hipStream_t)stream, src, dst, size, -dyA,
-                     -dxA, use_a, use_b);
+  hipLaunchKernelGGL(motion_blur3_kernel, dim3(grid_for((int64_t)net_h * net_w)), dim3(256), 0, (hipStream_t)stream, src, dst, net_h,
+                     net_w, -dyA, -dxA, use_a, use_b);
   DY_CHECK_LAUNCH();
   return DISYOLO_OK;
 }

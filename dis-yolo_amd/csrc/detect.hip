@@ -11,14 +11,14 @@
 namespace {
 
 struct ScaleInfo {
-  const float* logits;  // [B,g,g,3,5+C]
-  int g;
+  const float* logits;  // [B,gh,gw,3,5+C]
+  int gh, gw;
   int cand0;  // first candidate index of this scale inside an image
   float aw[3], ah[3];
 };
 struct DecodeParams {
   ScaleInfo sc[3];
-  int B, S, C, NC;
+  int B, H, W, C, NC;   // H x W = the net's input (net_h, net_w)
   const float* window;  // [B,4] y1,x1,y2,x2
   float4* boxes;        // [B][NC] (y1,x1,y2,x2)
   float* scores;        // [B][NC]
@@ -27,7 +27,7 @@ struct DecodeParams {
 
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + expf(-x)); }
 
-// candidate order inside an image: scale (S/8, S/16, S/32 grids), then y, x, anchor
+// candidate order inside an image: scale (1/8, 1/16, 1/32 grids), then y, x, anchor (row-major)
 // (yolo/yolo3_net_pos.py:527-542)
 __global__ __launch_bounds__(256) void decode_score_kernel(DecodeParams p) {
   const int b = blockIdx.y;
@@ -40,9 +40,9 @@ __global__ __launch_bounds__(256) void decode_score_kernel(DecodeParams p) {
   const int local = idx - si.cand0;
   const int a = local % 3;
   const int cell = local / 3;
-  const int x = cell % si.g, y = cell / si.g;
+  const int x = cell % si.gw, y = cell / si.gw;
   const int D = 5 + p.C;
-  const float* t = si.logits + (((size_t)b * si.g * si.g + cell) * 3 + a) * D;
+  const float* t = si.logits + (((size_t)b * si.gh * si.gw + cell) * 3 + a) * D;
   const float conf = sigmoidf_(t[4]);
   // softmax max-probability and argmax (first maximum wins, tf.argmax)
   float mx = t[5];
@@ -55,11 +55,11 @@ __global__ __launch_bounds__(256) void decode_score_kernel(DecodeParams p) {
   float den = 0.f;
   for (int c = 0; c < p.C; ++c) den += expf(t[5 + c] - mx);
   const float score = conf * (1.f / den);
-  const float g = (float)si.g, net = (float)p.S;
-  const float xc = ((float)x + sigmoidf_(t[0])) / g;
-  const float yc = ((float)y + sigmoidf_(t[1])) / g;
-  const float w = expf(t[2]) * si.aw[a] / net;
-  const float h = expf(t[3]) * si.ah[a] / net;
+  // grid_factor = [gw, gh], net_factor = [net_w, net_h] (yolo/yolo3_net_pos.py:473-506)
+  const float xc = ((float)x + sigmoidf_(t[0])) / (float)si.gw;
+  const float yc = ((float)y + sigmoidf_(t[1])) / (float)si.gh;
+  const float w = expf(t[2]) * si.aw[a] / (float)p.W;
+  const float h = expf(t[3]) * si.ah[a] / (float)p.H;
   const float* win = p.window + b * 4;
   float4 bx;
   bx.x = fmaxf(fminf(yc - h / 2.f, win[2]), win[0]);
@@ -539,26 +539,27 @@ __device__ __forceinline__ void bin_edges(float lo, float hi, int e[K + 1]) {
   e[K] = (int)hi;
 }
 
-// masks[b,r,y,x] = sigmoid(score[b,y,x,bin(y,x)]) inside the box, 0.5 outside (:925-928); score rows have k*k channels
+// masks[b,r,y,x] = sigmoid(score[b,y,x,bin(y,x)]) inside the box, 0.5 outside (:925-928); score rows have k*k channels.
+// The map is Hm x Wm: y-coordinates scale by Hm, x-coordinates by Wm (the reference's one `size` at Hm = Wm)
 template <int K>
 __global__ __launch_bounds__(256) void psroi_assemble_kernel(const float* score, const float* det, int B, int max_det,
-                                                             int Sm, float* masks, int* keep) {
+                                                             int Hm, int Wm, float* masks, int* keep) {
   const int r = blockIdx.y, b = blockIdx.z;
   const float* d = det + ((size_t)b * max_det + r) * 6;
-  const float sz = (float)Sm;
-  const float y1 = rintf(d[0] * sz), x1 = rintf(d[1] * sz), y2 = rintf(d[2] * sz), x2 = rintf(d[3] * sz);
+  const float szy = (float)Hm, szx = (float)Wm;
+  const float y1 = rintf(d[0] * szy), x1 = rintf(d[1] * szx), y2 = rintf(d[2] * szy), x2 = rintf(d[3] * szx);
   const bool kp = (y2 - y1) > 0.f && (x2 - x1) > 0.f;
   if (blockIdx.x == 0 && threadIdx.x == 0) keep[b * max_det + r] = kp ? 1 : 0;
   int gy[K + 1], gx[K + 1];
   bin_edges<K>(y1, y2, gy);
   bin_edges<K>(x1, x2, gx);
-  const int npx = Sm * Sm;
+  const int npx = Hm * Wm;
   float* out = masks + ((size_t)b * max_det + r) * npx;
   const float* sc = score + (size_t)b * npx * (K * K);
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < npx; i += gridDim.x * blockDim.x) {
     float v = 0.f;
     if (kp) {
-      const int y = i / Sm, x = i - y * Sm;
+      const int y = i / Wm, x = i - y * Wm;
       float logit = 0.f;
       if (y >= gy[0] && y < gy[K] && x >= gx[0] && x < gx[K]) {
         int by = 0, bx = 0;
@@ -583,7 +584,8 @@ __global__ __launch_bounds__(256) void psroi_assemble_kernel(const float* score,
 // same as the host restatement's), writes the per-detection bit and keeps the class of the last
 // covering detection for the merged class map.
 // THE tap arithmetic and the > 0.5 decision of the paste, shared by the per-image and the batched kernel so the two cannot drift:
-// the bit of pixel (y, x) for one detection, m = its size x size mask, r = its rect row (cy1,cx1,cy2,cx2, y1,x1,y2,x2)
+// the bit of pixel (y, x) for one detection, m = its mask (rows of `size` floats: the map's width), r = its rect row
+// (cy1,cx1,cy2,cx2, y1,x1,y2,x2)
 __device__ __forceinline__ unsigned char paste_bit(const float* m, int size, const int* r, int y, int x) {
   const int cy1 = r[0], cx1 = r[1], cy2 = r[2], cx2 = r[3], y1 = r[4], x1 = r[5], y2 = r[6], x2 = r[7];
   const int sh = cy2 - cy1, sw = cx2 - cx1, dh = y2 - y1, dw = x2 - x1;
@@ -606,7 +608,7 @@ __device__ __forceinline__ unsigned char paste_bit(const float* m, int size, con
   return v > 0.5f ? 1 : 0;
 }
 
-__global__ __launch_bounds__(256) void mask_paste_kernel(const float* masks, int n, int size, const int* rects,
+__global__ __launch_bounds__(256) void mask_paste_kernel(const float* masks, int n, int mh, int mw, const int* rects,
                                                          const int* classids, int H, int W, unsigned char* full,
                                                          unsigned char* merged) {
   const int64_t total = (int64_t)H * W;
@@ -614,7 +616,7 @@ __global__ __launch_bounds__(256) void mask_paste_kernel(const float* masks, int
     const int y = (int)(i / W), x = (int)(i - (int64_t)y * W);
     unsigned char mcls = 0;
     for (int k = 0; k < n; ++k) {
-      const unsigned char bit = paste_bit(masks + (size_t)k * size * size, size, rects + k * 8, y, x);
+      const unsigned char bit = paste_bit(masks + (size_t)k * mh * mw, mw, rects + k * 8, y, x);
       if (full) full[(size_t)k * total + i] = bit;
       if (bit) mcls = (unsigned char)(classids[k] + 1);
     }
@@ -637,7 +639,7 @@ constexpr int PB_CHUNK = PB_T * PB_PX;
 constexpr int PB_GT = 32;
 constexpr int PB_MAXN = 64;
 
-__global__ __launch_bounds__(PB_T) void mask_paste_iou_batch_kernel(const disyolo_paste_job* jobs, int njobs, int size,
+__global__ __launch_bounds__(PB_T) void mask_paste_iou_batch_kernel(const disyolo_paste_job* jobs, int njobs, int mh, int mw,
                                                                     unsigned long long* conf) {
   __shared__ unsigned int s_area[PB_MAXN];
   __shared__ unsigned int s_inter[PB_MAXN * PB_GT];
@@ -669,9 +671,9 @@ __global__ __launch_bounds__(PB_T) void mask_paste_iou_batch_kernel(const disyol
     for (int k = 0; k < n; ++k) {
       const int* r = j.rects + k * 8;
       unsigned char bit = 0;
-      // (a crop that leaves the size x size mask would read outside `masks`: such a row pastes nothing)
-      if (valid && r[0] >= 0 && r[1] >= 0 && r[2] <= size && r[3] <= size)
-        bit = paste_bit(j.masks + (size_t)k * size * size, size, r, y, x);
+      // (a crop that leaves the mh x mw mask would read outside `masks`: such a row pastes nothing)
+      if (valid && r[0] >= 0 && r[1] >= 0 && r[2] <= mh && r[3] <= mw)
+        bit = paste_bit(j.masks + (size_t)k * mh * mw, mw, r, y, x);
       if (bit) {
         b |= 1ull << k;
         mcls = (unsigned char)(s_cls[k] + 1);
@@ -723,14 +725,14 @@ __global__ __launch_bounds__(PB_T) void mask_paste_iou_batch_kernel(const disyol
 
 // image_read (calculate_test_map.py:149-176, utils/val_data.py:36-63): aspect-preserving bilinear
 // resize of an RGB uint8 image (as float32, like cv2.resize(image.astype(float32), INTER_LINEAR))
-// centred in a size x size letter box padded with 127, then / 255.  Same tap arithmetic as the mask
+// centred in an oh x ow letter box padded with 127, then / 255.  Same tap arithmetic as the mask
 // paste above (aligned pixel centres, clamped border taps with weight 0, horizontal then vertical
 // pass, float32 without FMA).  One thread per output pixel; the three channels together.
-__global__ __launch_bounds__(256) void letterbox_kernel(const unsigned char* rgb, int H, int W, float* out, int size,
+__global__ __launch_bounds__(256) void letterbox_kernel(const unsigned char* rgb, int H, int W, float* out, int oh, int ow,
                                                         int new_h, int new_w, int top, int left) {
-  const int64_t total = (int64_t)size * size;
+  const int64_t total = (int64_t)oh * ow;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-    const int y = (int)(i / size), x = (int)(i - (int64_t)y * size);
+    const int y = (int)(i / ow), x = (int)(i - (int64_t)y * ow);
     float v[3] = {127.f, 127.f, 127.f};
     if (y >= top && y < top + new_h && x >= left && x < left + new_w) {
       float fx = (float)(((double)(x - left) + 0.5) * ((double)W / (double)new_w) - 0.5);
@@ -790,10 +792,10 @@ __global__ __launch_bounds__(256) void confusion_n_kernel(const unsigned char* t
 
 }  // namespace
 
-extern "C" size_t disyolo_detect_workspace(int B, int S, int num_class) {
-  if (B <= 0 || S <= 0 || S % 32) return 0;
-  const int g1 = S / 32;
-  const size_t NC = 3 * (size_t)(16 * g1 * g1 + 4 * g1 * g1 + g1 * g1);
+extern "C" size_t disyolo_detect_workspace_hw(int B, int H, int W, int num_class) {
+  if (B <= 0 || H <= 0 || W <= 0 || H % 32 || W % 32) return 0;
+  const size_t c1 = (size_t)(H / 32) * (W / 32);
+  const size_t NC = 3 * (16 * c1 + 4 * c1 + c1);
   // boxes (16 B) + scores + classes, per-class list + live, per-class kept (idx, score, n)
   if (num_class <= 16)
     return (size_t)B * NC * (16 + 4 + 4) + (size_t)B * num_class * NC * 8 + (size_t)B * num_class * (64 * 8 + 4) + 256;
@@ -802,17 +804,31 @@ extern "C" size_t disyolo_detect_workspace(int B, int S, int num_class) {
          (size_t)B * num_class * (64 * 8 + 4) + 256;
 }
 
+extern "C" size_t disyolo_detect_workspace(int B, int S, int num_class) {
+  return disyolo_detect_workspace_hw(B, S, S, num_class);
+}
+
 extern "C" int disyolo_detect(const float* logits3, const float* logits2, const float* logits1, int B, int S,
                               int num_class, const float* anchors_host, const float* clip_window, float obj_thresh,
                               float nms_thresh, int max_det, float* detections, int32_t* det_count, void* workspace,
                               size_t workspace_bytes, void* stream) {
+  return disyolo_detect_hw(logits3, logits2, logits1, B, S, S, num_class, anchors_host, clip_window, obj_thresh, nms_thresh,
+                           max_det, detections, det_count, workspace, workspace_bytes, stream);
+}
+
+// the filter on a net of H x W pixels: head grids (H/8, W/8), (H/16, W/16), (H/32, W/32)
+extern "C" int disyolo_detect_hw(const float* logits3, const float* logits2, const float* logits1, int B, int H, int W,
+                                 int num_class, const float* anchors_host, const float* clip_window, float obj_thresh,
+                                 float nms_thresh, int max_det, float* detections, int32_t* det_count, void* workspace,
+                                 size_t workspace_bytes, void* stream) {
   DY_REQUIRE(logits3 && logits2 && logits1 && anchors_host && clip_window && detections && det_count,
              "detect: null pointer");
-  DY_REQUIRE(B > 0 && S > 0 && S % 32 == 0 && num_class > 0 && num_class <= WD_MAXC, "detect: bad sizes");
+  DY_REQUIRE(B > 0 && H > 0 && W > 0 && H % 32 == 0 && W % 32 == 0 && num_class > 0 && num_class <= WD_MAXC,
+             "detect: bad sizes");
   DY_REQUIRE(max_det > 0 && max_det <= 64 && (num_class > 16 || num_class * max_det <= MAX_KEEP),
              "detect: max_det must be <= 64");
   DY_REQUIRE(obj_thresh >= 0.f, "detect: obj_thresh must be >= 0");
-  if (!workspace || workspace_bytes < disyolo_detect_workspace(B, S, num_class)) {
+  if (!workspace || workspace_bytes < disyolo_detect_workspace_hw(B, H, W, num_class)) {
     disyolo_set_error("detect: workspace too small");
     return DISYOLO_E_WORKSPACE;
   }
@@ -820,26 +836,26 @@ extern "C" int disyolo_detect(const float* logits3, const float* logits2, const 
     std::array<float, 18> anc;
     for (int i = 0; i < 18; ++i) anc[i] = anchors_host[i];
     DY_RECORD_OR_RUN([=](void* s) {
-      return disyolo_detect(logits3, logits2, logits1, B, S, num_class, anc.data(), clip_window, obj_thresh, nms_thresh,
-                            max_det, detections, det_count, workspace, workspace_bytes, s);
+      return disyolo_detect_hw(logits3, logits2, logits1, B, H, W, num_class, anc.data(), clip_window, obj_thresh,
+                               nms_thresh, max_det, detections, det_count, workspace, workspace_bytes, s);
     });
   }
-  const int g1 = S / 32;
   DecodeParams p;
   const float* lg[3] = {logits3, logits2, logits1};
-  const int gs[3] = {4 * g1, 2 * g1, g1};
+  const int div[3] = {8, 16, 32};
   int c0 = 0;
   for (int s = 0; s < 3; ++s) {
     p.sc[s].logits = lg[s];
-    p.sc[s].g = gs[s];
+    p.sc[s].gh = H / div[s];
+    p.sc[s].gw = W / div[s];
     p.sc[s].cand0 = c0;
-    c0 += gs[s] * gs[s] * 3;
+    c0 += p.sc[s].gh * p.sc[s].gw * 3;
     for (int a = 0; a < 3; ++a) {
       p.sc[s].aw[a] = anchors_host[(3 * s + a) * 2 + 0];
       p.sc[s].ah[a] = anchors_host[(3 * s + a) * 2 + 1];
     }
   }
-  p.B = B; p.S = S; p.C = num_class; p.NC = c0;
+  p.B = B; p.H = H; p.W = W; p.C = num_class; p.NC = c0;
   p.window = clip_window;
   char* ws = (char*)workspace;
   p.boxes = (float4*)ws;                  ws += (size_t)B * c0 * 16;
@@ -884,28 +900,45 @@ extern "C" int disyolo_detect(const float* logits3, const float* logits2, const 
 
 extern "C" int disyolo_psroi_assemble(const float* score, const float* detections, int B, int max_det, int map_size,
                                       int k, float* masks, int32_t* keep, void* stream) {
-  DY_REQUIRE(score && detections && masks && keep && B > 0 && max_det > 0 && map_size > 0, "psroi_assemble: bad args");
+  return disyolo_psroi_assemble_hw(score, detections, B, max_det, map_size, map_size, k, masks, keep, stream);
+}
+
+extern "C" int disyolo_psroi_assemble_hw(const float* score, const float* detections, int B, int max_det, int map_h,
+                                         int map_w, int k, float* masks, int32_t* keep, void* stream) {
+  DY_REQUIRE(score && detections && masks && keep && B > 0 && max_det > 0 && map_h > 0 && map_w > 0 &&
+                 (int64_t)map_h * map_w <= (1ll << 30),
+             "psroi_assemble: bad args");
   DY_REQUIRE(k == 3 || k == 5 || k == 7, "psroi_assemble: k must be one of k = 3, 5, 7 (got %d)", k);
-  DY_RECORD_OR_RUN([=](void* s) { return disyolo_psroi_assemble(score, detections, B, max_det, map_size, k, masks, keep, s); });
-  const int npx = map_size * map_size;
+  DY_RECORD_OR_RUN([=](void* s) {
+    return disyolo_psroi_assemble_hw(score, detections, B, max_det, map_h, map_w, k, masks, keep, s);
+  });
+  const int npx = map_h * map_w;
   int gx = ceil_div(npx, 256 * 4);
   if (gx < 1) gx = 1;
   auto kern = k == 3 ? psroi_assemble_kernel<3> : k == 5 ? psroi_assemble_kernel<5> : psroi_assemble_kernel<7>;
-  hipLaunchKernelGGL(kern, dim3(gx, max_det, B), dim3(256), 0, (hipStream_t)stream, score, detections, B, max_det, map_size,
-                     masks, keep);
+  hipLaunchKernelGGL(kern, dim3(gx, max_det, B), dim3(256), 0, (hipStream_t)stream, score, detections, B, max_det, map_h,
+                     map_w, masks, keep);
   DY_CHECK_LAUNCH();
   return DISYOLO_OK;
 }
 
 extern "C" int disyolo_mask_paste(const float* masks, int n, int size, const int32_t* rects, const int32_t* classids,
                                   int image_h, int image_w, uint8_t* full_masks, uint8_t* merged, void* stream) {
-  DY_REQUIRE(merged && image_h > 0 && image_w > 0 && n >= 0 && size > 0, "mask_paste: bad args");
+  return disyolo_mask_paste_hw(masks, n, size, size, rects, classids, image_h, image_w, full_masks, merged, stream);
+}
+
+extern "C" int disyolo_mask_paste_hw(const float* masks, int n, int map_h, int map_w, const int32_t* rects,
+                                     const int32_t* classids, int image_h, int image_w, uint8_t* full_masks, uint8_t* merged,
+                                     void* stream) {
+  DY_REQUIRE(merged && image_h > 0 && image_w > 0 && n >= 0 && map_h > 0 && map_w > 0, "mask_paste: bad args");
   DY_REQUIRE(n == 0 || (masks && rects && classids), "mask_paste: null pointer");
-  DY_RECORD_OR_RUN([=](void* s) { return disyolo_mask_paste(masks, n, size, rects, classids, image_h, image_w, full_masks, merged, s); });
+  DY_RECORD_OR_RUN([=](void* s) {
+    return disyolo_mask_paste_hw(masks, n, map_h, map_w, rects, classids, image_h, image_w, full_masks, merged, s);
+  });
   const int64_t total = (int64_t)image_h * image_w;
   int grid = (int)((total + 255) / 256);
   if (grid > 256 * 16) grid = 256 * 16;
-  hipLaunchKernelGGL(mask_paste_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, masks, n, size, (const int*)rects,
+  hipLaunchKernelGGL(mask_paste_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, masks, n, map_h, map_w, (const int*)rects,
                      (const int*)classids, image_h, image_w, (unsigned char*)full_masks, (unsigned char*)merged);
   DY_CHECK_LAUNCH();
   return DISYOLO_OK;
@@ -935,8 +968,14 @@ extern "C" int disyolo_paste_job_plan(disyolo_paste_job* jobs, int njobs) {
 
 extern "C" int disyolo_mask_paste_iou_batch(const disyolo_paste_job* jobs_host, const disyolo_paste_job* jobs, int njobs, int size,
                                             int64_t* conf, void* stream) {
+  DY_REQUIRE(size > 0 || !(jobs_host && jobs && njobs > 0), "mask_paste_iou_batch: size must be > 0");
+  return disyolo_mask_paste_iou_batch_hw(jobs_host, jobs, njobs, size, size, conf, stream);
+}
+
+extern "C" int disyolo_mask_paste_iou_batch_hw(const disyolo_paste_job* jobs_host, const disyolo_paste_job* jobs, int njobs,
+                                               int map_h, int map_w, int64_t* conf, void* stream) {
   DY_REQUIRE(jobs_host && jobs && njobs > 0, "mask_paste_iou_batch: null table or njobs <= 0");
-  DY_REQUIRE(size > 0, "mask_paste_iou_batch: size must be > 0");
+  DY_REQUIRE(map_h > 0 && map_w > 0, "mask_paste_iou_batch: size must be > 0");
   // the host copy is what this call can check and size the grid from; it must be a planned table (disyolo_paste_job_plan)
   std::vector<disyolo_paste_job> plan(jobs_host, jobs_host + njobs);
   const int blocks = disyolo_paste_job_plan(plan.data(), njobs);
@@ -945,8 +984,8 @@ extern "C" int disyolo_mask_paste_iou_batch(const disyolo_paste_job* jobs_host, 
     DY_REQUIRE(plan[i].block0 == jobs_host[i].block0, "mask_paste_iou_batch: job %d is not planned (disyolo_paste_job_plan)", i);
     DY_REQUIRE(!jobs_host[i].true_map || conf, "mask_paste_iou_batch: job %d has a true_map but conf is NULL", i);
   }
-  DY_RECORD_OR_RUN([=](void* s) { return disyolo_mask_paste_iou_batch(plan.data(), jobs, njobs, size, conf, s); });
-  hipLaunchKernelGGL(mask_paste_iou_batch_kernel, dim3(blocks), dim3(PB_T), 0, (hipStream_t)stream, jobs, njobs, size,
+  DY_RECORD_OR_RUN([=](void* s) { return disyolo_mask_paste_iou_batch_hw(plan.data(), jobs, njobs, map_h, map_w, conf, s); });
+  hipLaunchKernelGGL(mask_paste_iou_batch_kernel, dim3(blocks), dim3(PB_T), 0, (hipStream_t)stream, jobs, njobs, map_h, map_w,
                      (unsigned long long*)conf);
   DY_CHECK_LAUNCH();
   return DISYOLO_OK;
@@ -954,29 +993,35 @@ extern "C" int disyolo_mask_paste_iou_batch(const disyolo_paste_job* jobs_host, 
 
 extern "C" int disyolo_letterbox(const uint8_t* rgb, int image_h, int image_w, float* out, int size, float* window_host,
                                  void* stream) {
-  DY_REQUIRE(rgb && out && image_h > 0 && image_w > 0 && size > 0, "letterbox: bad args");
+  return disyolo_letterbox_hw(rgb, image_h, image_w, out, size, size, window_host, stream);
+}
+
+// the letter box of a net of net_h x net_w pixels: the width binds when net_w / image_w < net_h / image_h
+extern "C" int disyolo_letterbox_hw(const uint8_t* rgb, int image_h, int image_w, float* out, int net_h, int net_w,
+                                    float* window_host, void* stream) {
+  DY_REQUIRE(rgb && out && image_h > 0 && image_w > 0 && net_h > 0 && net_w > 0, "letterbox: bad args");
   int new_h, new_w;
-  if (((double)size / image_w) < ((double)size / image_h)) {   // Python float division
-    new_h = (int)(((int64_t)image_h * size) / image_w);
-    new_w = size;
+  if (((double)net_w / image_w) < ((double)net_h / image_h)) {   // Python float division
+    new_h = (int)(((int64_t)image_h * net_w) / image_w);
+    new_w = net_w;
   } else {
-    new_w = (int)(((int64_t)image_w * size) / image_h);
-    new_h = size;
+    new_w = (int)(((int64_t)image_w * net_h) / image_h);
+    new_h = net_h;
   }
-  DY_REQUIRE(new_h > 0 && new_w > 0, "letterbox: degenerate image");
-  const int top = (size - new_h) / 2, left = (size - new_w) / 2;
-  if (window_host) {   // [top, left, bottom, right] normalised, float32 of the float64 quotient like numpy
-    window_host[0] = (float)((double)top / size);
-    window_host[1] = (float)((double)left / size);
-    window_host[2] = (float)((double)(new_h + top) / size);
-    window_host[3] = (float)((double)(new_w + left) / size);
+  DY_REQUIRE(new_h > 0 && new_w > 0 && new_h <= net_h && new_w <= net_w, "letterbox: degenerate image");
+  const int top = (net_h - new_h) / 2, left = (net_w - new_w) / 2;
+  if (window_host) {   // [top, left, bottom, right] normalised by (net_h, net_w), float32 of the float64 quotient like numpy
+    window_host[0] = (float)((double)top / net_h);
+    window_host[1] = (float)((double)left / net_w);
+    window_host[2] = (float)((double)(new_h + top) / net_h);
+    window_host[3] = (float)((double)(new_w + left) / net_w);
   }
-  DY_RECORD_OR_RUN([=](void* s) { return disyolo_letterbox(rgb, image_h, image_w, out, size, nullptr, s); });
-  const int64_t total = (int64_t)size * size;
+  DY_RECORD_OR_RUN([=](void* s) { return disyolo_letterbox_hw(rgb, image_h, image_w, out, net_h, net_w, nullptr, s); });
+  const int64_t total = (int64_t)net_h * net_w;
   int grid = (int)((total + 255) / 256);
   if (grid > 256 * 16) grid = 256 * 16;
-  hipLaunchKernelGGL(letterbox_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, rgb, image_h, image_w, out, size,
-                     new_h, new_w, top, left);
+  hipLaunchKernelGGL(letterbox_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, rgb, image_h, image_w, out, net_h,
+                     net_w, new_h, new_w, top, left);
   DY_CHECK_LAUNCH();
   return DISYOLO_OK;
 }

@@ -23,12 +23,12 @@ __device__ __forceinline__ float sigmoid_ce(float z, float x) {
 constexpr int DL_LD = 32;  // padded channel count of the dlogits / dscore rows
 
 struct YoloLossParams {
-  const float* logits;  // [B,g,g,3,D]
-  const float* labels;  // [B,g,g,3,D]
+  const float* logits;  // [B,gh,gw,3,D]
+  const float* labels;  // [B,gh,gw,3,D]
   const float* true_boxes;  // [B,G,5] xc,yc,w,h,cls (normalised)
-  bf16* dlogits;        // [B,g,g,DL_LD]
+  bf16* dlogits;        // [B,gh,gw,DL_LD]
   float* partial;       // [gridDim.y*gridDim.x][5]
-  int B, g, C, G, S;
+  int B, gh, gw, C, G, H, W;   // grid gh x gw of a net of H x W pixels
   float aw[3], ah[3];
   float ignore_thresh, obj_scale, noobj_scale, class_scale, coord_scale;
   float inv_B;
@@ -52,20 +52,21 @@ __device__ __forceinline__ void yolo_loss_body(const YoloLossParams& p, const in
   }
   __syncthreads();
   const int D = 5 + p.C;
-  const int ncell = p.g * p.g;
+  const int ncell = p.gh * p.gw;
   const int idx = bx * 256 + threadIdx.x;
   float l_obj = 0.f, l_noobj = 0.f, l_cls = 0.f, l_xy = 0.f, l_wh = 0.f;
   if (idx < ncell * 3) {
     const int a = idx % 3, cell = idx / 3;
-    const int x = cell % p.g, y = cell / p.g;
+    const int x = cell % p.gw, y = cell / p.gw;
     const size_t base = (((size_t)b * ncell + cell) * 3 + a) * D;
     const float* t = p.logits + base;
     const float* lab = p.labels + base;
-    const float gf = (float)p.g, net = (float)p.S;
+    // grid_factor = [gw, gh], net_factor = [net_w, net_h] (:646, :709-718)
+    const float gfx = (float)p.gw, gfy = (float)p.gh, netw = (float)p.W, neth = (float)p.H;
     const float sx = sigmoidf_(t[0]), sy = sigmoidf_(t[1]);
     // decoded normalised box (interpret_output, :493-506)
-    const float bxc = ((float)x + sx) / gf, byc = ((float)y + sy) / gf;
-    const float bw = expf(t[2]) * p.aw[a] / net, bh = expf(t[3]) * p.ah[a] / net;
+    const float bxc = ((float)x + sx) / gfx, byc = ((float)y + sy) / gfy;
+    const float bw = expf(t[2]) * p.aw[a] / netw, bh = expf(t[3]) * p.ah[a] / neth;
     const float pminx = bxc - bw / 2.f, pmaxx = bxc + bw / 2.f, pminy = byc - bh / 2.f, pmaxy = byc + bh / 2.f;
     const float parea = bw * bh;
     float best = 0.f;  // iou is clipped to [0,1], so the max over >=1 boxes is >= 0
@@ -107,9 +108,9 @@ __device__ __forceinline__ void yolo_loss_body(const YoloLossParams& p, const in
       d[5 + c] = obj * p.class_scale * (pr - (c == tc ? 1.f : 0.f)) * p.inv_B;
     }
     // coordinates (:706-726)
-    const float tcx = lab[0] * gf - (float)x, tcy = lab[1] * gf - (float)y;
-    const float ttw = fminf(fmaxf(logf(lab[2] * net / p.aw[a]), -100.f), 100.f);
-    const float tth = fminf(fmaxf(logf(lab[3] * net / p.ah[a]), -100.f), 100.f);
+    const float tcx = lab[0] * gfx - (float)x, tcy = lab[1] * gfy - (float)y;
+    const float ttw = fminf(fmaxf(logf(lab[2] * netw / p.aw[a]), -100.f), 100.f);
+    const float tth = fminf(fmaxf(logf(lab[3] * neth / p.ah[a]), -100.f), 100.f);
     const float whs = 2.f - lab[2] * lab[3];
     const float whs2 = whs * whs * p.coord_scale;
     const float dx_ = obj * (sx - tcx), dy_ = obj * (sy - tcy);
@@ -184,8 +185,8 @@ __device__ __forceinline__ void yolo_loss_wide_body(const YoloLossParams& p, con
     s_tb[i] = p.true_boxes[((size_t)b * p.G + gidx) * 5 + k];
   }
   const int D = 5 + p.C;
-  const int ncell = p.g * p.g, nrow = ncell * 3;
-  const float gf = (float)p.g, net = (float)p.S;
+  const int ncell = p.gh * p.gw, nrow = ncell * 3;
+  const float gfx = (float)p.gw, gfy = (float)p.gh, netw = (float)p.W, neth = (float)p.H;
   const int r = tid >> 2, q = tid & 3;
   float l_obj = 0.f, l_noobj = 0.f, l_cls = 0.f, l_xy = 0.f, l_wh = 0.f;
   for (int ch = 0; ch < 256 / WL_ROWS; ++ch) {
@@ -202,13 +203,13 @@ __device__ __forceinline__ void yolo_loss_wide_body(const YoloLossParams& p, con
     if (r < nr) {                                      // (the four lanes of a quad agree)
       const int idx = row0 + r;
       const int a = idx % 3, cell = idx / 3;
-      const int x = cell % p.g, y = cell / p.g;
+      const int x = cell % p.gw, y = cell / p.gw;
       float* t = s_t + r * D;
       const float* lab = s_l + r * D;
       const float t0 = t[0], t1 = t[1], t2 = t[2], t3 = t[3], conf = t[4];
       const float sx = sigmoidf_(t0), sy = sigmoidf_(t1);
-      const float bxc = ((float)x + sx) / gf, byc = ((float)y + sy) / gf;
-      const float bw = expf(t2) * p.aw[a] / net, bh = expf(t3) * p.ah[a] / net;
+      const float bxc = ((float)x + sx) / gfx, byc = ((float)y + sy) / gfy;
+      const float bw = expf(t2) * p.aw[a] / netw, bh = expf(t3) * p.ah[a] / neth;
       const float pminx = bxc - bw / 2.f, pmaxx = bxc + bw / 2.f, pminy = byc - bh / 2.f, pmaxy = byc + bh / 2.f;
       const float parea = bw * bh;
       float best = 0.f;
@@ -252,9 +253,9 @@ __device__ __forceinline__ void yolo_loss_wide_body(const YoloLossParams& p, con
       den = quad_sum(den);
       const float lse = mx + logf(den);
       const float ttc = t[5 + tc];                     // read before any lane of the quad overwrites it
-      const float tcx = lab[0] * gf - (float)x, tcy = lab[1] * gf - (float)y;
-      const float ttw = fminf(fmaxf(logf(lab[2] * net / p.aw[a]), -100.f), 100.f);
-      const float tth = fminf(fmaxf(logf(lab[3] * net / p.ah[a]), -100.f), 100.f);
+      const float tcx = lab[0] * gfx - (float)x, tcy = lab[1] * gfy - (float)y;
+      const float ttw = fminf(fmaxf(logf(lab[2] * netw / p.aw[a]), -100.f), 100.f);
+      const float tth = fminf(fmaxf(logf(lab[3] * neth / p.ah[a]), -100.f), 100.f);
       const float whs = 2.f - lab[2] * lab[3];
       const float whs2 = whs * whs * p.coord_scale;
       const float dx_ = obj * (sx - tcx), dy_ = obj * (sy - tcy);
@@ -385,8 +386,8 @@ __device__ __forceinline__ void bin_edges(float lo, float hi, int e[K + 1]) {
 // single-thread version spent 40 us in dependent global loads.
 template <int K>
 __global__ __launch_bounds__(64) void mask_rois_kernel(const float* det_g, int max_det, const float* true_boxes_g, int G,
-                                                       const int* perm_det_g, const int* perm_gt_g, int B, int Sm, int n_det,
-                                                       int n_gt, float iou_thr, int* rois, int* roi_count) {
+                                                       const int* perm_det_g, const int* perm_gt_g, int B, int Hm, int Wm,
+                                                       int n_det, int n_gt, float iou_thr, int* rois, int* roi_count) {
   constexpr int RW = roi_w(K);
   __shared__ float s_det[64 * 6];
   __shared__ float s_tb[64 * 5];
@@ -452,9 +453,10 @@ __global__ __launch_bounds__(64) void mask_rois_kernel(const float* det_g, int m
       }
     }
     if (ng > 0 && best >= iou_thr) {
-      const float sz = (float)Sm;
-      const float y1 = rintf(rb[r][0] * sz), x1 = rintf(rb[r][1] * sz);
-      const float y2 = rintf(rb[r][2] * sz), x2 = rintf(rb[r][3] * sz);
+      // y-coordinates scale by the map's height, x-coordinates by its width (the reference's one `size` at Hm = Wm, :842)
+      const float szy = (float)Hm, szx = (float)Wm;
+      const float y1 = rintf(rb[r][0] * szy), x1 = rintf(rb[r][1] * szx);
+      const float y2 = rintf(rb[r][2] * szy), x2 = rintf(rb[r][3] * szx);
       int gy[K + 1], gx[K + 1];
       bin_edges<K>(y1, y2, gy);
       bin_edges<K>(x1, x2, gx);
@@ -468,7 +470,7 @@ __global__ __launch_bounds__(64) void mask_rois_kernel(const float* det_g, int m
       int area = 0;
       for (int by = 0; by < K; ++by)
         for (int bx = 0; bx < K; ++bx) {
-          const int hh = min(gy[by + 1], Sm) - max(gy[by], 0), ww = min(gx[bx + 1], Sm) - max(gx[bx], 0);
+          const int hh = min(gy[by + 1], Hm) - max(gy[by], 0), ww = min(gx[bx + 1], Wm) - max(gx[bx], 0);
           if (hh > 0 && ww > 0) area += hh * ww;
         }
       o[2 * K + 3] = area;
@@ -484,11 +486,11 @@ __global__ __launch_bounds__(64) void mask_rois_kernel(const float* det_g, int m
 
 // one thread = one score-map pixel; loops the image's positive RoIs.  score rows have k*k channels, dscore rows
 // dscore_ld(k) (the pad channels are written as zeros); the k*k gradient accumulators stay in registers.  The GT masks
-// are st x the score map's size (st = the mask subnet's stride: 1, 2, 4).
+// are st x the score map's size (st = the mask subnet's stride: 1, 2, 4); the map is Hm x Wm.
 template <int K>
 __global__ __launch_bounds__(256) void psroi_loss_kernel(const float* score, const uint8_t* true_masks, int G,
-                                                         const int* rois, const int* roi_count, int B, int Sm, int st,
-                                                         float mask_scale, bf16* dscore, float* partial) {
+                                                         const int* rois, const int* roi_count, int B, int Hm, int Wm,
+                                                         int st, float mask_scale, bf16* dscore, float* partial) {
   constexpr int RW = roi_w(K), KK = K * K, LD = dscore_ld(K);
   __shared__ int s_roi[ROI_MAX * RW];
   __shared__ float s_red[4][ROI_MAX];
@@ -496,7 +498,7 @@ __global__ __launch_bounds__(256) void psroi_loss_kernel(const float* score, con
   const int cnt = roi_count[b];
   for (int i = threadIdx.x; i < ROI_MAX * RW; i += 256) s_roi[i] = rois[(size_t)b * ROI_MAX * RW + i];
   __syncthreads();
-  const int npx = Sm * Sm;
+  const int npx = Hm * Wm;
   const int i = blockIdx.x * 256 + threadIdx.x;
   float g[KK];
 #pragma unroll
@@ -505,9 +507,9 @@ __global__ __launch_bounds__(256) void psroi_loss_kernel(const float* score, con
 #pragma unroll
   for (int r = 0; r < ROI_MAX; ++r) lsum[r] = 0.f;
   if (i < npx && cnt > 0) {
-    const int y = i / Sm, x = i - y * Sm;
+    const int y = i / Wm, x = i - y * Wm;
     const float* sc = score + ((size_t)b * npx + i) * KK;
-    const int S = st * Sm;
+    const int SH = st * Hm, SW = st * Wm;
     const float coef0 = mask_scale / ((float)B * (float)cnt);
 #pragma unroll
     for (int r = 0; r < ROI_MAX; ++r) {
@@ -523,7 +525,7 @@ __global__ __launch_bounds__(256) void psroi_loss_kernel(const float* score, con
           const int ch = by * K + bx;
           const float logit = sc[ch];
           // GT mask down-sampled by exact st-x legacy bilinear == [::st, ::st] (:773-775)
-          const float gt = true_masks[(((size_t)b * G + o[2 * K + 2]) * S + st * y) * S + st * x] ? 1.f : 0.f;
+          const float gt = true_masks[(((size_t)b * G + o[2 * K + 2]) * SH + st * y) * SW + st * x] ? 1.f : 0.f;
           const float inv_area = 1.f / (float)o[2 * K + 3];
           lsum[r] = sigmoid_ce(gt, logit) * inv_area;
           const float dv = (sigmoidf_(logit) - gt) * inv_area * coef0;
@@ -587,22 +589,25 @@ __global__ void psroi_loss_final_kernel(const float* img_loss, int B, float* los
 
 }  // namespace
 
-extern "C" size_t disyolo_yolo_loss_workspace(int B, int S, int num_class) {
-  if (B <= 0 || S <= 0 || S % 32) return 0;
-  const int g1 = S / 32;
+extern "C" size_t disyolo_yolo_loss_workspace_hw(int B, int H, int W, int num_class) {
+  if (B <= 0 || H <= 0 || W <= 0 || H % 32 || W % 32) return 0;
+  const int h1 = H / 32, w1 = W / 32;
   size_t blocks = 0;
-  for (int m = 1; m <= 4; m *= 2) blocks += (size_t)ceil_div((size_t)(m * g1) * (m * g1) * 3, 256) * B;
+  for (int m = 1; m <= 4; m *= 2) blocks += (size_t)ceil_div((size_t)(m * h1) * (m * w1) * 3, 256) * B;
   return blocks * 5 * sizeof(float);
+}
+
+extern "C" size_t disyolo_yolo_loss_workspace(int B, int S, int num_class) {
+  return disyolo_yolo_loss_workspace_hw(B, S, S, num_class);
 }
 
 // the launch both entry points share: ld = 0 is the 32-channel kernel of disyolo_yolo_loss, ld > 0 the wide one
 static int yolo_loss_launch(const float* const logits[3], const float* const labels[3], const float* true_boxes,
-                            int max_boxes, int B, int S, int num_class, int ld, const float* anchors_host,
+                            int max_boxes, int B, int H, int W, int num_class, int ld, const float* anchors_host,
                             float ignore_thresh, const float scales[4], void* const dlogits[3], float* losses,
                             void* workspace, void* stream) {
   hipStream_t st = (hipStream_t)stream;
-  const int g1 = S / 32;
-  const int gs[3] = {4 * g1, 2 * g1, g1};
+  const int ghs[3] = {H / 8, H / 16, H / 32}, gws[3] = {W / 8, W / 16, W / 32};
   float* part = (float*)workspace;
   int nblk[3];
   YoloLoss3 P;
@@ -614,7 +619,7 @@ static int yolo_loss_launch(const float* const logits[3], const float* const lab
     p.true_boxes = true_boxes;
     p.dlogits = (bf16*)dlogits[s];
     p.partial = part;
-    p.B = B; p.g = gs[s]; p.C = num_class; p.G = max_boxes; p.S = S;
+    p.B = B; p.gh = ghs[s]; p.gw = gws[s]; p.C = num_class; p.G = max_boxes; p.H = H; p.W = W;
     for (int a = 0; a < 3; ++a) {
       p.aw[a] = anchors_host[(3 * s + a) * 2 + 0];
       p.ah[a] = anchors_host[(3 * s + a) * 2 + 1];
@@ -622,7 +627,7 @@ static int yolo_loss_launch(const float* const logits[3], const float* const lab
     p.ignore_thresh = ignore_thresh;
     p.obj_scale = scales[0]; p.noobj_scale = scales[1]; p.class_scale = scales[2]; p.coord_scale = scales[3];
     p.inv_B = 1.f / (float)B;
-    P.gx[s] = ceil_div(gs[s] * gs[s] * 3, 256);
+    P.gx[s] = ceil_div(ghs[s] * gws[s] * 3, 256);
     nblk[s] = P.gx[s] * B;
     part += (size_t)nblk[s] * 5;
   }
@@ -660,7 +665,7 @@ extern "C" int disyolo_yolo_loss(const float* const logits[3], const float* cons
                                sc4.data(), dl.data(), losses, workspace, workspace_bytes, s);
     });
   }
-  return yolo_loss_launch(logits, labels, true_boxes, max_boxes, B, S, num_class, 0, anchors_host, ignore_thresh, scales,
+  return yolo_loss_launch(logits, labels, true_boxes, max_boxes, B, S, S, num_class, 0, anchors_host, ignore_thresh, scales,
                           dlogits, losses, workspace, stream);
 }
 
@@ -692,7 +697,44 @@ extern "C" int disyolo_yolo_loss_wide(const float* const logits[3], const float*
                                     ignore_thresh, sc4.data(), dl.data(), losses, workspace, workspace_bytes, s);
     });
   }
-  return yolo_loss_launch(logits, labels, true_boxes, max_boxes, B, S, num_class, dlogits_ld, anchors_host, ignore_thresh,
+  return yolo_loss_launch(logits, labels, true_boxes, max_boxes, B, S, S, num_class, dlogits_ld, anchors_host, ignore_thresh,
+                          scales, dlogits, losses, workspace, stream);
+}
+
+extern "C" int disyolo_yolo_loss_hw(const float* const logits[3], const float* const labels[3], const float* true_boxes,
+                                    int max_boxes, int B, int H, int W, int num_class, int dlogits_ld,
+                                    const float* anchors_host, float ignore_thresh, const float scales[4],
+                                    void* const dlogits[3], float* losses, void* workspace, size_t workspace_bytes,
+                                    void* stream) {
+  DY_REQUIRE(logits && labels && true_boxes && anchors_host && scales && dlogits && losses, "yolo_loss_hw: null pointer");
+  DY_REQUIRE(B > 0 && H > 0 && W > 0 && H % 32 == 0 && W % 32 == 0, "yolo_loss_hw: bad sizes (H = %d, W = %d)", H, W);
+  if (dlogits_ld == 0) {
+    DY_REQUIRE(num_class > 0 && 3 * (5 + num_class) <= DL_LD && num_class <= 11,
+               "yolo_loss_hw: bad sizes (dlogits_ld = 0 takes at most 5 classes, got %d)", num_class);
+  } else {
+    DY_REQUIRE(num_class >= 1 && num_class <= WL_MAXD - 5, "yolo_loss_hw: bad sizes (num_class must be in 1..80, got %d)",
+               num_class);
+    DY_REQUIRE(dlogits_ld % 32 == 0 && dlogits_ld >= 3 * (5 + num_class) && dlogits_ld <= 256,
+               "yolo_loss_hw: bad sizes (dlogits_ld must be 0 or a multiple of 32 in [3 (5 + num_class), 256], got %d)",
+               dlogits_ld);
+  }
+  DY_REQUIRE(max_boxes > 0 && max_boxes <= 64, "yolo_loss_hw: max_boxes must be in 1..64");
+  if (!workspace || workspace_bytes < disyolo_yolo_loss_workspace_hw(B, H, W, num_class)) {
+    disyolo_set_error("yolo_loss_hw: workspace too small");
+    return DISYOLO_E_WORKSPACE;
+  }
+  {
+    std::array<float, 18> anc;
+    for (int i = 0; i < 18; ++i) anc[i] = anchors_host[i];
+    std::array<float, 4> sc4 = {scales[0], scales[1], scales[2], scales[3]};
+    std::array<const float*, 3> lg = {logits[0], logits[1], logits[2]}, lb = {labels[0], labels[1], labels[2]};
+    std::array<void*, 3> dl = {dlogits[0], dlogits[1], dlogits[2]};
+    DY_RECORD_OR_RUN([=](void* s) {
+      return disyolo_yolo_loss_hw(lg.data(), lb.data(), true_boxes, max_boxes, B, H, W, num_class, dlogits_ld, anc.data(),
+                                  ignore_thresh, sc4.data(), dl.data(), losses, workspace, workspace_bytes, s);
+    });
+  }
+  return yolo_loss_launch(logits, labels, true_boxes, max_boxes, B, H, W, num_class, dlogits_ld, anchors_host, ignore_thresh,
                           scales, dlogits, losses, workspace, stream);
 }
 
@@ -712,17 +754,25 @@ static bool kmap_supported(int k) { return k == 3 || k == 5 || k == 7; }
 extern "C" int disyolo_mask_rois_k(const float* detections, int max_det, const float* true_boxes, int G,
                                    const int32_t* perm_det, const int32_t* perm_gt, int B, int map_size, int k, int n_det,
                                    int n_gt, float iou_thresh, int32_t* rois, int32_t* roi_count, void* stream) {
+  return disyolo_mask_rois_hw(detections, max_det, true_boxes, G, perm_det, perm_gt, B, map_size, map_size, k, n_det, n_gt,
+                              iou_thresh, rois, roi_count, stream);
+}
+
+extern "C" int disyolo_mask_rois_hw(const float* detections, int max_det, const float* true_boxes, int G,
+                                    const int32_t* perm_det, const int32_t* perm_gt, int B, int map_h, int map_w, int k,
+                                    int n_det, int n_gt, float iou_thresh, int32_t* rois, int32_t* roi_count,
+                                    void* stream) {
   DY_REQUIRE(detections && true_boxes && rois && roi_count, "mask_rois: null pointer");
   DY_REQUIRE(kmap_supported(k), "mask_rois: k must be one of k = 3, 5, 7 (got %d)", k);
-  DY_REQUIRE(B > 0 && max_det > 0 && max_det <= 64 && G > 0 && G <= 64 && map_size > 0, "mask_rois: bad sizes");
+  DY_REQUIRE(B > 0 && max_det > 0 && max_det <= 64 && G > 0 && G <= 64 && map_h > 0 && map_w > 0, "mask_rois: bad sizes");
   DY_REQUIRE(n_det >= 0 && n_gt >= 0 && n_det + n_gt <= ROI_MAX, "mask_rois: n_det + n_gt > %d", ROI_MAX);
   DY_RECORD_OR_RUN([=](void* s) {
-    return disyolo_mask_rois_k(detections, max_det, true_boxes, G, perm_det, perm_gt, B, map_size, k, n_det, n_gt,
-                               iou_thresh, rois, roi_count, s);
+    return disyolo_mask_rois_hw(detections, max_det, true_boxes, G, perm_det, perm_gt, B, map_h, map_w, k, n_det, n_gt,
+                                iou_thresh, rois, roi_count, s);
   });
   auto kern = k == 3 ? mask_rois_kernel<3> : k == 5 ? mask_rois_kernel<5> : mask_rois_kernel<7>;
   hipLaunchKernelGGL(kern, dim3(B), dim3(64), 0, (hipStream_t)stream, detections, max_det, true_boxes, G, perm_det,
-                     perm_gt, B, map_size, n_det, n_gt, iou_thresh, rois, roi_count);
+                     perm_gt, B, map_h, map_w, n_det, n_gt, iou_thresh, rois, roi_count);
   DY_CHECK_LAUNCH();
   return DISYOLO_OK;
 }
@@ -734,9 +784,13 @@ extern "C" int disyolo_mask_rois(const float* detections, int max_det, const flo
                              iou_thresh, rois, roi_count, stream);
 }
 
+extern "C" size_t disyolo_psroi_loss_workspace_hw(int B, int map_h, int map_w) {
+  if (B <= 0 || map_h <= 0 || map_w <= 0) return 0;
+  return ((size_t)B * ceil_div((size_t)map_h * map_w, 256) * ROI_MAX + B) * sizeof(float);
+}
+
 extern "C" size_t disyolo_psroi_loss_workspace(int B, int map_size) {
-  if (B <= 0 || map_size <= 0) return 0;
-  return ((size_t)B * ceil_div((size_t)map_size * map_size, 256) * ROI_MAX + B) * sizeof(float);
+  return disyolo_psroi_loss_workspace_hw(B, map_size, map_size);
 }
 
 extern "C" int disyolo_psroi_loss(const float* score, const uint8_t* true_masks, int G, const int32_t* rois,
@@ -750,23 +804,31 @@ extern "C" int disyolo_psroi_loss_s(const float* score, const uint8_t* true_mask
                                     const int32_t* roi_count, int B, int map_size, int mask_stride, int k,
                                     float mask_scale, void* dscore, float* loss, void* workspace,
                                     size_t workspace_bytes, void* stream) {
+  return disyolo_psroi_loss_hw(score, true_masks, G, rois, roi_count, B, map_size, map_size, mask_stride, k, mask_scale,
+                               dscore, loss, workspace, workspace_bytes, stream);
+}
+
+extern "C" int disyolo_psroi_loss_hw(const float* score, const uint8_t* true_masks, int G, const int32_t* rois,
+                                     const int32_t* roi_count, int B, int map_h, int map_w, int mask_stride, int k,
+                                     float mask_scale, void* dscore, float* loss, void* workspace,
+                                     size_t workspace_bytes, void* stream) {
   DY_REQUIRE(score && true_masks && rois && roi_count && dscore && loss, "psroi_loss: null pointer");
-  DY_REQUIRE(B > 0 && map_size > 0 && G > 0, "psroi_loss: bad sizes");
+  DY_REQUIRE(B > 0 && map_h > 0 && map_w > 0 && (int64_t)map_h * map_w <= (1ll << 30) && G > 0, "psroi_loss: bad sizes");
   DY_REQUIRE(kmap_supported(k), "psroi_loss: k must be one of k = 3, 5, 7 (got %d)", k);
   DY_REQUIRE(mask_stride == 1 || mask_stride == 2 || mask_stride == 4,
              "psroi_loss: mask_stride must be one of 1, 2, 4 (got %d)", mask_stride);
-  if (!workspace || workspace_bytes < disyolo_psroi_loss_workspace(B, map_size)) {
+  if (!workspace || workspace_bytes < disyolo_psroi_loss_workspace_hw(B, map_h, map_w)) {
     disyolo_set_error("psroi_loss: workspace too small");
     return DISYOLO_E_WORKSPACE;
   }
   DY_RECORD_OR_RUN([=](void* s) {
-    return disyolo_psroi_loss_s(score, true_masks, G, rois, roi_count, B, map_size, mask_stride, k, mask_scale, dscore,
-                                loss, workspace, workspace_bytes, s);
+    return disyolo_psroi_loss_hw(score, true_masks, G, rois, roi_count, B, map_h, map_w, mask_stride, k, mask_scale, dscore,
+                                 loss, workspace, workspace_bytes, s);
   });
   hipStream_t st = (hipStream_t)stream;
-  const int nblk = ceil_div((size_t)map_size * map_size, 256);
+  const int nblk = ceil_div((size_t)map_h * map_w, 256);
   auto kern = k == 3 ? psroi_loss_kernel<3> : k == 5 ? psroi_loss_kernel<5> : psroi_loss_kernel<7>;
-  hipLaunchKernelGGL(kern, dim3(nblk, B), dim3(256), 0, st, score, true_masks, G, rois, roi_count, B, map_size,
+  hipLaunchKernelGGL(kern, dim3(nblk, B), dim3(256), 0, st, score, true_masks, G, rois, roi_count, B, map_h, map_w,
                      mask_stride, mask_scale, (bf16*)dscore, (float*)workspace);
   DY_CHECK_LAUNCH();
   float* img_loss = (float*)workspace + (size_t)B * nblk * ROI_MAX;

@@ -22,16 +22,17 @@ from .postprocess import SegmentationAccuracy, correct_yolo_boxes, paste_detecti
 from .voc_eval import voc_eval
 
 
-def image_read(image_rgb, image_size: int, device=None, out: Optional[torch.Tensor] = None):
+def image_read(image_rgb, image_size, device=None, out: Optional[torch.Tensor] = None):
     """calculate_test_map.py:149-176: RGB uint8 [H,W,3] (numpy or CUDA tensor) -> (letter-boxed image f32
-    CUDA [S,S,3] in [0,1], clip window f32 [4] = top, left, bottom, right)."""
+    CUDA [net_h,net_w,3] in [0,1], clip window f32 [4] = top, left, bottom, right).  ``image_size``: the net's size, an int
+    or (net_h, net_w)."""
     if not torch.is_tensor(image_rgb):
         image_rgb = torch.from_numpy(np.ascontiguousarray(image_rgb))
     if device is None:
         device = image_rgb.device if image_rgb.is_cuda else torch.device("cuda", torch.cuda.current_device())
     rgb = image_rgb.to(device, torch.uint8).contiguous()
     if out is None:
-        out = torch.empty(image_size, image_size, 3, dtype=torch.float32, device=device)
+        out = torch.empty(*L.hw_of(image_size), 3, dtype=torch.float32, device=device)
     window = L.letterbox(rgb, out, image_size)
     return out, window
 
@@ -50,10 +51,11 @@ class MAP(object):
       recs_mask: image id -> [{'imageid', 'classid', 'difficult', 'mask' bool [H,W]}]
       sizes:     image id -> [image_h, image_w]
       merged:    image id -> uint8 [H,W] class map (0 background, classid + 1), for mIoU; optional
-      index:     list of image ids in evaluation order."""
+      index:     list of image ids in evaluation order.
+    ``net_size``: the size of the net whose detections are collected, an int or (H, W)."""
 
     def __init__(self, recs_mask: Dict[str, List[Dict]], sizes: Dict[str, Sequence[int]], index: Sequence[str],
-                 merged: Optional[Dict[str, np.ndarray]] = None, net_size: int = cfg.TEST_SIZE,
+                 merged: Optional[Dict[str, np.ndarray]] = None, net_size=cfg.TEST_SIZE,
                  classes: Optional[Sequence[str]] = None):
         from .net import check_classes
         self.classes = check_classes(cfg.CLASSES if classes is None else classes)
@@ -173,7 +175,7 @@ class MAP(object):
                       detfile: Dict[str, List[Dict]], true_maps: Optional[Sequence] = None,
                       conf: Optional[torch.Tensor] = None) -> List[torch.Tensor]:
         """``collect`` for a batch, on the device-resident outputs of ``YOLONet.evaluation_device`` / ``infer``: detections
-        [B,max_det,6], keep [B,max_det], masks [B,max_det,Sm,Sm]; ``imageids`` names the first len(imageids) <= B images
+        [B,max_det,6], keep [B,max_det], masks [B,max_det,Hm,Wm]; ``imageids`` names the first len(imageids) <= B images
         (a short last batch leaves the other rows unused).  Per batch: one fetch of detections + keep, the job table on the
         host, one upload (jobs, rects, class ids), ONE launch (disyolo_mask_paste_iou_batch: merged maps, pixel counts,
         intersections and -- with ``true_maps`` (one uint8 [H,W] class map per image) and ``conf`` (int64 [16] on the GPU, e.g.
@@ -203,7 +205,8 @@ class MAP(object):
                     self._add_confusion(self._true_map(imageid, true_maps[b], dev), merged, conf)
                 out.append(merged)
             return out
-        size = int(masks.shape[-1])
+        map_h, map_w = int(masks.shape[-2]), int(masks.shape[-1])
+        size = (map_h, map_w)
         masks = masks.contiguous()
         # the paste's own confusion counts are the 4x4 table of 3 classes; any other class list counts after the launch
         fused_conf = self.num_class == 3
@@ -240,7 +243,7 @@ class MAP(object):
             pix0 += image_h * image_w
             out.append(merged)
             j = jobs[b]
-            j["masks"] = masks.data_ptr() + b * max_det * size * size * 4
+            j["masks"] = masks.data_ptr() + b * max_det * map_h * map_w * 4
             j["rects"] = dbuf.data_ptr() + off_rects + b * max_det * 32
             j["classids"] = dbuf.data_ptr() + off_cls + b * max_det * 4
             j["gt"], j["gt_class"] = (0, 0) if gt is None else (gt.data_ptr(), gt_cls.data_ptr())
@@ -308,7 +311,7 @@ def evaluate(net, images: Dict[str, np.ndarray], eval_map: MAP, det_thresh: floa
     if weights_file is not None:
         from .checkpoint import restore_net
         restore_net(net, weights_file)                       # saver.restore (:184-185)
-    S, B = net.S, net.B
+    S, B = (net.H, net.W), net.B
     if (not net.training and getattr(net, "_infer_prog", None) is None and os.environ.get("DISYOLO_EVAL_REPLAY", "1") != "0"):
         # an inference net: record forward + detection filter + mask assembly once for this threshold (a hipGraph of one lane);
         # every image is then one replay (YOLONet.evaluation uses the recording when the threshold matches)
@@ -321,7 +324,7 @@ def evaluate(net, images: Dict[str, np.ndarray], eval_map: MAP, det_thresh: floa
     if B > 1:
         t_pred, t_crop = _evaluate_batches(net, images, eval_map, det_thresh, detfile, seg)
         return _evaluate_result(eval_map, detfile, seg, t_pred, t_crop)
-    frame = torch.empty(1, S, S, 3, dtype=torch.float32, device=net.device)
+    frame = torch.empty(1, S[0], S[1], 3, dtype=torch.float32, device=net.device)
     for index in eval_map.index:
         src = images[index]
         rgb = load_image_rgb(src) if isinstance(src, str) else np.asarray(src)
@@ -356,9 +359,9 @@ def _evaluate_batches(net, images, eval_map: MAP, det_thresh: float, detfile, se
     """evaluate()'s loop for a net of batch size B > 1: B letter boxes into one frame, one pass of the net, one
     ``MAP.collect_batch``; the last batch may hold fewer images -- the frames (and clip windows) of the batch before stay in the
     unused rows, and only the real images get a job.  Returns (prediction seconds, crop + assemble seconds)."""
-    S, B = net.S, net.B
+    S, B = (net.H, net.W), net.B
     t_pred = t_crop = 0.0
-    frame = torch.zeros(B, S, S, 3, dtype=torch.float32, device=net.device)
+    frame = torch.zeros(B, S[0], S[1], 3, dtype=torch.float32, device=net.device)
     windows = np.tile(np.array([0.0, 0.0, 1.0, 1.0], np.float32), (B, 1))
     for a in range(0, len(eval_map.index), B):
         ids = eval_map.index[a:a + B]

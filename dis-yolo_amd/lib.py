@@ -131,7 +131,13 @@ _SIGS = {
     "disyolo_detect_workspace": (C.c_size_t, [C.c_int] * 3),
     "disyolo_detect": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 3 + [C.c_void_p] * 2 + [C.c_float, C.c_float, C.c_int] +
                        [C.c_void_p] * 3 + [C.c_size_t, C.c_void_p]),
+    "disyolo_detect_workspace_hw": (C.c_size_t, [C.c_int] * 4),
+    "disyolo_detect_hw": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 4 + [C.c_void_p] * 2 + [C.c_float, C.c_float, C.c_int] +
+                          [C.c_void_p] * 3 + [C.c_size_t, C.c_void_p]),
     "disyolo_yolo_loss_workspace": (C.c_size_t, [C.c_int] * 3),
+    "disyolo_yolo_loss_workspace_hw": (C.c_size_t, [C.c_int] * 4),
+    "disyolo_yolo_loss_hw": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p, C.c_float] +
+                             [C.c_void_p] * 4 + [C.c_size_t, C.c_void_p]),
     "disyolo_yolo_loss": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p, C.c_float] +
                           [C.c_void_p] * 4 + [C.c_size_t, C.c_void_p]),
     "disyolo_yolo_loss_wide": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p, C.c_float] +
@@ -141,7 +147,13 @@ _SIGS = {
                           [C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
     "disyolo_mask_rois_k": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p] + [C.c_int] * 5 +
                             [C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "disyolo_mask_rois_hw": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p] + [C.c_int] * 6 +
+                             [C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
     "disyolo_psroi_loss_workspace": (C.c_size_t, [C.c_int, C.c_int]),
+    "disyolo_psroi_loss_workspace_hw": (C.c_size_t, [C.c_int] * 3),
+    "disyolo_psroi_loss_hw": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p] + [C.c_int] * 5 +
+                              [C.c_float] + [C.c_void_p] * 3 + [C.c_size_t, C.c_void_p]),
+    "disyolo_psroi_assemble_hw": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p] * 3),
     "disyolo_psroi_loss": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p] + [C.c_int] * 3 +
                            [C.c_float] + [C.c_void_p] * 3 + [C.c_size_t, C.c_void_p]),
     "disyolo_psroi_loss_s": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p] + [C.c_int] * 4 +
@@ -149,12 +161,16 @@ _SIGS = {
     "disyolo_psroi_assemble": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] * 3),
     "disyolo_mask_paste": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
                                      C.c_void_p, C.c_void_p]),
+    "disyolo_mask_paste_hw": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                        C.c_void_p, C.c_void_p, C.c_void_p]),
     "disyolo_letterbox": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "disyolo_letterbox_hw": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "disyolo_confusion16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "disyolo_confusion_n": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p]),
     "disyolo_paste_job_size": (C.c_size_t, []),
     "disyolo_paste_job_plan": (C.c_int, [C.c_void_p, C.c_int]),
     "disyolo_mask_paste_iou_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "disyolo_mask_paste_iou_batch_hw": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "disyolo_adam_step": (C.c_int, [C.c_void_p] * 4 + [C.c_int64, C.c_int64] + [C.c_float] * 5 + [C.c_int64, C.c_float,
                                                                                              C.c_void_p]),
     "disyolo_adam_step_dev": (C.c_int, [C.c_void_p] * 4 + [C.c_int64, C.c_int64] + [C.c_float] * 5 + [C.c_void_p, C.c_float,
@@ -201,6 +217,11 @@ _SIGS = {
     "disyolo_aug_salt_pepper": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "disyolo_aug_change_light": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_void_p]),
     "disyolo_aug_motion_blur3": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "disyolo_aug_place_hw": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p] + [C.c_int] * 7 + [C.c_void_p]),
+    "disyolo_aug_place_batch_hw": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "disyolo_aug_salt_pepper_hw": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "disyolo_aug_change_light_hw": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_void_p]),
+    "disyolo_aug_motion_blur3_hw": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "disyolo_aug_to_float": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "disyolo_crc32c": (C.c_uint32, [C.c_void_p, C.c_size_t, C.c_uint32]),
     "disyolo_l2_workspace": (C.c_size_t, [C.c_int64]),
@@ -906,14 +927,15 @@ def bn_frozen_bwd(dy, x, scale, shift, dx, rows, C_, alpha=0.1, shortcut_grad=No
 
 
 def mask_paste(masks, rects, classids, image_h: int, image_w: int, full_masks, merged) -> None:
-    """masks f32 [n,S,S]; rects int32 [n,8]; classids int32 [n]; full_masks uint8 [n,H,W] or None; merged uint8 [H,W]"""
+    """masks f32 [n,Hm,Wm]; rects int32 [n,8]; classids int32 [n]; full_masks uint8 [n,H,W] or None; merged uint8 [H,W]"""
     n = int(rects.shape[0])
     if n:
         _need(masks, torch.float32, "masks")
         _need(rects, torch.int32, "rects")
         _need(classids, torch.int32, "classids")
-    _check(load().disyolo_mask_paste(_p(masks) if n else None, n, int(masks.shape[-1]) if n else 1, _p(rects) if n else None,
-                                     _p(classids) if n else None, image_h, image_w, _p(full_masks), _p(merged), _stream()),
+    mh, mw = (int(masks.shape[-2]), int(masks.shape[-1])) if n else (1, 1)
+    _check(load().disyolo_mask_paste_hw(_p(masks) if n else None, n, mh, mw, _p(rects) if n else None,
+                                        _p(classids) if n else None, image_h, image_w, _p(full_masks), _p(merged), _stream()),
            "mask_paste")
 
 
@@ -933,9 +955,10 @@ def paste_job_plan(jobs) -> int:
     return rc
 
 
-def mask_paste_iou_batch(jobs, jobs_dev, size: int, conf=None) -> None:
+def mask_paste_iou_batch(jobs, jobs_dev, size, conf=None) -> None:
     """jobs: the planned PASTE_JOB records on the host; jobs_dev: a uint8 CUDA tensor that starts with the same bytes (uploaded by
-    the caller on this stream); conf: int64 [16] CUDA or None.  One launch for all jobs (disyolo_mask_paste_iou_batch)."""
+    the caller on this stream); size: the masks' size, an int or (Hm, Wm); conf: int64 [16] CUDA or None.  One launch for all
+    jobs (disyolo_mask_paste_iou_batch_hw)."""
     if jobs.dtype != PASTE_JOB or not jobs.flags["C_CONTIGUOUS"] or jobs.ndim != 1:
         raise DisyoloError("mask_paste_iou_batch: jobs must be a contiguous 1-d array of PASTE_JOB records")
     _need(jobs_dev, torch.uint8, "jobs_dev")
@@ -944,20 +967,23 @@ def mask_paste_iou_batch(jobs, jobs_dev, size: int, conf=None) -> None:
     if conf is not None:
         _need(conf, torch.int64, "conf")
         _need_shape(conf, (16,), "conf")
-    _check(load().disyolo_mask_paste_iou_batch(jobs.ctypes.data, _p(jobs_dev), int(jobs.shape[0]), int(size), _p(conf), _stream()),
-           "mask_paste_iou_batch")
+    mh, mw = hw_of(size)
+    _check(load().disyolo_mask_paste_iou_batch_hw(jobs.ctypes.data, _p(jobs_dev), int(jobs.shape[0]), mh, mw, _p(conf),
+                                                  _stream()), "mask_paste_iou_batch")
 
 
-def letterbox(rgb_u8, out, size: int):
-    """rgb_u8 uint8 CUDA [H,W,3] -> out f32 CUDA [size,size,3]; returns the clip window (numpy f32 [4])"""
+def letterbox(rgb_u8, out, size):
+    """rgb_u8 uint8 CUDA [H,W,3] -> out f32 CUDA [net_h,net_w,3] (``size``: an int, or (net_h, net_w)); returns the clip
+    window (numpy f32 [4])"""
     import numpy as np
     _need(rgb_u8, torch.uint8, "rgb")
     _need(out, torch.float32, "out")
-    if rgb_u8.dim() != 3 or rgb_u8.shape[2] != 3 or tuple(out.shape) != (size, size, 3):
-        raise DisyoloError("letterbox: rgb must be [H,W,3] uint8 and out [size,size,3] f32")
+    nh, nw = hw_of(size)
+    if rgb_u8.dim() != 3 or rgb_u8.shape[2] != 3 or tuple(out.shape) != (nh, nw, 3):
+        raise DisyoloError("letterbox: rgb must be [H,W,3] uint8 and out [size,size,3] f32 ([net_h,net_w,3] for a pair)")
     win = (C.c_float * 4)()
-    _check(load().disyolo_letterbox(_p(rgb_u8), int(rgb_u8.shape[0]), int(rgb_u8.shape[1]), _p(out), size, win, _stream()),
-           "letterbox")
+    _check(load().disyolo_letterbox_hw(_p(rgb_u8), int(rgb_u8.shape[0]), int(rgb_u8.shape[1]), _p(out), nh, nw, win,
+                                       _stream()), "letterbox")
     return np.array(list(win), np.float32)
 
 
@@ -972,11 +998,15 @@ def polygon_mask(px, py, poly_start, poly_is_out, image_h: int, image_w: int, ma
                                        image_w, _p(mask), _stream()), "polygon_mask")
 
 
-def aug_place(src, is_mask: bool, dst, size: int, new_w: int, new_h: int, dx: int, dy: int, flip: int) -> None:
+def aug_place(src, is_mask: bool, dst, size, new_w: int, new_h: int, dx: int, dy: int, flip: int) -> None:
+    """``size`` (here and in the four functions below): the frame's size, an int or (net_h, net_w)"""
     _need(src, torch.uint8, "src")
     _need(dst, torch.uint8, "dst")
-    _check(load().disyolo_aug_place(_p(src), int(is_mask), int(src.shape[0]), int(src.shape[1]), _p(dst), size, new_w, new_h,
-                                    dx, dy, flip, _stream()), "aug_place")
+    nh, nw = hw_of(size)
+    if tuple(dst.shape[:2]) != (nh, nw):
+        raise DisyoloError("aug_place: dst must be [%d,%d(,3)] (got %s)" % (nh, nw, tuple(dst.shape)))
+    _check(load().disyolo_aug_place_hw(_p(src), int(is_mask), int(src.shape[0]), int(src.shape[1]), _p(dst), nh, nw, new_w,
+                                       new_h, dx, dy, flip, _stream()), "aug_place")
 
 
 PLACE_JOB = np.dtype([("src", np.uint64), ("dst", np.uint64), ("is_mask", np.int32), ("image_h", np.int32), ("image_w", np.int32),
@@ -984,24 +1014,28 @@ PLACE_JOB = np.dtype([("src", np.uint64), ("dst", np.uint64), ("is_mask", np.int
 assert PLACE_JOB.itemsize == 48      # (disyolo_place_job, include/disyolo.h)
 
 
-def aug_place_batch(jobs_dev, njobs: int, size: int) -> None:
+def aug_place_batch(jobs_dev, njobs: int, size) -> None:
     """jobs_dev: uint8 CUDA tensor holding njobs PLACE_JOB records (uploaded by the caller on this stream)"""
     _need(jobs_dev, torch.uint8, "jobs")
     if jobs_dev.numel() < njobs * PLACE_JOB.itemsize:
         raise DisyoloError("aug_place_batch: %d jobs do not fit %d bytes" % (njobs, jobs_dev.numel()))
-    _check(load().disyolo_aug_place_batch(_p(jobs_dev), njobs, size, _stream()), "aug_place_batch")
+    nh, nw = hw_of(size)
+    _check(load().disyolo_aug_place_batch_hw(_p(jobs_dev), njobs, nh, nw, _stream()), "aug_place_batch")
 
 
-def aug_salt_pepper(image, size: int, rows, cols, nsalt: int, npepper: int) -> None:
-    _check(load().disyolo_aug_salt_pepper(_p(image), size, _p(rows), _p(cols), nsalt, npepper, _stream()), "aug_salt_pepper")
+def aug_salt_pepper(image, size, rows, cols, nsalt: int, npepper: int) -> None:
+    nh, nw = hw_of(size)
+    _check(load().disyolo_aug_salt_pepper_hw(_p(image), nh, nw, _p(rows), _p(cols), nsalt, npepper, _stream()), "aug_salt_pepper")
 
 
-def aug_change_light(image, size: int, coeff: float) -> None:
-    _check(load().disyolo_aug_change_light(_p(image), size, float(coeff), _stream()), "aug_change_light")
+def aug_change_light(image, size, coeff: float) -> None:
+    nh, nw = hw_of(size)
+    _check(load().disyolo_aug_change_light_hw(_p(image), nh, nw, float(coeff), _stream()), "aug_change_light")
 
 
-def aug_motion_blur3(src, dst, size: int, angle: int, line_type: int) -> None:
-    _check(load().disyolo_aug_motion_blur3(_p(src), _p(dst), size, angle, line_type, _stream()), "aug_motion_blur3")
+def aug_motion_blur3(src, dst, size, angle: int, line_type: int) -> None:
+    nh, nw = hw_of(size)
+    _check(load().disyolo_aug_motion_blur3_hw(_p(src), _p(dst), nh, nw, angle, line_type, _stream()), "aug_motion_blur3")
 
 
 def aug_to_float(image, out) -> None:
@@ -1041,41 +1075,61 @@ def colsum(x, out, rows, C_, out_C, ws: Workspace) -> None:
     _check(load().disyolo_colsum(_p(x), _p(out), rows, C_, out_C, _p(buf), buf.numel(), _stream()), "colsum")
 
 
+def hw_of(size):
+    """(H, W) of a size given as one int (a square) or as a pair"""
+    if isinstance(size, (int, np.integer)):
+        return int(size), int(size)
+    h, w = size
+    return int(h), int(w)
+
+
+def detect_workspace(B, S, num_class) -> int:
+    H, W = hw_of(S)
+    return load().disyolo_detect_workspace_hw(B, H, W, num_class)
+
+
 def detect(logits3, logits2, logits1, B, S, num_class, anchors_host, clip_window, obj_thresh, nms_thresh, max_det,
            detections, det_count, ws: Workspace) -> None:
-    need = load().disyolo_detect_workspace(B, S, num_class)
+    """``S``: the net's input size, an int or (H, W)"""
+    H, W = hw_of(S)
+    need = load().disyolo_detect_workspace_hw(B, H, W, num_class)
     buf = ws.get(need)
     anc = (C.c_float * 18)(*[float(v) for v in anchors_host])
-    _check(load().disyolo_detect(_p(logits3), _p(logits2), _p(logits1), B, S, num_class, anc, _p(clip_window),
-                                 obj_thresh, nms_thresh, max_det, _p(detections), _p(det_count), _p(buf), buf.numel(),
-                                 _stream()), "detect")
+    _check(load().disyolo_detect_hw(_p(logits3), _p(logits2), _p(logits1), B, H, W, num_class, anc, _p(clip_window),
+                                    obj_thresh, nms_thresh, max_det, _p(detections), _p(det_count), _p(buf), buf.numel(),
+                                    _stream()), "detect")
 
 
 def yolo_loss(logits, labels, true_boxes, max_boxes, B, S, num_class, anchors_host, ignore_thresh, scales, dlogits,
               losses, ws: Workspace) -> None:
-    need = load().disyolo_yolo_loss_workspace(B, S, num_class)
+    """``S``: the net's input size, an int or (H, W)"""
+    H, W = hw_of(S)
+    need = load().disyolo_yolo_loss_workspace_hw(B, H, W, num_class)
     buf = ws.get(need)
     anc = (C.c_float * 18)(*[float(v) for v in anchors_host])
     lg = (C.c_void_p * 3)(*[_p(t) for t in logits])
     lb = (C.c_void_p * 3)(*[_p(t) for t in labels])
     dl = (C.c_void_p * 3)(*[_p(t) for t in dlogits])
     sc = (C.c_float * 4)(*[float(v) for v in scales])
-    _check(load().disyolo_yolo_loss(lg, lb, _p(true_boxes), max_boxes, B, S, num_class, anc, ignore_thresh, sc, dl,
-                                    _p(losses), _p(buf), buf.numel(), _stream()), "yolo_loss")
+    _check(load().disyolo_yolo_loss_hw(lg, lb, _p(true_boxes), max_boxes, B, H, W, num_class, 0, anc, ignore_thresh, sc, dl,
+                                       _p(losses), _p(buf), buf.numel(), _stream()), "yolo_loss")
 
 
 def yolo_loss_wide(logits, labels, true_boxes, max_boxes, B, S, num_class, dlogits_ld, anchors_host, ignore_thresh, scales,
                    dlogits, losses, ws: Workspace) -> None:
-    """yolo_loss for rows past 32 channels: dlogits bf16 [B, g, g, dlogits_ld] per scale"""
-    need = load().disyolo_yolo_loss_workspace(B, S, num_class)
+    """yolo_loss for rows past 32 channels: dlogits bf16 [B, gh, gw, dlogits_ld] per scale"""
+    if not dlogits_ld:
+        raise DisyoloError("yolo_loss_wide: dlogits_ld must be a positive multiple of 32")
+    H, W = hw_of(S)
+    need = load().disyolo_yolo_loss_workspace_hw(B, H, W, num_class)
     buf = ws.get(need)
     anc = (C.c_float * 18)(*[float(v) for v in anchors_host])
     lg = (C.c_void_p * 3)(*[_p(t) for t in logits])
     lb = (C.c_void_p * 3)(*[_p(t) for t in labels])
     dl = (C.c_void_p * 3)(*[_p(t) for t in dlogits])
     sc = (C.c_float * 4)(*[float(v) for v in scales])
-    _check(load().disyolo_yolo_loss_wide(lg, lb, _p(true_boxes), max_boxes, B, S, num_class, dlogits_ld, anc, ignore_thresh,
-                                         sc, dl, _p(losses), _p(buf), buf.numel(), _stream()), "yolo_loss_wide")
+    _check(load().disyolo_yolo_loss_hw(lg, lb, _p(true_boxes), max_boxes, B, H, W, num_class, dlogits_ld, anc, ignore_thresh,
+                                       sc, dl, _p(losses), _p(buf), buf.numel(), _stream()), "yolo_loss_wide")
 
 
 def shuffle_perm(perm_det, perm_gt, B, seed, step_counter) -> None:
@@ -1085,24 +1139,28 @@ def shuffle_perm(perm_det, perm_gt, B, seed, step_counter) -> None:
 
 def mask_rois(detections, max_det, true_boxes, G, perm_det, perm_gt, B, map_size, n_det, n_gt, iou_thresh, rois,
               roi_count, k: int = 3) -> None:
-    """rois int32 [B, ROI_MAX, roi_w(k)]"""
+    """rois int32 [B, ROI_MAX, roi_w(k)]; ``map_size``: the score map's size, an int or (Hm, Wm)"""
     _need_shape(rois, (B, ROI_MAX, roi_w(k)), "mask_rois: rois")
-    _check(load().disyolo_mask_rois_k(_p(detections), max_det, _p(true_boxes), G, _p(perm_det), _p(perm_gt), B, map_size,
-                                      k, n_det, n_gt, iou_thresh, _p(rois), _p(roi_count), _stream()), "mask_rois")
+    Hm, Wm = hw_of(map_size)
+    _check(load().disyolo_mask_rois_hw(_p(detections), max_det, _p(true_boxes), G, _p(perm_det), _p(perm_gt), B, Hm, Wm,
+                                       k, n_det, n_gt, iou_thresh, _p(rois), _p(roi_count), _stream()), "mask_rois")
 
 
 def psroi_loss(score, true_masks, G, rois, roi_count, B, map_size, k, mask_scale, dscore, loss, ws: Workspace,
                mask_stride: int = 2) -> None:
-    """true_masks uint8 [B, G, mask_stride * map_size, mask_stride * map_size], sampled at [::mask_stride, ::mask_stride]"""
-    need = load().disyolo_psroi_loss_workspace(B, map_size)
+    """true_masks uint8 [B, G, mask_stride * Hm, mask_stride * Wm], sampled at [::mask_stride, ::mask_stride];
+    ``map_size``: the score map's size, an int or (Hm, Wm)"""
+    Hm, Wm = hw_of(map_size)
+    need = load().disyolo_psroi_loss_workspace_hw(B, Hm, Wm)
     buf = ws.get(need)
-    _check(load().disyolo_psroi_loss_s(_p(score), _p(true_masks), G, _p(rois), _p(roi_count), B, map_size, mask_stride, k,
-                                       mask_scale, _p(dscore), _p(loss), _p(buf), buf.numel(), _stream()), "psroi_loss")
+    _check(load().disyolo_psroi_loss_hw(_p(score), _p(true_masks), G, _p(rois), _p(roi_count), B, Hm, Wm, mask_stride, k,
+                                        mask_scale, _p(dscore), _p(loss), _p(buf), buf.numel(), _stream()), "psroi_loss")
 
 
 def psroi_assemble(score, detections, B, max_det, map_size, k, masks, keep) -> None:
-    _check(load().disyolo_psroi_assemble(_p(score), _p(detections), B, max_det, map_size, k, _p(masks), _p(keep),
-                                         _stream()), "psroi_assemble")
+    Hm, Wm = hw_of(map_size)
+    _check(load().disyolo_psroi_assemble_hw(_p(score), _p(detections), B, max_det, Hm, Wm, k, _p(masks), _p(keep),
+                                            _stream()), "psroi_assemble")
 
 
 def adam_step(w, grad, m, v, n, n_decay, lr, b1, b2, eps, l2, t, grad_scale=1.0) -> None:

@@ -159,8 +159,25 @@ def check_classes(classes) -> List[str]:
     return names
 
 
+def check_image_size(image_size) -> Tuple[int, int]:
+    """(H, W) of an ``image_size`` given as one int S (a square net) or as a pair (H, W); each side a positive multiple of 32"""
+    if isinstance(image_size, (int, np.integer)) and not isinstance(image_size, bool):
+        sides = (int(image_size), int(image_size))
+    else:
+        try:
+            sides = tuple(image_size)
+        except TypeError:
+            raise ValueError("image_size must be an int or a pair (H, W) (got %r)" % (image_size,))
+        if len(sides) != 2 or any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) for v in sides):
+            raise ValueError("image_size must be an int or a pair of ints (H, W) (got %r)" % (image_size,))
+        sides = (int(sides[0]), int(sides[1]))
+    if any(v <= 0 or v % 32 for v in sides):
+        raise ValueError("image size must be a positive multiple of 32 on both sides (got H = %d, W = %d)" % sides)
+    return sides
+
+
 class YOLONet(object):
-    def __init__(self, training: bool = False, device=None, image_size: Optional[int] = None,
+    def __init__(self, training: bool = False, device=None, image_size=None,
                  batch_size: Optional[int] = None, stage: int = 1, lock: Optional[Dict[int, bool]] = None,
                  seed: int = 0, xavier_locked: bool = True, plan_only: bool = False, dtype: str = "bf16",
                  backbone_pair: bool = False, k_map: Optional[int] = None, mask_stride: Optional[int] = None,
@@ -198,9 +215,12 @@ class YOLONet(object):
             raise ValueError("dtype must be 'bf16' or 'fp8'")
         self.dtype = dtype
         self.fp8_ready = False
-        self.image_size = int(image_size if image_size is not None else cfg.IMAGE_SIZE)
-        if self.image_size % 32:
-            raise ValueError("image size must be a multiple of 32")
+        # image_size: an int S (the square net) or a pair (H, W).  H and W always exist; S and image_size stay ints on a
+        # square net, and on a rectangular one image_size == (H, W) and S is None -- a forgotten square assumption then
+        # fails loudly instead of computing with the wrong side
+        self.H, self.W = check_image_size(image_size if image_size is not None else cfg.IMAGE_SIZE)
+        self.S = self.H if self.H == self.W else None
+        self.image_size = self.S if self.S is not None else (self.H, self.W)
         # plan_only: variables, parameter arena and layer table only (any device, no kernel library) --
         # what checkpoint tools and the CPU tests of the data-parallel protocol need; it cannot compute
         self.plan_only = bool(plan_only)
@@ -284,8 +304,9 @@ class YOLONet(object):
             self._pair_P = self._backbone_prefix()
             if self._pair_P < 2:
                 raise L.DisyoloError("backbone_pair needs a locked layer prefix (stage 1)")
+        self._plan_sizes(self.H, self.W)
         if not self.plan_only:
-            self._plan(self.batchsize, self.image_size)
+            self._plan(self.batchsize, self.H, self.W)
 
     # ------------------------------------------------------------------ parameters
     def _init_params(self, seed: int, xavier_locked: bool) -> None:
@@ -425,20 +446,23 @@ class YOLONet(object):
             self.refresh_weights()
 
     # ------------------------------------------------------------------ static plan
-    def _plan(self, B: int, S: int) -> None:
-        """Allocate every activation / gradient buffer and build the conv descriptors once
-        for (B, S): nothing is allocated inside forward / train_step."""
-        dev = self.device
-        self.B, self.S = B, S
-        self.images = torch.zeros(2 * B if self.pair else B, S, S, 3, dtype=F32, device=dev)
-        spatial = {0: (S, S)}
-        # which activations need a gradient: any trainable layer at or upstream of a consumer
+    def _plan_sizes(self, H: int, W: int) -> None:
+        """every layer's input and output size and SAME pads for an H x W image (no device, no kernel library)"""
+        spatial = {0: (H, W)}
         for l in self.layers:
-            H, W = spatial[l.src]
-            l.H, l.W = H, W
-            l.Ho, l.pad_t = L.same_pads(H, l.k, l.stride)
-            l.Wo, l.pad_l = L.same_pads(W, l.k, l.stride)
+            l.H, l.W = spatial[l.src]
+            l.Ho, l.pad_t = L.same_pads(l.H, l.k, l.stride)
+            l.Wo, l.pad_l = L.same_pads(l.W, l.k, l.stride)
             spatial[l.idx] = (l.Ho, l.Wo)
+
+    def _plan(self, B: int, H: int, W: int) -> None:
+        """Allocate every activation / gradient buffer and build the conv descriptors once
+        for (B, H, W): nothing is allocated inside forward / train_step."""
+        dev = self.device
+        self.B = B
+        self.images = torch.zeros(2 * B if self.pair else B, H, W, 3, dtype=F32, device=dev)
+        self._plan_sizes(H, W)
+        # which activations need a gradient: any trainable layer at or upstream of a consumer
         has_trainable_upto = self._needs_grad_into       # (_mark_pass_through)
         # activation tensors are views into ONE allocation: a process that has allocated and freed a lot of
         # device memory gets later allocations on worse-mapped memory (B = 32 inference 4.8 -> 3.9 k img/s after
@@ -492,7 +516,7 @@ class YOLONet(object):
             self._plan_fp8()
         l1 = self.by_idx[1]
         if self.training and not l1.lock:
-            l1.stats_rows = L.colstats_rows(B * S * S, l1.cout)
+            l1.stats_rows = L.colstats_rows(B * H * W, l1.cout)
             l1.stats = torch.zeros(l1.stats_rows, l1.cout, 2, dtype=F32, device=dev)
             self._ones32 = torch.ones(l1.cout, dtype=F32, device=dev)
             self._zeros32 = torch.zeros(l1.cout, dtype=F32, device=dev)
@@ -504,11 +528,10 @@ class YOLONet(object):
         self.keep = torch.zeros(B, cfg.MAX_DETECTION, dtype=torch.int32, device=dev)
         if self.training:
             G = cfg.MAX_BOX_PER_IMAGE
-            g1 = S // 32
-            self.labels = [torch.zeros(B, g, g, 3, 5 + self.num_class, dtype=F32, device=dev)
-                           for g in (4 * g1, 2 * g1, g1)]          # yolo3, yolo2, yolo1
+            self.labels = [torch.zeros(B, H // d, W // d, 3, 5 + self.num_class, dtype=F32, device=dev)
+                           for d in (8, 16, 32)]                   # yolo3, yolo2, yolo1
             self.true_boxes = torch.zeros(B, G, 5, dtype=F32, device=dev)
-            self.true_masks = torch.zeros(B, G, S, S, dtype=torch.uint8, device=dev)
+            self.true_masks = torch.zeros(B, G, H, W, dtype=torch.uint8, device=dev)
             self.perm_det = torch.arange(cfg.MAX_DETECTION, dtype=torch.int32, device=dev).repeat(B, 1).contiguous()
             self.perm_gt = torch.arange(G, dtype=torch.int32, device=dev).repeat(B, 1).contiguous()
             self.rois = torch.zeros(B, L.ROI_MAX, L.roi_w(self.k), dtype=torch.int32, device=dev)
@@ -538,10 +561,10 @@ class YOLONet(object):
                 if l.dx is not None and l.kind != "lin" and not l.lock:
                     need = max(need, L.load().disyolo_bn_act_bwd_workspace(B * l.Ho * l.Wo, l.cout))
             if not l1.lock:
-                need = max(need, L.load().disyolo_conv_first_wgrad_workspace(B, S, S, l1.cout))
+                need = max(need, L.load().disyolo_conv_first_wgrad_workspace(B, H, W, l1.cout))
             self.ws.get(int(need))
             self.ws_aux.get(int(need))
-        self.ws_det.get(int(max(L.load().disyolo_detect_workspace(B, S, self.num_class), 1 << 20)))
+        self.ws_det.get(int(max(L.detect_workspace(B, (H, W), self.num_class), 1 << 20)))
         self._build_dgrad_descs()
         self.refresh_weights()
 
@@ -1042,7 +1065,7 @@ class YOLONet(object):
             return False            # (a trainable conv1 / conv2 needs its own output -- and its batch statistics)
         if any(1 in (l.src, l.src_up, l.shortcut) for l in self.layers if l.idx != 2):
             return False            # (act1 has another consumer: m = 1's conv83)
-        return L.conv12_fused_ok(self.B, self.S, self.S)
+        return L.conv12_fused_ok(self.B, self.H, self.W)
 
     def _forward_layer(self, l, is_training: bool) -> None:
         B = self.B
@@ -1130,8 +1153,12 @@ class YOLONet(object):
         if not getattr(self, "plan_only", False) and any(l.fused_fwd for l in self.layers):
             self._apply_tiles()
 
+    def mask_map_size(self) -> Tuple[int, int]:
+        """(Hm, Wm) of the score maps: (H / mask_stride, W / mask_stride)"""
+        return self.H // self.mask_stride, self.W // self.mask_stride
+
     def _detect(self, det_thresh: float) -> None:
-        L.detect(self.by_idx[75].act, self.by_idx[67].act, self.by_idx[59].act, self.B, self.S, self.num_class,
+        L.detect(self.by_idx[75].act, self.by_idx[67].act, self.by_idx[59].act, self.B, (self.H, self.W), self.num_class,
                  self.anchors.reshape(-1), self.clip_window, float(det_thresh), cfg.IOU_THRESHOLD, cfg.MAX_DETECTION,
                  self.detections, self.det_count, self.ws_det)
 
@@ -1164,9 +1191,10 @@ class YOLONet(object):
         if not self._inputs_free_of_tail():
             self.sync_lanes()
         images = torch.as_tensor(images)
-        if tuple(images.shape) != (self.B, self.S, self.S, 3):
-            raise ValueError("images must be [%d,%d,%d,3] NHWC (batch size and image size are baked into the plan, "
-                             "as in the reference: yolo/yolo3_net_pos.py:17)" % (self.B, self.S, self.S))
+        if tuple(images.shape) != (self.B, self.H, self.W, 3):
+            raise ValueError("images must be [%d,%d,%d,3] NHWC, height %d then width %d (batch size and image size are baked "
+                             "into the plan, as in the reference: yolo/yolo3_net_pos.py:17); got %s"
+                             % (self.B, self.H, self.W, self.H, self.W, list(images.shape)))
         cw = self.clip_window if not self.pair else self._in_sets[half]["clip_window"]
         img = self.images
         if pipe_set is not None:
@@ -1176,8 +1204,8 @@ class YOLONet(object):
 
     def forward(self, images, clip_window, det_thresh=cfg.OBJ_THRESHOLD, is_training: bool = False):
         """``sess.run(net.logits)``: returns (predictions, detections, mask_pos) with
-        predictions = [yolov3_3, yolov3_2, yolov3_1] raw logits [B,g,g,3,5+C] (f32),
-        detections [B,30,6], mask_pos [B,S/2,S/2,k*k] (yolo/yolo3_net_pos.py:353-357,463)."""
+        predictions = [yolov3_3, yolov3_2, yolov3_1] raw logits [B,gh,gw,3,5+C] (f32),
+        detections [B,30,6], mask_pos [B,H/m,W/m,k*k] (yolo/yolo3_net_pos.py:353-357,463)."""
         # backbone_pair: the caller's images are half 0 of the 2B-image backbone pass; the trainable layers, the clip
         # windows and the outputs must be that half's too, whatever half the training loop stopped at
         prev_half = self._half
@@ -1196,7 +1224,7 @@ class YOLONet(object):
 
     def evaluation_device(self, images, clip_window, det_thresh=cfg.OBJ_THRESHOLD):
         """the device half of ``evaluation``: network + detection filter + mask assembly on a batch; returns the fixed-shape
-        outputs where they are, (detections [B,30,6], keep [B,30], masks [B,30,Sm,Sm]) -- what MAP.collect_batch takes"""
+        outputs where they are, (detections [B,30,6], keep [B,30], masks [B,30,Hm,Wm]) -- what MAP.collect_batch takes"""
         thr = float(np.asarray(det_thresh).reshape(-1)[0])
         if (not self.training and getattr(self, "_infer_prog", None) is not None and getattr(self, "_infer_thresh", None) == thr
                 and not self.pair):
@@ -1205,11 +1233,11 @@ class YOLONet(object):
             self.infer(images, clip_window)
         else:
             self.forward(images, clip_window, det_thresh, is_training=False)
-            Sm = self.S // self.mask_stride
+            Hm, Wm = self.mask_map_size()
             if self.masks is None:
-                self.masks = torch.zeros(self.B, cfg.MAX_DETECTION, Sm, Sm, dtype=F32, device=self.device)
-            L.psroi_assemble(self.by_idx[self.score_layer].act, self.detections, self.B, cfg.MAX_DETECTION, Sm, self.k, self.masks,
-                             self.keep)
+                self.masks = torch.zeros(self.B, cfg.MAX_DETECTION, Hm, Wm, dtype=F32, device=self.device)
+            L.psroi_assemble(self.by_idx[self.score_layer].act, self.detections, self.B, cfg.MAX_DETECTION, (Hm, Wm), self.k,
+                             self.masks, self.keep)
         return self.detections, self.keep, self.masks
 
     def evaluation(self, images, clip_window, det_thresh=cfg.OBJ_THRESHOLD, masks_on_device: bool = False):
@@ -1233,11 +1261,11 @@ class YOLONet(object):
     def build_infer_program(self, det_thresh: float = cfg.OBJ_THRESHOLD, graph: bool = True) -> None:
         """Record inference (network + detection filter + mask assembly) into a command list
         and optionally a hipGraph; afterwards ``infer()`` is one replay.  Outputs stay on the
-        device, fixed-shape: detections [B,30,6], det_count [B], masks [B,30,S/2,S/2],
+        device, fixed-shape: detections [B,30,6], det_count [B], masks [B,30,H/m,W/m],
         keep [B,30] (BASELINE.json config 4)."""
-        Sm = self.S // self.mask_stride
+        Hm, Wm = self.mask_map_size()
         if self.masks is None:
-            self.masks = torch.zeros(self.B, cfg.MAX_DETECTION, Sm, Sm, dtype=F32, device=self.device)
+            self.masks = torch.zeros(self.B, cfg.MAX_DETECTION, Hm, Wm, dtype=F32, device=self.device)
         prog = L.CmdList()
         # a hipGraph is captured from ONE lane: the graph executor runs a captured side lane on a stream of its own choosing,
         # and whether that stream's hardware queue runs beside the launch stream's or stalls it is out of the caller's hands
@@ -1250,8 +1278,8 @@ class YOLONet(object):
             with prog:
                 self._forward_layers(False)
                 self._detect(det_thresh)
-                L.psroi_assemble(self.by_idx[self.score_layer].act, self.detections, self.B, cfg.MAX_DETECTION, Sm, self.k, self.masks,
-                                 self.keep)
+                L.psroi_assemble(self.by_idx[self.score_layer].act, self.detections, self.B, cfg.MAX_DETECTION, (Hm, Wm), self.k,
+                                 self.masks, self.keep)
         finally:
             self.use_side_lane = side_lane
         self.ws.frozen = True
@@ -1359,7 +1387,7 @@ class YOLONet(object):
         if self.shuffle_seed is not None:
             L.shuffle_perm(self.perm_det, self.perm_gt, self.B, int(self.shuffle_seed) & 0xffffffff, self.step_dev)
         self._detect(det_thresh)
-        Sm = self.S // self.mask_stride
+        Sm = self.mask_map_size()
         L.mask_rois(self.detections, cfg.MAX_DETECTION, self.true_boxes, cfg.MAX_BOX_PER_IMAGE, self.perm_det,
                     self.perm_gt, self.B, Sm, cfg.MASK_ROI_DET, cfg.MASK_ROI_GT, cfg.MASK_ROI_IOU, self.rois,
                     self.roi_count, k=self.k)
@@ -1375,11 +1403,11 @@ class YOLONet(object):
             L.set_lane(0)
         scales = (self.object_scale, self.noobject_scale, self.class_scale, self.coord_scale)
         if self.output_depth > L.GRAD_LD:      # rows past 32 channels (more than 5 classes): the heads' own pitch
-            L.yolo_loss_wide([h.act for h in heads], self.labels, self.true_boxes, cfg.MAX_BOX_PER_IMAGE, self.B, self.S,
+            L.yolo_loss_wide([h.act for h in heads], self.labels, self.true_boxes, cfg.MAX_BOX_PER_IMAGE, self.B, (self.H, self.W),
                              self.num_class, heads[0].cout_pad, self.anchors.reshape(-1), cfg.IGNORE_THRESH, scales,
                              [h.dx for h in heads], self.losses, self.ws)
         else:
-            L.yolo_loss([h.act for h in heads], self.labels, self.true_boxes, cfg.MAX_BOX_PER_IMAGE, self.B, self.S,
+            L.yolo_loss([h.act for h in heads], self.labels, self.true_boxes, cfg.MAX_BOX_PER_IMAGE, self.B, (self.H, self.W),
                         self.num_class, self.anchors.reshape(-1), cfg.IGNORE_THRESH, scales,
                         [h.dx for h in heads], self.losses, self.ws)
         self._mask_loss_pending = side

@@ -13,18 +13,20 @@ import torch
 from . import lib as L
 
 
-def letterbox_window(image_h: int, image_w: int, size: int) -> np.ndarray:
-    """``image_read``'s clip window (calculate_test_map.py:151-169): [top, left, bottom, right],
-    normalised, of the aspect-preserving resize centred in the size x size letter box."""
+def letterbox_window(image_h: int, image_w: int, size) -> np.ndarray:
+    """``image_read``'s clip window (calculate_test_map.py:151-169): [top, left, bottom, right], normalised by
+    (net_h, net_w), of the aspect-preserving resize centred in the letter box of a net of ``size`` (an int, or
+    (net_h, net_w)); the width binds when net_w / image_w < net_h / image_h."""
+    net_h, net_w = L.hw_of(size)
     imgh, imgw = image_h, image_w
-    if (float(size) / imgw) < (float(size) / imgh):
-        imgh = (imgh * size) // imgw
-        imgw = size
+    if (float(net_w) / imgw) < (float(net_h) / imgh):
+        imgh = (imgh * net_w) // imgw
+        imgw = net_w
     else:
-        imgw = (imgw * size) // imgh
-        imgh = size
-    top, left = (size - imgh) // 2, (size - imgw) // 2
-    return np.array([top / size, left / size, (imgh + top) / size, (imgw + left) / size], np.float32)
+        imgw = (imgw * net_h) // imgh
+        imgh = net_h
+    top, left = (net_h - imgh) // 2, (net_w - imgw) // 2
+    return np.array([top / net_h, left / net_w, (imgh + top) / net_h, (imgw + left) / net_w], np.float32)
 
 
 def correct_yolo_boxes(boxes_yxyx: np.ndarray, image_h: int, image_w: int, net_h: int, net_w: int) -> np.ndarray:
@@ -44,34 +46,37 @@ def correct_yolo_boxes(boxes_yxyx: np.ndarray, image_h: int, image_w: int, net_h
                      corner(b[:, 3], x_off, x_scale, image_w), corner(b[:, 2], y_off, y_scale, image_h)], axis=1)
 
 
-def paste_rects(box: np.ndarray, image_h: int, image_w: int, net_size: int, map_size: int) -> Tuple[np.ndarray, np.ndarray]:
+def paste_rects(box: np.ndarray, image_h: int, image_w: int, net_size, map_size) -> Tuple[np.ndarray, np.ndarray]:
     """The rect arithmetic of the paste (calculate_test_map.py:244-251) for an [n,6] detection array (normalised y1,x1,y2,x2,
-    class, score) on an image_h x image_w image, a net_size letter box and map_size x map_size masks: (rects int32 [n,8] =
-    cy1,cx1,cy2,cx2 on the mask map, y1,x1,y2,x2 in the image -- what disyolo_mask_paste takes --, ok bool [n]); the rows with an
-    empty crop or destination are not ``ok`` and have zero rects."""
+    class, score) on an image_h x image_w image, the letter box of a net of ``net_size`` and masks of ``map_size`` (each an int,
+    or a (height, width) pair): (rects int32 [n,8] = cy1,cx1,cy2,cx2 on the mask map -- around(y * Hm), around(x * Wm) --,
+    y1,x1,y2,x2 in the image -- what disyolo_mask_paste takes --, ok bool [n]); the rows with an empty crop or destination are
+    not ``ok`` and have zero rects."""
     box = np.asarray(box, np.float32).reshape(-1, 6)
-    dst = correct_yolo_boxes(box[:, :4], image_h, image_w, net_size, net_size)          # x1,y1,x2,y2
-    crop = np.around(box[:, :4] * np.float32(map_size)).astype(np.int32)                   # y1,x1,y2,x2 on the map
+    net_h, net_w = L.hw_of(net_size)
+    map_h, map_w = L.hw_of(map_size)
+    dst = correct_yolo_boxes(box[:, :4], image_h, image_w, net_h, net_w)                # x1,y1,x2,y2
+    crop = np.around(box[:, :4] * np.asarray([map_h, map_w, map_h, map_w], np.float32)).astype(np.int32)   # y1,x1,y2,x2 on the map
     rects = np.concatenate([crop, dst[:, [1, 0, 3, 2]]], axis=1).astype(np.int32)          # cy1,cx1,cy2,cx2,y1,x1,y2,x2
     ok = ((dst[:, 3] - dst[:, 1]) * (dst[:, 2] - dst[:, 0]) > 0) & (crop[:, 2] > crop[:, 0]) & (crop[:, 3] > crop[:, 1])
     rects[~ok] = 0
     return rects, ok
 
 
-def paste_detections(det_box, det_mask, image_h: int, image_w: int, net_size: int,
+def paste_detections(det_box, det_mask, image_h: int, image_w: int, net_size,
                      want_full: bool = True) -> Tuple[List[Dict], torch.Tensor]:
     """One image of ``evaluation``'s result -> (entries, merged) like the reference loop body
     (calculate_test_map.py:220-266): ``entries`` = [{index, classid, score, mask (bool CUDA tensor
     [H,W])}] for the detections with a non-empty box, ``merged`` = uint8 CUDA tensor [H,W] with
-    class id + 1.  ``det_box`` [n,6] (numpy or tensor), ``det_mask`` CUDA f32 [n,S,S] or the
-    scalar 0.0 the reference returns for an image without detections."""
+    class id + 1.  ``det_box`` [n,6] (numpy or tensor), ``det_mask`` CUDA f32 [n,Hm,Wm] or the
+    scalar 0.0 the reference returns for an image without detections; ``net_size``: the net's size, an int or (H, W)."""
     dev = det_mask.device if torch.is_tensor(det_mask) else torch.device("cuda", torch.cuda.current_device())
     merged = torch.zeros(image_h, image_w, dtype=torch.uint8, device=dev)
     box = det_box.detach().cpu().numpy() if torch.is_tensor(det_box) else np.asarray(det_box)
     if not torch.is_tensor(det_mask) or box.size == 0:
         return [], merged
     box = box.reshape(-1, 6).astype(np.float32)
-    n, size = box.shape[0], int(det_mask.shape[-1])
+    n, size = box.shape[0], (int(det_mask.shape[-2]), int(det_mask.shape[-1]))
     rects, ok = paste_rects(box, image_h, image_w, net_size, size)
     rects_d = torch.from_numpy(rects).to(dev)
     cls_d = torch.from_numpy(box[:, 4].astype(np.int32)).to(dev)

@@ -282,7 +282,7 @@ class Solver(object):
                               " Loss: {:5.3f}, crack: {:5.3f}, spall: {:5.3f}, rebar: {:5.3f}, mAP50: {:5.3f},"
                               "\nSpeed: {:.3f}s/iter, Load: {:.3f}s/iter, Remain: {}").format(
                         datetime.datetime.now().strftime("%m/%d %H:%M:%S"), getattr(self.data, "epoch", 0), int(step),
-                        getattr(self.data, "image_size", net.S), getattr(self.data, "batch_size", net.B),
+                        getattr(self.data, "image_size", net.image_size), getattr(self.data, "batch_size", net.B),
                         round(shown_lr, 6), record_loss, thresh_out["AP"][0], thresh_out["AP"][1], thresh_out["AP"][2],
                         thresh_out["mAP"][2], train_timer.average_time, load_timer.average_time,
                         train_timer.remain(step, self.max_iter)))

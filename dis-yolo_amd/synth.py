@@ -12,12 +12,21 @@ import numpy as np
 from . import config as cfg
 
 
-def assign_target_entries(boxes_px, cls, S: int, num_class: int):
+def net_hw(S):
+    """(net_h, net_w) of a net size given as one int S (square) or as a pair (H, W)"""
+    if isinstance(S, (int, np.integer)):
+        return int(S), int(S)
+    h, w = S
+    return int(h), int(w)
+
+
+def assign_target_entries(boxes_px, cls, S, num_class: int):
     """utils/train_data.py:149-178 as a sparse list: best-IoU anchor of the 9 (boxes centred at the origin),
-    cell = int(centre * grid / net); an occupied (cell, anchor) keeps its first box.  Returns, per scale (yolo3, yolo2,
-    yolo1), {(yi, xi, anchor): row float32 [5 + C]} in assignment order -- the non-zero rows of the dense target grids."""
-    g1 = S // 32
-    sizes = [4 * g1, 2 * g1, g1]
+    cell = (int(xc * grid_w / net_w), int(yc * grid_h / net_h)); an occupied (cell, anchor) keeps its first box.  ``S``: the
+    net's size, an int or (H, W).  Returns, per scale (yolo3, yolo2, yolo1), {(yi, xi, anchor): row float32 [5 + C]} in
+    assignment order -- the non-zero rows of the dense target grids."""
+    H, W = net_hw(S)
+    sizes = [(H // d, W // d) for d in (8, 16, 32)]
     out = [dict() for _ in sizes]
     amax = np.asarray(cfg.ANCHORS, np.float32) / 2.0
     a_area = amax[:, 0] * amax[:, 1] * 4
@@ -29,8 +38,8 @@ def assign_target_entries(boxes_px, cls, S: int, num_class: int):
         if iou.max() <= 0:
             continue
         idx = int(np.argmax(iou))
-        g = sizes[idx // 3]
-        xi, yi = int(b[0] * g / S), int(b[1] * g / S)
+        gh, gw = sizes[idx // 3]
+        xi, yi = int(b[0] * gw / W), int(b[1] * gh / H)
         key = (yi, xi, idx % 3)
         if key in out[idx // 3]:
             continue
@@ -42,32 +51,35 @@ def assign_target_entries(boxes_px, cls, S: int, num_class: int):
     return out
 
 
-def assign_targets(boxes_px, cls, S: int, num_class: int):
-    """the dense grids of utils/train_data.py:149-178: [g, g, 3, 5 + C] per scale (yolo3, yolo2, yolo1)"""
-    g1 = S // 32
-    yolos = [np.zeros((m * g1, m * g1, 3, 5 + num_class), np.float32) for m in (4, 2, 1)]
+def assign_targets(boxes_px, cls, S, num_class: int):
+    """the dense grids of utils/train_data.py:149-178: [gh, gw, 3, 5 + C] per scale (yolo3, yolo2, yolo1)"""
+    H, W = net_hw(S)
+    yolos = [np.zeros((H // d, W // d, 3, 5 + num_class), np.float32) for d in (8, 16, 32)]
     for y, ent in zip(yolos, assign_target_entries(boxes_px, cls, S, num_class)):
         for (yi, xi, a), row in ent.items():
             y[yi, xi, a] = row
     return yolos
 
 
-def synthetic_batch(B: int, S: int, seed: int = 1234, num_class: int = 3):
-    """dict of numpy arrays: images f32 [B,S,S,3] in [0,1), clip_window [B,4] = (0,0,1,1),
-    true_boxes [B,1,1,1,20,5] (xc,yc,w,h normalised, class), true_masks bool [B,20,S,S],
-    yolo1/2/3 targets [B,g,g,3,5+C] with normalised boxes."""
+def synthetic_batch(B: int, S, seed: int = 1234, num_class: int = 3):
+    """dict of numpy arrays for a net of size ``S`` (an int, or (H, W)): images f32 [B,H,W,3] in [0,1), clip_window [B,4] =
+    (0,0,1,1), true_boxes [B,1,1,1,20,5] (xc,yc,w,h normalised -- x, w by W and y, h by H --, class), true_masks bool
+    [B,20,H,W], yolo1/2/3 targets [B,gh,gw,3,5+C] with normalised boxes.  The order and count of the RNG draws do not depend
+    on the shape."""
+    H, W = net_hw(S)
+    norm = np.asarray([W, H, W, H], np.float32)
     rng = np.random.RandomState(seed)
     G = cfg.MAX_BOX_PER_IMAGE
-    images = rng.rand(B, S, S, 3).astype(np.float32)
+    images = rng.rand(B, H, W, 3).astype(np.float32)
     true_boxes = np.zeros((B, 1, 1, 1, G, 5), np.float32)
-    true_masks = np.zeros((B, G, S, S), bool)
-    ys = [np.zeros((B, S // d, S // d, 3, 5 + num_class), np.float32) for d in (8, 16, 32)]
-    yy, xx = np.mgrid[0:S, 0:S]
+    true_masks = np.zeros((B, G, H, W), bool)
+    ys = [np.zeros((B, H // d, W // d, 3, 5 + num_class), np.float32) for d in (8, 16, 32)]
+    yy, xx = np.mgrid[0:H, 0:W]
     for b in range(B):
         bx, cl = [], []
         for j in range(rng.randint(1, 6)):
-            w, h = rng.uniform(0.05, 0.6, size=2) * S
-            cx, cy = rng.uniform(w / 2, S - w / 2), rng.uniform(h / 2, S - h / 2)
+            w, h = rng.uniform(0.05, 0.6, size=2) * np.asarray([W, H])
+            cx, cy = rng.uniform(w / 2, W - w / 2), rng.uniform(h / 2, H - h / 2)
             m = ((xx - cx) / (w / 2)) ** 2 + ((yy - cy) / (h / 2)) ** 2 <= 1.0
             if not m.any():
                 continue
@@ -78,12 +90,12 @@ def synthetic_batch(B: int, S: int, seed: int = 1234, num_class: int = 3):
             c = rng.randint(0, num_class)
             box = [(x1 + x2) / 2.0, (y1 + y2) / 2.0, float(x2 - x1), float(y2 - y1)]
             true_masks[b, j] = m
-            true_boxes[b, 0, 0, 0, j, :4] = np.asarray(box, np.float32) / S
+            true_boxes[b, 0, 0, 0, j, :4] = np.asarray(box, np.float32) / norm
             true_boxes[b, 0, 0, 0, j, 4] = c
             bx.append(box)
             cl.append(c)
-        for dst, t in zip(ys, assign_targets(np.asarray(bx, np.float32).reshape(-1, 4), cl, S, num_class)):
-            t[..., 0:4] /= S
+        for dst, t in zip(ys, assign_targets(np.asarray(bx, np.float32).reshape(-1, 4), cl, (H, W), num_class)):
+            t[..., 0:4] /= norm
             dst[b] = t
     return {"images": images, "clip_window": np.tile(np.array([[0, 0, 1, 1]], np.float32), (B, 1)),
             "true_boxes": true_boxes, "true_masks": true_masks, "yolo3": ys[0], "yolo2": ys[1], "yolo1": ys[2]}

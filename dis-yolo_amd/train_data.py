@@ -9,7 +9,7 @@ assigns the targets, and the GPU does all pixel work (``csrc/augment.hip``): pol
 resize + place + pad + flip of image and masks, the three photometric augmentations, /255 -- straight into the
 batch buffers ``YOLONet.set_batch`` consumes.
 
-Same ``get()`` contract: (images [B,S,S,3] f32, true_masks [B,20,S,S] bool, true_boxes [B,1,1,1,20,5],
+Same ``get()`` contract, for ``image_size`` = S or (H, W): (images [B,H,W,3] f32, true_masks [B,20,H,W] bool, true_boxes [B,1,1,1,20,5],
 yolo_3, yolo_2, yolo_1, clip_window [B,4]); tensors live on the GPU (``.cpu().numpy()`` for a host caller).  The two device
 tensors are views of the loader's own batch buffers, of which there are two sets: what a ``get()`` returns stays intact through the
 NEXT ``get()`` and is overwritten by the one after it (a training loop that reads one batch ahead, ``Solver.train``, holds two).
@@ -65,13 +65,16 @@ class defect_train(object):
     'polygons': [[{'type', 'all_points_x', 'all_points_y'}, ...] per instance]}] -- the ``gt_labels`` structure of
     the reference's cache (utils/train_data.py:278-319)."""
 
-    def __init__(self, labels: List[Dict], batch_size: Optional[int] = None, image_size: Optional[int] = None, device=None,
+    def __init__(self, labels: List[Dict], batch_size: Optional[int] = None, image_size=None, device=None,
                  rng: Optional[np.random.RandomState] = None, flipped: Optional[bool] = None,
                  blur_noise_light: Optional[bool] = None, cache_bytes: int = 16 << 30,
                  classes: Optional[Sequence[str]] = None):
         self.batch_size = cfg.BATCH_SIZE if batch_size is None else batch_size
+        # image_size: an int S or a pair (net_h, net_w), like YOLONet's; the attribute keeps the caller's form
+        from .net import check_image_size
         self.image_size = cfg.IMAGE_SIZE if image_size is None else image_size
-        self.base_grid = self.image_size // 32
+        self.net_h, self.net_w = check_image_size(self.image_size)
+        self.base_grid = self.net_h // 32 if self.net_h == self.net_w else (self.net_h // 32, self.net_w // 32)
         self.max_box_per_image = cfg.MAX_BOX_PER_IMAGE
         self.anchors = cfg.ANCHORS
         self.num_anchor = 3
@@ -87,11 +90,12 @@ class defect_train(object):
         self.gt_labels = list(labels)
         self.rng.shuffle(self.gt_labels)                       # :40
         self.random_labels = copy.copy(self.gt_labels)
-        B, S, G = self.batch_size, self.image_size, self.max_box_per_image
+        B, G = self.batch_size, self.max_box_per_image
+        NH, NW = self.net_h, self.net_w
         dev = self.device
         # batch buffers, written in place by the kernels: two sets, used in turn
-        self._sets = [(torch.zeros(B, S, S, 3, dtype=torch.float32, device=dev),
-                       torch.zeros(B, G, S, S, dtype=torch.uint8, device=dev)) for _ in range(2)]
+        self._sets = [(torch.zeros(B, NH, NW, 3, dtype=torch.float32, device=dev),
+                       torch.zeros(B, G, NH, NW, dtype=torch.uint8, device=dev)) for _ in range(2)]
         self._turn = 0
         self.images, self.true_masks = self._sets[0]
         # the small host-built arrays (true_boxes, the three target grids, the clip windows): per set a staging copy on the host
@@ -99,8 +103,7 @@ class defect_train(object):
         # last fill of the set wrote (only those are cleared again: the grids are 5 MB of zeros around a dozen rows) and an
         # event behind the set's last upload
         cuda = dev.type == "cuda"
-        g1 = self.base_grid
-        shapes = [(B, 1, 1, 1, G, 5)] + [(B, g, g, 3, 5 + self.num_class) for g in (4 * g1, 2 * g1, g1)] + [(B, 4)]
+        shapes = [(B, 1, 1, 1, G, 5)] + [(B, NH // d, NW // d, 3, 5 + self.num_class) for d in (8, 16, 32)] + [(B, 4)]
         self._host = [[torch.zeros(sh, dtype=torch.float32, pin_memory=cuda) for sh in shapes] for _ in range(2)]
         self._dev = [[torch.zeros(sh, dtype=torch.float32, device=dev) for sh in shapes] for _ in range(2)]
         self._written = [[], []]
@@ -111,8 +114,8 @@ class defect_train(object):
         # uint8 frames of the batch (the placed images, augmented in place) + one scratch frame for the motion blur; the
         # placement jobs of a batch (images and instance masks: ONE launch, csrc/augment.hip place_batch_kernel) are written
         # into pinned staging and uploaded with the batch's other small arrays
-        self._frames = torch.zeros(B, S, S, 3, dtype=torch.uint8, device=dev)
-        self._blur = torch.zeros(S, S, 3, dtype=torch.uint8, device=dev)
+        self._frames = torch.zeros(B, NH, NW, 3, dtype=torch.uint8, device=dev)
+        self._blur = torch.zeros(NH, NW, 3, dtype=torch.uint8, device=dev)
         njob = B * (1 + G)
         self._jobs_host = [torch.zeros(njob * L.PLACE_JOB.itemsize, dtype=torch.uint8, pin_memory=dev.type == "cuda") for _ in range(2)]
         self._jobs_dev = [torch.zeros(njob * L.PLACE_JOB.itemsize, dtype=torch.uint8, device=dev) for _ in range(2)]
@@ -167,7 +170,9 @@ class defect_train(object):
                 "yolo2": d[2], "yolo1": d[3], "clip_window": d[4]}
 
     def _fill(self) -> None:
-        B, S, G, rng = self.batch_size, self.image_size, self.max_box_per_image, self.rng
+        B, G, rng = self.batch_size, self.max_box_per_image, self.rng
+        S = (self.net_h, self.net_w)
+        norm = np.asarray([self.net_w, self.net_h, self.net_w, self.net_h], np.float32)      # x, w by net_w; y, h by net_h
         dev = self.device
         turn = self._turn
         self._turn ^= 1
@@ -191,13 +196,14 @@ class defect_train(object):
             label = self.random_labels[self.cursor]
             image_h, image_w, src, masks, boxes, cls = self._record(label)
             # ---- augmentation step 1: random scale and crop (:90-133); the draws happen in the reference's order
-            net_w = net_h = S
+            net_h, net_w = S
+            fit_ar = net_w / net_h           # which side binds the fit: the reference's ``new_ar < 1`` at net_w = net_h
             scale_crop = int(rng.randint(low=1, high=3))
             if scale_crop == 2:
                 jitter = 0.2
                 new_ar = image_w / image_h * rng.uniform(1 - jitter, 1 + jitter) / rng.uniform(1 - jitter, 1 + jitter)
                 scale = rng.uniform(0.75, 1.5)
-                if new_ar < 1:
+                if new_ar < fit_ar:
                     new_h = int(scale * net_h)
                     new_w = int(new_h * new_ar)
                 else:
@@ -213,7 +219,7 @@ class defect_train(object):
                         scale_crop = 1                                                     # keep every defect inside
             if scale_crop == 1:
                 new_ar = image_w / image_h
-                if new_ar < 1:
+                if new_ar < fit_ar:
                     new_h = int(1.0 * net_h)
                     new_w = int(new_h * new_ar)
                 else:
@@ -238,7 +244,7 @@ class defect_train(object):
             if flip == 2:
                 bx[:, 0] = net_w - 1 - bx[:, 0]
                 for k, ent in enumerate(grids):
-                    gsz = ys[k].shape[1]
+                    gsz = ys[k].shape[2]
                     for row in ent.values():
                         row[0] = np.float32(net_w - 1) - row[0]
                     grids[k] = {(yi, gsz - 1 - xi, a): row for (yi, xi, a), row in ent.items()}
@@ -263,10 +269,10 @@ class defect_train(object):
                 jobs[njobs] = (m.data_ptr(), self.true_masks[count, j].data_ptr(), 1, image_h, image_w, new_w, new_h, dx, dy, flip)
                 njobs += 1
             if bnl == 2:                                                                    # salt & pepper (:511-525)
-                n_el = S * S * 3
+                n_el = net_h * net_w * 3
                 ns, npp = int(math.ceil(0.004 * n_el * 0.2)), int(math.ceil(0.004 * n_el * 0.8))
-                cs = [rng.randint(0, i - 1, ns) for i in (S, S, 3)]
-                cp = [rng.randint(0, i - 1, npp) for i in (S, S, 3)]
+                cs = [rng.randint(0, i - 1, ns) for i in (net_h, net_w, 3)]
+                cp = [rng.randint(0, i - 1, npp) for i in (net_h, net_w, 3)]
                 photo.append((count, "salt_pepper", (np.concatenate([cs[0], cp[0]]).astype(np.int32),
                                                      np.concatenate([cs[1], cp[1]]).astype(np.int32), ns, npp)))
                 dec.update(salt=(cs[0], cs[1]), pepper=(cp[0], cp[1]))
@@ -282,11 +288,11 @@ class defect_train(object):
                 photo.append((count, "blur", (angle, {0: 1, 1: 2, 2: 0}[type_idx])))
                 dec.update(angle=angle, line_type=("right", "left", "full")[type_idx], _len=int(length_idx))
             # ---- normalise (:250-257)
-            true_boxes[count, 0, 0, 0, :len(bx), :4] = bx / S
+            true_boxes[count, 0, 0, 0, :len(bx), :4] = bx / norm
             true_boxes[count, 0, 0, 0, :len(bx), 4] = cls
             for k, ent in enumerate(grids):
                 for (yi, xi, a), row in ent.items():
-                    row[0:4] = row[0:4] / np.float32(S)
+                    row[0:4] = row[0:4] / norm
                     ys[k][count, yi, xi, a] = row
                     written.append((k, count, yi, xi, a))
             self.last_decisions.append(dec)

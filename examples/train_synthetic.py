@@ -2,7 +2,7 @@
 Solver (recorded pipelined step: the next batch's backbone and its data loading beside the current step) -> TF-format checkpoint -> reload into an
 inference net -> detections + instance masks for one image.
 
-    python examples/train_synthetic.py [--steps 40] [--size 192] [--batch 4] [--out /tmp/disyolo_example] [--lock 62-64]
+    python examples/train_synthetic.py [--steps 40] [--size 192 | --size 128x192] [--batch 4] [--out /tmp/disyolo_example] [--lock 62-64]
                                        [--classes crack,spall,rebar,stain,joint,void]
 
 It mirrors what the reference's ``train_yolo3_mask.py:237-248`` (train) and ``calculate_test_map.py`` (test) do
@@ -56,10 +56,20 @@ def parse_lock(text):
     return lock
 
 
+def parse_size(text):
+    """"192" -> 192 (a square net), "128x192" -> (128, 192) = (H, W): what YOLONet, defect_train, image_read and
+    paste_detections take as the net's size"""
+    if "x" in text.lower():
+        h, _, w = text.lower().partition("x")
+        return int(h), int(w)
+    return int(text)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=40)
-    ap.add_argument("--size", type=int, default=192)
+    ap.add_argument("--size", type=parse_size, default=192,
+                    help="the net's input size: S (a square) or HxW, each side a multiple of 32 (e.g. 128x192)")
     ap.add_argument("--batch", type=int, default=4)
     ap.add_argument("--out", default="/tmp/disyolo_example")
     ap.add_argument("--k-map", type=int, default=cfg.K_MAP, choices=(3, 5, 7),

@@ -392,6 +392,14 @@ int disyolo_detect(const float* logits3, const float* logits2, const float* logi
                    int num_class, const float* anchors_host, const float* clip_window,
                    float obj_thresh, float nms_thresh, int max_det, float* detections,
                    int32_t* det_count, void* workspace, size_t workspace_bytes, void* stream);
+/* the same filter on a net of H x W pixels (both positive multiples of 32): head grids (H/8, W/8),
+ * (H/16, W/16), (H/32, W/32), logits [B,gh,gw,3,5+C], candidates in scale, y, x, anchor order; box x and w
+ * are normalised by gw / W, y and h by gh / H.  disyolo_detect is its H = W = S call. */
+size_t disyolo_detect_workspace_hw(int B, int H, int W, int num_class);
+int disyolo_detect_hw(const float* logits3, const float* logits2, const float* logits1, int B, int H, int W,
+                      int num_class, const float* anchors_host, const float* clip_window,
+                      float obj_thresh, float nms_thresh, int max_det, float* detections,
+                      int32_t* det_count, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- YOLO loss + gradient (loss_yolo, yolo/yolo3_net_pos.py:631-747) ---- */
 /* labels: f32 [B,g,g,3,5+C] per scale (yolo3, yolo2, yolo1); true_boxes f32 [B,20,5].
@@ -414,6 +422,16 @@ int disyolo_yolo_loss_wide(const float* const logits[3], const float* const labe
                            int dlogits_ld, const float* anchors_host, float ignore_thresh,
                            const float scales[4], void* const dlogits[3], float* losses,
                            void* workspace, size_t workspace_bytes, void* stream);
+/* both losses on a net of H x W pixels (positive multiples of 32): labels, logits and dlogits
+ * [B,gh,gw,...] per scale with (gh, gw) = (H/8, W/8), (H/16, W/16), (H/32, W/32); grid_factor = [gw, gh],
+ * net_factor = [W, H] as in the reference (:646, :709-718).  dlogits_ld = 0 runs the 32-channel kernel of
+ * disyolo_yolo_loss, any other value the wide one; those two are the H = W = S calls of this one. */
+size_t disyolo_yolo_loss_workspace_hw(int B, int H, int W, int num_class);
+int disyolo_yolo_loss_hw(const float* const logits[3], const float* const labels[3],
+                         const float* true_boxes, int max_boxes, int B, int H, int W, int num_class,
+                         int dlogits_ld, const float* anchors_host, float ignore_thresh,
+                         const float scales[4], void* const dlogits[3], float* losses,
+                         void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- position-sensitive RoI assembly (yolo/yolo3_net_pos.py:750-938) ---- */
 /* RoI selection for the mask loss (:757-796): detections [B,max_det,6], true_boxes [B,G,5],
@@ -429,6 +447,13 @@ int disyolo_mask_rois(const float* detections, int max_det, const float* true_bo
                       const int32_t* perm_det, const int32_t* perm_gt, int B, int map_size,
                       int n_det, int n_gt, float iou_thresh, int32_t* rois, int32_t* roi_count,
                       void* stream);
+/* RoI selection on a score map of map_h x map_w: y-coordinates are scaled by map_h, x-coordinates by map_w,
+ * each through tf.round; bin edges per axis; the area is the pixel count clipped to the map.
+ * disyolo_mask_rois_k is its map_h = map_w call. */
+int disyolo_mask_rois_hw(const float* detections, int max_det, const float* true_boxes, int G,
+                         const int32_t* perm_det, const int32_t* perm_gt, int B, int map_h, int map_w, int k,
+                         int n_det, int n_gt, float iou_thresh, int32_t* rois, int32_t* roi_count,
+                         void* stream);
 /* tf.random_shuffle replacement (:781-782): uniformly random permutations perm_det int32
  * [B,n_det], perm_gt int32 [B,n_gt] from a counter-based hash of (seed, *step_counter, image);
  * step_counter (device int64, may be NULL) makes every replay of a recorded step reshuffle */
@@ -451,11 +476,21 @@ int disyolo_psroi_loss_s(const float* score, const uint8_t* true_masks, int G, c
                          const int32_t* roi_count, int B, int map_size, int mask_stride, int k,
                          float mask_scale, void* dscore, float* loss, void* workspace,
                          size_t workspace_bytes, void* stream);
+/* disyolo_psroi_loss_s on a score map of map_h x map_w: score f32 [B,map_h,map_w,k*k], true_masks uint8
+ * [B,G,s*map_h,s*map_w], dscore bf16 [B,map_h,map_w,P]; rois from disyolo_mask_rois_hw with the same map. */
+size_t disyolo_psroi_loss_workspace_hw(int B, int map_h, int map_w);
+int disyolo_psroi_loss_hw(const float* score, const uint8_t* true_masks, int G, const int32_t* rois,
+                          const int32_t* roi_count, int B, int map_h, int map_w, int mask_stride, int k,
+                          float mask_scale, void* dscore, float* loss, void* workspace,
+                          size_t workspace_bytes, void* stream);
 /* inference assembly (val_test, :862-938): masks f32 [B,max_det,Sm,Sm] = sigmoid(selected
  * channel) inside the box, 0.5 outside; keep int32 [B,max_det] = 1 for rows with h>0 and w>0.
  * k = 3, 5 or 7; score f32 [B,Sm,Sm,k*k]. */
 int disyolo_psroi_assemble(const float* score, const float* detections, int B, int max_det,
                            int map_size, int k, float* masks, int32_t* keep, void* stream);
+/* the assembly on a score map of map_h x map_w: masks f32 [B,max_det,map_h,map_w]; y scaled by map_h, x by map_w */
+int disyolo_psroi_assemble_hw(const float* score, const float* detections, int B, int max_det,
+                              int map_h, int map_w, int k, float* masks, int32_t* keep, void* stream);
 
 /* evaluate()'s per-image mask post-processing (calculate_test_map.py:237-262), the caller side
  * of `evaluation`: for each of the image's n detections the crop [cy1:cy2, cx1:cx2] of its
@@ -468,6 +503,11 @@ int disyolo_psroi_assemble(const float* score, const float* detections, int B, i
 int disyolo_mask_paste(const float* masks, int n, int size, const int32_t* rects,
                        const int32_t* classids, int image_h, int image_w, uint8_t* full_masks,
                        uint8_t* merged, void* stream);
+/* the paste from masks of map_h x map_w (disyolo_psroi_assemble_hw output): the crop rows are cy1,cy2 on map_h
+ * and cx1,cx2 on map_w.  disyolo_mask_paste is its map_h = map_w call. */
+int disyolo_mask_paste_hw(const float* masks, int n, int map_h, int map_w, const int32_t* rects,
+                          const int32_t* classids, int image_h, int image_w, uint8_t* full_masks,
+                          uint8_t* merged, void* stream);
 /* the same paste for a whole batch of images in ONE launch, with the counts the mask AP and the mIoU need instead of the
  * full-resolution masks (which are never written).  One job per image:
  *   masks / rects / classids / image_h / image_w / merged: as in disyolo_mask_paste, n <= 64 rows; a row whose rect is all zero
@@ -500,12 +540,20 @@ size_t disyolo_paste_job_size(void);
 int disyolo_paste_job_plan(disyolo_paste_job* jobs_host, int njobs);
 int disyolo_mask_paste_iou_batch(const disyolo_paste_job* jobs_host, const disyolo_paste_job* jobs, int njobs, int size,
                                  int64_t* conf, void* stream);
+/* the batched paste from masks of map_h x map_w; disyolo_mask_paste_iou_batch is its map_h = map_w call */
+int disyolo_mask_paste_iou_batch_hw(const disyolo_paste_job* jobs_host, const disyolo_paste_job* jobs, int njobs, int map_h,
+                                    int map_w, int64_t* conf, void* stream);
 /* image_read of the test / validation drivers (calculate_test_map.py:149-176; utils/val_data.py:36-63):
  * rgb uint8 [image_h, image_w, 3] (device) -> out f32 [size, size, 3] (device): aspect-preserving
  * bilinear resize (cv2.resize INTER_LINEAR on the float32 image) centred in the letter box, padding
  * 127, / 255.  window_host (host, may be NULL) receives the clip window [top, left, bottom, right]. */
 int disyolo_letterbox(const uint8_t* rgb, int image_h, int image_w, float* out, int size,
                       float* window_host, void* stream);
+/* the letter box of a net of net_h x net_w pixels: out f32 [net_h, net_w, 3]; the width binds when
+ * net_w / image_w < net_h / image_h; the window is normalised by (net_h, net_w).  disyolo_letterbox is its
+ * net_h = net_w call. */
+int disyolo_letterbox_hw(const uint8_t* rgb, int image_h, int image_w, float* out, int net_h, int net_w,
+                         float* window_host, void* stream);
 /* semantic-segmentation accuracy of evaluate (calculate_test_map.py:303-346): adds the 4x4 pixel
  * confusion counts of two uint8 class maps (0 = background, 1..3 = classes; other values are
  * ignored) to conf int64 [16], conf[true*4 + pred]; the caller zeroes conf before the first image
@@ -597,6 +645,17 @@ int disyolo_aug_salt_pepper(uint8_t* image, int size, const int32_t* rows, const
 int disyolo_aug_change_light(uint8_t* image, int size, double coeff, void* stream);
 /* linearmotion_blur3C (:466-494), line length 3: angle 0/45/90/135, line_type 0 full / 1 right / 2 left */
 int disyolo_aug_motion_blur3(const uint8_t* src, uint8_t* dst, int size, int angle, int line_type, void* stream);
+/* the five kernels above on a frame of net_h x net_w (the loader of a rectangular net: dst [net_h, net_w, 3] or
+ * [net_h, net_w], flips about the frame's own width / height, salt-and-pepper rows < net_h and cols < net_w -- a coordinate
+ * outside the frame is skipped); each entry point above is the net_h = net_w = size call of its _hw form */
+int disyolo_aug_place_hw(const uint8_t* src, int is_mask, int image_h, int image_w, uint8_t* dst, int net_h, int net_w,
+                         int new_w, int new_h, int dx, int dy, int flip, void* stream);
+int disyolo_aug_place_batch_hw(const disyolo_place_job* jobs, int njobs, int net_h, int net_w, void* stream);
+int disyolo_aug_salt_pepper_hw(uint8_t* image, int net_h, int net_w, const int32_t* rows, const int32_t* cols, int nsalt,
+                               int npepper, void* stream);
+int disyolo_aug_change_light_hw(uint8_t* image, int net_h, int net_w, double coeff, void* stream);
+int disyolo_aug_motion_blur3_hw(const uint8_t* src, uint8_t* dst, int net_h, int net_w, int angle, int line_type,
+                                void* stream);
 /* image.astype(float32) / 255.0 (:411-413) */
 int disyolo_aug_to_float(const uint8_t* image, float* out, int64_t n, void* stream);
 

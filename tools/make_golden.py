@@ -193,6 +193,81 @@ def targets_fixture():
         json.dump({"source": "utils/train_data.py:134-178 executed by tools/make_golden.py", "cases": cases}, f)
 
 
+RECT_NETS = [(64, 128), (128, 64), (352, 576), (576, 448)]      # (net_h, net_w): both orientations
+
+
+def rect_targets_fixture():
+    """targets_fixture at net_h != net_w, into a file of its own: the same loop of utils/train_data.py:134-178, executed
+    with net_h and net_w apart (the reference's text keeps them apart; only its caller sets both to image_size)"""
+    import ast
+    import types
+    import yolo.config as c
+    src = open(os.path.join(REF, "utils", "train_data.py")).read()
+    loop = None
+    for node in ast.walk(ast.parse(src)):
+        if (isinstance(node, ast.For) and isinstance(node.target, ast.Name) and node.target.id == "index"
+                and isinstance(node.iter, ast.Name) and node.iter.id == "bbox_index" and 130 <= node.lineno <= 140):
+            loop = node
+    code = compile(ast.Module(body=[loop], type_ignores=[]), "train_data.py", "exec")
+    rng = np.random.RandomState(22)
+    cases = []
+    for (net_h, net_w) in RECT_NETS:
+        for case in range(4):
+            n = rng.randint(1, 9)
+            bbox = np.zeros((1, 1, 1, 20, 5), np.float32)
+            for j in range(n):
+                w, h = rng.uniform(4, 0.7 * net_w), rng.uniform(4, 0.7 * net_h)
+                if case == 3 and j > 0:          # collisions: same cell and anchor as box 0
+                    x1, y1 = bbox[0, 0, 0, 0, 0] + rng.uniform(-2, 2), bbox[0, 0, 0, 0, 1] + rng.uniform(-2, 2)
+                    w, h = bbox[0, 0, 0, 0, 2] - bbox[0, 0, 0, 0, 0], bbox[0, 0, 0, 0, 3] - bbox[0, 0, 0, 0, 1]
+                elif case == 2 and j == 0:       # a box in the last cell of both axes
+                    x1, y1 = net_w - 1 - w, net_h - 1 - h
+                else:
+                    x1, y1 = rng.uniform(0, net_w - w), rng.uniform(0, net_h - h)
+                bbox[0, 0, 0, j] = [x1, y1, x1 + w, y1 + h, rng.randint(0, 3)]
+            inp = bbox[0, 0, 0, :n].copy()
+            yolos = [np.zeros((net_h // d, net_w // d, 3, 8), np.float32) for d in (8, 16, 32)]
+            ns = {"np": np, "self": types.SimpleNamespace(anchors=c.ANCHORS, num_anchor=3), "bbox_index": list(range(n)),
+                  "bbox": bbox, "sx": 1.0, "sy": 1.0, "dx": 0, "dy": 0, "net_w": net_w, "net_h": net_h, "yolos": yolos,
+                  "print": lambda *a: None}
+            exec(code, ns)
+            nz = [{"grid": gi, "idx": [int(v) for v in idx], "row": yolos[gi][tuple(idx)].tolist()}
+                  for gi in range(3) for idx in np.argwhere(yolos[gi][..., 4] == 1)]
+            cases.append({"net_hw": [net_h, net_w], "boxes_x1y1x2y2c": inp.tolist(),
+                          "true_box_xcycwh": bbox[0, 0, 0, :n, :4].tolist(), "objects": nz})
+    with open(os.path.join(OUT, "assign_targets_rect.json"), "w") as f:
+        json.dump({"source": "utils/train_data.py:134-178 executed by tools/make_golden.py with net_h != net_w", "cases": cases}, f)
+
+
+def rect_boxes_fixture():
+    """boxes_fixture at net_h != net_w, into a file of its own: calculate_test_map.py:121-138 takes net_h, net_w"""
+    import ast
+    src = open(os.path.join(REF, "calculate_test_map.py")).read()
+    fn = None
+    for node in ast.walk(ast.parse(src)):
+        if isinstance(node, ast.FunctionDef) and node.name == "correct_yolo_boxes":
+            fn = node
+    ns = {"np": np}
+    exec(compile(ast.Module(body=[fn], type_ignores=[]), "calculate_test_map.py", "exec"), ns)
+    ref = ns["correct_yolo_boxes"]
+    from PIL import Image
+    import glob
+    sizes = sorted({Image.open(f).size[::-1] for f in glob.glob(os.path.join(REF, "data/train_sample/images/*.jpg"))})
+    rng = np.random.RandomState(4)
+    cases = []
+    for (h, w) in sizes:
+        for (net_h, net_w) in RECT_NETS:
+            boxes = rng.rand(16, 4).astype(np.float32)
+            boxes[:4] = [[0, 0, 1, 1], [0.5, 0.5, 0.5, 0.5], [0.25, 0.1, 0.2, 0.9], [0.999, 0.001, 1.0, 0.0]]
+            for (x1, y1, x2, y2) in boxes:
+                r = ref(None, np.float32(x1), np.float32(y1), np.float32(x2), np.float32(y2), h, w, net_h, net_w)
+                cases.append({"box": [float(x1), float(y1), float(x2), float(y2)], "image_hw": [int(h), int(w)],
+                              "net_hw": [net_h, net_w], "out": [int(v) for v in r]})
+    with open(os.path.join(OUT, "correct_yolo_boxes_rect.json"), "w") as f:
+        json.dump({"source": "calculate_test_map.py:121-138 executed by tools/make_golden.py with net_h != net_w",
+                   "cases": cases}, f)
+
+
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
     config_fixture()
@@ -200,4 +275,6 @@ if __name__ == "__main__":
     boxes_fixture()
     miou_fixture()
     targets_fixture()
+    rect_targets_fixture()
+    rect_boxes_fixture()
     print("golden fixtures written to", OUT)
