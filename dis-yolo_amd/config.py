@@ -64,3 +64,6 @@ ADAM_EPSILON = 1e-8
 MASK_ROI_DET = 7          # yolo/yolo3_net_pos.py:783
 MASK_ROI_GT = 3           # yolo/yolo3_net_pos.py:783
 MASK_ROI_IOU = 0.5        # yolo/yolo3_net_pos.py:60
+# filter_detections' NMS form: "per_class" = Method 1 (yolo/yolo3_net_pos.py:564-592, the active one), "agnostic" =
+# Method 2 (:594-605, commented out there), "none" = its nms=False (:518, 585).  YOLONet(nms=...) overrides it
+NMS_METHOD = "per_class"

@@ -99,7 +99,8 @@ __device__ __forceinline__ float nms_iou(const float4& a, const float4& b) {
 // thousands of candidates per class (random logits at 576^2: ~6,800 of 20,412); with the list
 // in global memory a round cost 16 us (two dependent sweeps + two barriers), 30 rounds = 0.5 ms
 // on the chain that holds up the mask subnet's backward pass; in registers a round is ~1 us.
-// Longer lists (one class taking > 8,192 candidates) keep the global-memory form.
+// Longer lists (one class taking > 8,192 candidates) keep the global-memory form.  (The image-wide modes, one list per image
+// whatever the class: nms_image_kernel below, 20 slots per thread.)
 constexpr int NMS_T = 1024;
 constexpr int NMS_K = 8;
 constexpr int NMS_W = NMS_T / 64;
@@ -324,6 +325,217 @@ __global__ __launch_bounds__(NMS_T) void nms_class_kernel(const float4* boxes, c
   __syncthreads();  // list[] (global) written by this block, read below by all its threads
   const int nk = greedy_nms_block(total, list, boxes, scores, live_glob, nms_thr, max_det, kept_idx, kept_sc);
   if (tid == 0) kept_n[blockIdx.x] = nk;
+}
+
+// ---- image-wide filter: class-agnostic NMS (Method 2 of yolo/yolo3_net_pos.py:594-605) and NMS off (nms=False, :518, 585) ----
+// One block per image compacts ALL candidates with score > thr in index order and runs the same greedy loop over that one
+// list.  The selection order -- score descending, ties to the lower candidate index -- already is the top_k order of
+// :608-612, so the block writes the rows, the zero padding and det_count itself: no merge launch.  "No NMS" is the same
+// loop with nms_thr = +inf (no IoU is > +inf): max_det rounds of "take the best, retire it".
+// The register form holds NMS_KA slots per thread: 20,480 candidates >= the 20,412 of a 576^2 image.  A slot costs 5
+// VGPRs and a 1,024-thread block has 128 per lane, so 20 (100 VGPRs) is about what fits beside the sweep's own registers.
+constexpr int NMS_KA = 20;
+constexpr int NMS_KA_LD = 4;          // slots whose loads are in flight together while the list is read
+
+// nms_class_kernel's ordered compaction without the class test, as a function: list[0..total) receives, in ascending order,
+// the indices of the image's candidates with score > thr; total is returned to every thread.  list[] is global memory: the
+// caller puts a barrier before the block reads it.  (That kernel keeps its own inlined copy: its code is left as measured.)
+__device__ __forceinline__ int compact_above(const float* scores, const int NC, const float thr, int* list) {
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  __shared__ int s_wcnt[2][NMS_CB][NMS_W];
+  int total = 0;
+  for (int base = 0, bt = 0; base < NC; base += NMS_T * NMS_CB, ++bt) {
+    bool f[NMS_CB];
+    unsigned long long mask[NMS_CB];
+#pragma unroll
+    for (int j = 0; j < NMS_CB; ++j) {
+      const int i = base + j * NMS_T + tid;
+      const float sv = scores[i < NC ? i : 0];
+      f[j] = (i < NC) && (sv > thr);
+    }
+#pragma unroll
+    for (int j = 0; j < NMS_CB; ++j) {
+      mask[j] = __ballot(f[j]);
+      if (lane == 0) s_wcnt[bt & 1][j][wv] = __popcll(mask[j]);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < NMS_CB; ++j) {
+      int off = total;
+#pragma unroll
+      for (int w = 0; w < NMS_W; ++w) {
+        const int cw = s_wcnt[bt & 1][j][w];
+        if (w < wv) off += cw;
+        total += cw;
+      }
+      if (f[j]) list[off + __popcll(mask[j] & ((1ull << lane) - 1ull))] = base + j * NMS_T + tid;
+    }
+  }
+  return total;
+}
+
+// min / max of two numbers as compare + select: fminf / fmaxf on a value the compiler has not produced itself (the winner
+// out of LDS, a slot after the asm below) cost an extra canonicalising instruction and a register each
+__device__ __forceinline__ float nms_lo(float a, float b) { return a < b ? a : b; }
+__device__ __forceinline__ float nms_hi(float a, float b) { return a > b ? a : b; }
+
+// greedy_nms_block for the image-wide list: the same rounds and the same one barrier, with the register form trimmed to
+// what 20 slots leave room for.  A slot holds its score and its box with the corner order already normalised (nms_iou's
+// min / max are idempotent, so the IoU is the same bit for bit); a thread tracks only score and slot of its best survivor,
+// and the wave winner's owner picks that slot's box out of its registers with a select chain when it publishes it; the
+// round's winner lives in scalar registers.  hipcc 7.2: 128 VGPRs, no spill, no scratch (-Rpass-analysis=kernel-resource-usage);
+// each of these choices removed spills, so look at that report after touching the loop.
+__device__ __forceinline__ int greedy_nms_image(const int n, const int* list, const float4* boxes, const float* scores,
+                                                float* live_glob, const float nms_thr, const int max_det, int* kept_idx,
+                                                float* kept_sc) {
+  const int tid = threadIdx.x, wv = __builtin_amdgcn_readfirstlane(tid >> 6);   // (wave-uniform: LDS addresses in scalars)
+  __shared__ float s_ws[2][NMS_W];
+  __shared__ int s_wp[2][NMS_W];
+  __shared__ float4 s_wb[2][NMS_W];
+  __shared__ int s_kidx[64];
+  __shared__ float s_ksc[64];
+  if (n > NMS_KA * NMS_T) {
+    for (int q = tid; q < n; q += NMS_T) live_glob[q] = scores[list[q]];
+    __syncthreads();
+    return greedy_nms_global(n, list, boxes, live_glob, nms_thr, max_det, kept_idx, kept_sc, s_ws[0], s_wp[0]);
+  }
+  float sc[NMS_KA], y1[NMS_KA], x1[NMS_KA], y2[NMS_KA], x2[NMS_KA];
+  float bs = -1.f;                   // this thread's best survivor: score and slot (list position tid + bk * NMS_T)
+  int bk = -1;
+#pragma unroll
+  for (int k = 0; k < NMS_KA; ++k) {
+    const int q = tid + k * NMS_T;
+    sc[k] = -1.f;
+    float4 bx = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (q < n) {
+      const int i = list[q];
+      sc[k] = scores[i];
+      bx = boxes[i];
+    }
+    y1[k] = fminf(bx.x, bx.z);
+    x1[k] = fminf(bx.y, bx.w);
+    y2[k] = fmaxf(bx.x, bx.z);
+    x2[k] = fmaxf(bx.y, bx.w);
+    const bool take = sc[k] > bs;    // ascending positions: the lowest wins among equal scores
+    bs = take ? sc[k] : bs;
+    bk = take ? k : bk;
+    if (k % NMS_KA_LD == NMS_KA_LD - 1) asm volatile("" ::: "memory");   // (bounds the loads in flight, and their registers)
+  }
+  int nk = 0;
+  for (int it = 0; it < max_det; ++it) {
+    const int par = it & 1;
+    const int bp = bk < 0 ? 0x7fffffff : tid + bk * NMS_T;
+    float ws = bs;
+    int wp = bp;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const float v2 = __shfl_xor(ws, o, 64);
+      const int p2 = __shfl_xor(wp, o, 64);
+      if (nms_better(v2, p2, ws, wp)) {
+        ws = v2;
+        wp = p2;
+      }
+    }
+    if (wp == bp) {  // the wave winner's owner (a wave with nothing alive: every lane, the same values)
+      float4 bb = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+      for (int k = 0; k < NMS_KA; ++k) {
+        const bool mine = bk == k;
+        bb.x = mine ? y1[k] : bb.x;
+        bb.y = mine ? x1[k] : bb.y;
+        bb.z = mine ? y2[k] : bb.z;
+        bb.w = mine ? x2[k] : bb.w;
+      }
+      s_ws[par][wv] = ws;
+      s_wp[par][wv] = wp;
+      s_wb[par][wv] = bb;
+    }
+    __syncthreads();
+    float wsc = s_ws[par][0];
+    int wq = s_wp[par][0], ww = 0;
+#pragma unroll
+    for (int w = 1; w < NMS_W; ++w) {
+      const float v2 = s_ws[par][w];
+      const int p2 = s_wp[par][w];
+      if (nms_better(v2, p2, wsc, wq)) {
+        wsc = v2;
+        wq = p2;
+        ww = w;
+      }
+    }
+    if (!(wsc > 0.f)) break;  // nothing alive (live scores are > thr >= 0); uniform exit
+    // the block winner is the same in every lane: position and (normalised) box go to scalar registers, the vector ones
+    // are all needed for the slots
+    wq = __builtin_amdgcn_readfirstlane(wq);
+    const float4 wbv = s_wb[par][ww];
+    float4 wb;
+    wb.x = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, wbv.x)));
+    wb.y = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, wbv.y)));
+    wb.z = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, wbv.z)));
+    wb.w = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, wbv.w)));
+    const float ab = (wb.z - wb.x) * (wb.w - wb.y);
+    if (tid == 0) {
+      s_kidx[nk] = wq;        // list position; the candidate index is looked up once, after the loop
+      s_ksc[nk] = wsc;
+    }
+    ++nk;
+    // suppress against the winner and find this thread's best survivor, one sweep, branch-free like greedy_nms_block's:
+    // the IoU is nms_iou's, operation by operation, with its early "empty box -> 0" as a select
+    const int dq = wq - tid;
+    const int kq = (dq & (NMS_T - 1)) ? -1 : dq / NMS_T;   // the winner's slot in the thread that holds it
+    bs = -1.f;
+    bk = -1;
+#pragma unroll
+    for (int k = 0; k < NMS_KA; ++k) {
+      // (no instruction: the slot's area is the same every round, and hoisted out of the round loop it would cost a
+      //  sixth register per slot, which spills)
+      asm volatile("" : "+v"(y2[k]), "+v"(x2[k]));
+      const float aa = (y2[k] - y1[k]) * (x2[k] - x1[k]);
+      const float inter = fmaxf(nms_lo(y2[k], wb.z) - nms_hi(y1[k], wb.x), 0.f) * fmaxf(nms_lo(x2[k], wb.w) - nms_hi(x1[k], wb.y), 0.f);
+      const float quot = inter / (aa + ab - inter);
+      const float iou = ((aa <= 0.f) | (ab <= 0.f)) ? 0.f : quot;
+      const bool kill = (kq == k) | (iou > nms_thr);
+      sc[k] = kill ? -1.f : sc[k];            // (dead slots stay at -1)
+      const bool take = sc[k] > bs;
+      bs = take ? sc[k] : bs;
+      bk = take ? k : bk;
+    }
+  }
+  __syncthreads();
+  if (tid < nk) {
+    kept_idx[tid] = list[s_kidx[tid]];
+    kept_sc[tid] = s_ksc[tid];
+  }
+  return nk;
+}
+
+__global__ __launch_bounds__(NMS_T) void nms_image_kernel(const float4* boxes, const float* scores, const int* classes,
+                                                          int NC, float thr, float nms_thr, int max_det, int* list_g,
+                                                          float* live_g, int* kept_idx, float* kept_sc, float* det,
+                                                          int* det_count) {
+  const int b = blockIdx.x, tid = threadIdx.x;
+  boxes += (size_t)b * NC;
+  scores += (size_t)b * NC;
+  classes += (size_t)b * NC;
+  int* list = list_g + (size_t)b * NC;
+  kept_idx += (size_t)b * max_det;
+  kept_sc += (size_t)b * max_det;
+  det += (size_t)b * max_det * 6;
+  const int total = compact_above(scores, NC, thr, list);
+  __syncthreads();  // list[] (global) written by this block, read below by all its threads
+  const int nk = greedy_nms_image(total, list, boxes, scores, live_g + (size_t)b * NC, nms_thr, max_det, kept_idx, kept_sc);
+  __syncthreads();  // kept_idx / kept_sc (global) written by this block
+  for (int e = tid; e < max_det * 6; e += NMS_T) {
+    const int r = e / 6, f = e - r * 6;
+    float v = 0.f;
+    if (r < nk) {
+      const int i = kept_idx[r];
+      const float4 bx = boxes[i];
+      v = f == 0 ? bx.x : f == 1 ? bx.y : f == 2 ? bx.z : f == 3 ? bx.w : f == 4 ? (float)classes[i] : kept_sc[r];
+    }
+    det[e] = v;
+  }
+  if (tid == 0) det_count[b] = nk;
 }
 
 // ---- more than 16 classes: one ordered pass per image buckets the candidates by class, the greedy loop runs per segment ----
@@ -821,6 +1033,20 @@ extern "C" int disyolo_detect_hw(const float* logits3, const float* logits2, con
                                  int num_class, const float* anchors_host, const float* clip_window, float obj_thresh,
                                  float nms_thresh, int max_det, float* detections, int32_t* det_count, void* workspace,
                                  size_t workspace_bytes, void* stream) {
+  return disyolo_detect_nms_hw(logits3, logits2, logits1, B, H, W, num_class, anchors_host, clip_window, obj_thresh,
+                               nms_thresh, max_det, DISYOLO_NMS_PER_CLASS, detections, det_count, workspace, workspace_bytes,
+                               stream);
+}
+
+extern "C" int disyolo_detect_list_capacity(void) { return NMS_KA * NMS_T; }
+
+// ... with the choice of which candidates above the threshold survive (DISYOLO_NMS_*)
+extern "C" int disyolo_detect_nms_hw(const float* logits3, const float* logits2, const float* logits1, int B, int H, int W,
+                                     int num_class, const float* anchors_host, const float* clip_window, float obj_thresh,
+                                     float nms_thresh, int max_det, int nms_mode, float* detections, int32_t* det_count,
+                                     void* workspace, size_t workspace_bytes, void* stream) {
+  DY_REQUIRE(nms_mode == DISYOLO_NMS_PER_CLASS || nms_mode == DISYOLO_NMS_AGNOSTIC || nms_mode == DISYOLO_NMS_NONE,
+             "detect: nms_mode must be 0 (per class), 1 (class-agnostic) or 2 (none) (got %d)", nms_mode);
   DY_REQUIRE(logits3 && logits2 && logits1 && anchors_host && clip_window && detections && det_count,
              "detect: null pointer");
   DY_REQUIRE(B > 0 && H > 0 && W > 0 && H % 32 == 0 && W % 32 == 0 && num_class > 0 && num_class <= WD_MAXC,
@@ -832,12 +1058,19 @@ extern "C" int disyolo_detect_hw(const float* logits3, const float* logits2, con
     disyolo_set_error("detect: workspace too small");
     return DISYOLO_E_WORKSPACE;
   }
+  if (nms_mode != DISYOLO_NMS_PER_CLASS) {
+    // decode results, ONE list + live per image, max_det kept (idx, score): inside what any class count's workspace holds
+    const size_t NC = (size_t)3 * 21 * (H / 32) * (W / 32);
+    DY_REQUIRE((size_t)B * NC * (16 + 4 + 4) + (size_t)B * NC * 8 + (size_t)B * max_det * 8 <=
+                   disyolo_detect_workspace_hw(B, H, W, num_class),
+               "detect: the workspace does not hold an image-wide list");
+  }
   {
     std::array<float, 18> anc;
     for (int i = 0; i < 18; ++i) anc[i] = anchors_host[i];
     DY_RECORD_OR_RUN([=](void* s) {
-      return disyolo_detect_hw(logits3, logits2, logits1, B, H, W, num_class, anc.data(), clip_window, obj_thresh,
-                               nms_thresh, max_det, detections, det_count, workspace, workspace_bytes, s);
+      return disyolo_detect_nms_hw(logits3, logits2, logits1, B, H, W, num_class, anc.data(), clip_window, obj_thresh,
+                                   nms_thresh, max_det, nms_mode, detections, det_count, workspace, workspace_bytes, s);
     });
   }
   DecodeParams p;
@@ -862,6 +1095,19 @@ extern "C" int disyolo_detect_hw(const float* logits3, const float* logits2, con
   p.scores = (float*)ws;                  ws += (size_t)B * c0 * 4;
   p.classes = (int*)ws;                   ws += (size_t)B * c0 * 4;
   hipStream_t st = (hipStream_t)stream;
+  if (nms_mode != DISYOLO_NMS_PER_CLASS) {
+    int* list = (int*)ws;                 ws += (size_t)B * c0 * 4;
+    float* live = (float*)ws;             ws += (size_t)B * c0 * 4;
+    int* kept_idx = (int*)ws;             ws += (size_t)B * max_det * 4;
+    float* kept_sc = (float*)ws;
+    hipLaunchKernelGGL(decode_score_kernel, dim3(ceil_div(c0, 256), B), dim3(256), 0, st, p);
+    DY_CHECK_LAUNCH();
+    hipLaunchKernelGGL(nms_image_kernel, dim3(B), dim3(NMS_T), 0, st, p.boxes, p.scores, p.classes, c0, obj_thresh,
+                       nms_mode == DISYOLO_NMS_NONE ? INFINITY : nms_thresh, max_det, list, live, kept_idx, kept_sc,
+                       detections, det_count);
+    DY_CHECK_LAUNCH();
+    return DISYOLO_OK;
+  }
   if (num_class > 16) {
     int* list = (int*)ws;                 ws += (size_t)B * c0 * 4;
     float* live = (float*)ws;             ws += (size_t)B * c0 * 4;

@@ -21,6 +21,9 @@ ROI_MAX = 16
 ROI_W = 12
 K_MAPS = (3, 5, 7)          # position-sensitive grids the mask path covers (the reference's list)
 MASK_STRIDES = (1, 2, 4)    # GT mask -> score map sampling steps psroi_loss_s covers (score maps at S, S/2, S/4)
+# which candidates above the score threshold the detection filter keeps (DISYOLO_NMS_* of disyolo.h; filter_detections,
+# yolo/yolo3_net_pos.py:564-592 / 594-605 / nms=False)
+NMS_MODES = {"per_class": 0, "agnostic": 1, "none": 2}
 
 
 def roi_w(k: int) -> int:
@@ -134,6 +137,9 @@ _SIGS = {
     "disyolo_detect_workspace_hw": (C.c_size_t, [C.c_int] * 4),
     "disyolo_detect_hw": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 4 + [C.c_void_p] * 2 + [C.c_float, C.c_float, C.c_int] +
                           [C.c_void_p] * 3 + [C.c_size_t, C.c_void_p]),
+    "disyolo_detect_list_capacity": (C.c_int, []),
+    "disyolo_detect_nms_hw": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 4 + [C.c_void_p] * 2 +
+                              [C.c_float, C.c_float, C.c_int, C.c_int] + [C.c_void_p] * 3 + [C.c_size_t, C.c_void_p]),
     "disyolo_yolo_loss_workspace": (C.c_size_t, [C.c_int] * 3),
     "disyolo_yolo_loss_workspace_hw": (C.c_size_t, [C.c_int] * 4),
     "disyolo_yolo_loss_hw": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p, C.c_float] +
@@ -1088,16 +1094,31 @@ def detect_workspace(B, S, num_class) -> int:
     return load().disyolo_detect_workspace_hw(B, H, W, num_class)
 
 
+def nms_mode(nms) -> int:
+    """the DISYOLO_NMS_* value of a mode name"""
+    if not isinstance(nms, str) or nms not in NMS_MODES:
+        raise ValueError("nms must be one of %s (got %r)" % (", ".join(repr(m) for m in NMS_MODES), nms))
+    return NMS_MODES[nms]
+
+
+def detect_list_capacity() -> int:
+    """candidates above the threshold that the image-wide filter ("agnostic", "none") keeps in registers; a longer list
+    runs from the workspace, with the same result"""
+    return load().disyolo_detect_list_capacity()
+
+
 def detect(logits3, logits2, logits1, B, S, num_class, anchors_host, clip_window, obj_thresh, nms_thresh, max_det,
-           detections, det_count, ws: Workspace) -> None:
-    """``S``: the net's input size, an int or (H, W)"""
+           detections, det_count, ws: Workspace, nms: str = "per_class") -> None:
+    """``S``: the net's input size, an int or (H, W).  ``nms``: "per_class" (greedy NMS inside each arg-max class),
+    "agnostic" (one greedy NMS over all of an image's candidates) or "none" (the max_det highest scores)"""
     H, W = hw_of(S)
+    mode = nms_mode(nms)
     need = load().disyolo_detect_workspace_hw(B, H, W, num_class)
     buf = ws.get(need)
     anc = (C.c_float * 18)(*[float(v) for v in anchors_host])
-    _check(load().disyolo_detect_hw(_p(logits3), _p(logits2), _p(logits1), B, H, W, num_class, anc, _p(clip_window),
-                                    obj_thresh, nms_thresh, max_det, _p(detections), _p(det_count), _p(buf), buf.numel(),
-                                    _stream()), "detect")
+    _check(load().disyolo_detect_nms_hw(_p(logits3), _p(logits2), _p(logits1), B, H, W, num_class, anc, _p(clip_window),
+                                        obj_thresh, nms_thresh, max_det, mode, _p(detections), _p(det_count), _p(buf),
+                                        buf.numel(), _stream()), "detect")
 
 
 def yolo_loss(logits, labels, true_boxes, max_boxes, B, S, num_class, anchors_host, ignore_thresh, scales, dlogits,

@@ -181,7 +181,7 @@ class YOLONet(object):
                  batch_size: Optional[int] = None, stage: int = 1, lock: Optional[Dict[int, bool]] = None,
                  seed: int = 0, xavier_locked: bool = True, plan_only: bool = False, dtype: str = "bf16",
                  backbone_pair: bool = False, k_map: Optional[int] = None, mask_stride: Optional[int] = None,
-                 classes: Optional[Sequence[str]] = None):
+                 classes: Optional[Sequence[str]] = None, nms: Optional[str] = None):
         # 1. parameters (yolo/yolo3_net_pos.py:15-38)
         self.batchsize = int(batch_size if batch_size is not None else cfg.BATCH_SIZE)
         # the class list (CLASSES of yolo/config.py): cfg.CLASSES unless given; it sizes the three heads
@@ -201,6 +201,11 @@ class YOLONet(object):
         if self.mask_stride not in MASK_STRIDES:
             raise ValueError("mask_stride must be one of %s (got %d)" % (", ".join(map(str, MASK_STRIDES)), self.mask_stride))
         self.score_layer = score_layer_of(self.mask_stride)
+        # which candidates above the score threshold the detection filter keeps (filter_detections,
+        # yolo/yolo3_net_pos.py:517-628): "per_class" = its Method 1, "agnostic" = its Method 2, "none" = nms=False;
+        # cfg.NMS_METHOD unless given.  Every path that detects follows it, the mask-loss RoIs of training included
+        self.nms = cfg.NMS_METHOD if nms is None else nms
+        L.nms_mode(self.nms)
         self.object_scale = cfg.OBJECT_SCALE
         self.noobject_scale = cfg.NOOBJECT_SCALE
         self.class_scale = cfg.CLASS_SCALE
@@ -1160,7 +1165,7 @@ class YOLONet(object):
     def _detect(self, det_thresh: float) -> None:
         L.detect(self.by_idx[75].act, self.by_idx[67].act, self.by_idx[59].act, self.B, (self.H, self.W), self.num_class,
                  self.anchors.reshape(-1), self.clip_window, float(det_thresh), cfg.IOU_THRESHOLD, cfg.MAX_DETECTION,
-                 self.detections, self.det_count, self.ws_det)
+                 self.detections, self.det_count, self.ws_det, nms=self.nms)
 
     def _use_half(self, h: int) -> None:
         """backbone_pair: the trainable part reads half ``h`` of the backbone outputs and the inputs of that batch"""

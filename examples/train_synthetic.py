@@ -79,6 +79,9 @@ def main():
     ap.add_argument("--lock", default="", help="layer ranges to lock on top of stage 1, e.g. 5-9,62-64 (\"!40-52\" unlocks)")
     ap.add_argument("--classes", default=",".join(cfg.CLASSES),
                     help="comma-separated class list, 1 to 80 names (cfg.CLASSES): it sizes the heads, the targets and the metric")
+    ap.add_argument("--nms", default=cfg.NMS_METHOD, choices=("per_class", "agnostic", "none"),
+                    help="detection filter: greedy NMS inside each class (cfg.NMS_METHOD), one class-agnostic NMS per image, "
+                         "or no suppression; it picks the mask-loss RoIs in training and what is pasted at test time")
     args = ap.parse_args()
     classes = [c.strip() for c in args.classes.split(",")]
     dev = torch.device("cuda:0")
@@ -89,7 +92,7 @@ def main():
     data = defect_train(labels, batch_size=args.batch, image_size=args.size, device=dev, rng=np.random.RandomState(1),
                         classes=classes)
     net = YOLONet(training=True, device=dev, image_size=args.size, batch_size=args.batch, stage=1, seed=0, k_map=args.k_map,
-                  mask_stride=args.mask_stride, lock=parse_lock(args.lock), classes=classes)
+                  mask_stride=args.mask_stride, lock=parse_lock(args.lock), classes=classes, nms=args.nms)
     if net.pass_through_layers():
         print("locked layers the gradient crosses:", net.pass_through_layers())
     solver = Solver(net, data, output_dir=args.out, max_iter=args.steps, summary_iter=max(1, args.steps // 4),
@@ -102,7 +105,7 @@ def main():
     prefix = checkpoint.latest_checkpoint(os.path.join(args.out, "checkpoint"))
     print("restoring", prefix)
     inf = YOLONet(training=False, device=dev, image_size=args.size, batch_size=1, stage=1, seed=123, k_map=args.k_map,
-                  mask_stride=args.mask_stride, classes=classes)
+                  mask_stride=args.mask_stride, classes=classes, nms=args.nms)
     checkpoint.restore_net(inf, prefix)
     rec = labels[0]
     from disyolo_amd.evaluate import image_read

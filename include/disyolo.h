@@ -400,6 +400,24 @@ int disyolo_detect_hw(const float* logits3, const float* logits2, const float* l
                       int num_class, const float* anchors_host, const float* clip_window,
                       float obj_thresh, float nms_thresh, int max_det, float* detections,
                       int32_t* det_count, void* workspace, size_t workspace_bytes, void* stream);
+/* ... with the choice of which candidates with score > obj_thresh (on the clipped boxes, :558) survive:
+ *   DISYOLO_NMS_PER_CLASS  Method 1 (:564-592), what disyolo_detect / disyolo_detect_hw run: greedy NMS per arg-max class,
+ *                          then the max_det best survivors;
+ *   DISYOLO_NMS_AGNOSTIC   Method 2 (:594-605): ONE greedy NMS over all of an image's candidates whatever their class --
+ *                          visited by descending score, ties to the lower candidate index, dropped iff the IoU with an
+ *                          already kept one is > nms_thresh, at most max_det kept;
+ *   DISYOLO_NMS_NONE       nms=False (:518, 585): the max_det highest scores, ties to the lower candidate index.
+ * Any other nms_mode: DISYOLO_E_ARG.  Same outputs, same workspace (disyolo_detect_workspace_hw) in every mode.  The two
+ * image-wide modes run one block per image; its candidate list sits in registers up to disyolo_detect_list_capacity()
+ * candidates above the threshold (a whole 576 x 576 image) and in the workspace beyond -- the same result either way. */
+#define DISYOLO_NMS_PER_CLASS 0
+#define DISYOLO_NMS_AGNOSTIC 1
+#define DISYOLO_NMS_NONE 2
+int disyolo_detect_list_capacity(void);
+int disyolo_detect_nms_hw(const float* logits3, const float* logits2, const float* logits1, int B, int H, int W,
+                          int num_class, const float* anchors_host, const float* clip_window,
+                          float obj_thresh, float nms_thresh, int max_det, int nms_mode, float* detections,
+                          int32_t* det_count, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- YOLO loss + gradient (loss_yolo, yolo/yolo3_net_pos.py:631-747) ---- */
 /* labels: f32 [B,g,g,3,5+C] per scale (yolo3, yolo2, yolo1); true_boxes f32 [B,20,5].
