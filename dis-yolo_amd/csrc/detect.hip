@@ -169,7 +169,9 @@ __device__ __forceinline__ int greedy_nms_global(int n, const int* list, const f
 // The greedy loop over one (image, class) list, shared by the kernel that compacts its own list (<= 16 classes) and the one
 // that takes a segment of the bucketed list (more classes): list[0..n) holds candidate indices in ascending order, scores /
 // boxes are the image's, live_glob has room for n floats.  All NMS_T threads of the block call it; kept_idx / kept_sc receive
-// the survivors in selection order and the count is returned to every thread.
+// the survivors in selection order and the count is returned to every thread.  KMAX >= max_det: the winners' LDS list (64 is
+// the instance of the entry points that take max_det <= 64, 256 = DISYOLO_MAX_DET the one of disyolo_detect_x).
+template <int KMAX>
 __device__ __forceinline__ int greedy_nms_block(const int n, const int* list, const float4* boxes, const float* scores,
                                                 float* live_glob, const float nms_thr, const int max_det, int* kept_idx,
                                                 float* kept_sc) {
@@ -177,8 +179,8 @@ __device__ __forceinline__ int greedy_nms_block(const int n, const int* list, co
   __shared__ float s_ws[2][NMS_W];
   __shared__ int s_wp[2][NMS_W];
   __shared__ float4 s_wb[2][NMS_W];
-  __shared__ int s_kidx[64];
-  __shared__ float s_ksc[64];
+  __shared__ int s_kidx[KMAX];
+  __shared__ float s_ksc[KMAX];
   int nk = 0;
   if (n <= NMS_K * NMS_T) {
     float sc[NMS_K];
@@ -263,7 +265,7 @@ __device__ __forceinline__ int greedy_nms_block(const int n, const int* list, co
       }
     }
     __syncthreads();
-    if (tid < nk) {
+    if (tid < nk) {          // (nk <= max_det <= KMAX <= NMS_T)
       kept_idx[tid] = list[s_kidx[tid]];
       kept_sc[tid] = s_ksc[tid];
     }
@@ -275,6 +277,7 @@ __device__ __forceinline__ int greedy_nms_block(const int n, const int* list, co
   return nk;
 }
 
+template <int KMAX>
 __global__ __launch_bounds__(NMS_T) void nms_class_kernel(const float4* boxes, const float* scores, const int* classes,
                                                           int NC, int C, float thr, float nms_thr, int max_det,
                                                           int* list_g, float* live_g, int* kept_idx, float* kept_sc,
@@ -323,7 +326,7 @@ __global__ __launch_bounds__(NMS_T) void nms_class_kernel(const float4* boxes, c
     }
   }
   __syncthreads();  // list[] (global) written by this block, read below by all its threads
-  const int nk = greedy_nms_block(total, list, boxes, scores, live_glob, nms_thr, max_det, kept_idx, kept_sc);
+  const int nk = greedy_nms_block<KMAX>(total, list, boxes, scores, live_glob, nms_thr, max_det, kept_idx, kept_sc);
   if (tid == 0) kept_n[blockIdx.x] = nk;
 }
 
@@ -384,7 +387,8 @@ __device__ __forceinline__ float nms_hi(float a, float b) { return a > b ? a : b
 // min / max are idempotent, so the IoU is the same bit for bit); a thread tracks only score and slot of its best survivor,
 // and the wave winner's owner picks that slot's box out of its registers with a select chain when it publishes it; the
 // round's winner lives in scalar registers.  hipcc 7.2: 128 VGPRs, no spill, no scratch (-Rpass-analysis=kernel-resource-usage);
-// each of these choices removed spills, so look at that report after touching the loop.
+// each of these choices removed spills, so look at that report after touching the loop.  KMAX as in greedy_nms_block.
+template <int KMAX>
 __device__ __forceinline__ int greedy_nms_image(const int n, const int* list, const float4* boxes, const float* scores,
                                                 float* live_glob, const float nms_thr, const int max_det, int* kept_idx,
                                                 float* kept_sc) {
@@ -392,8 +396,8 @@ __device__ __forceinline__ int greedy_nms_image(const int n, const int* list, co
   __shared__ float s_ws[2][NMS_W];
   __shared__ int s_wp[2][NMS_W];
   __shared__ float4 s_wb[2][NMS_W];
-  __shared__ int s_kidx[64];
-  __shared__ float s_ksc[64];
+  __shared__ int s_kidx[KMAX];
+  __shared__ float s_ksc[KMAX];
   if (n > NMS_KA * NMS_T) {
     for (int q = tid; q < n; q += NMS_T) live_glob[q] = scores[list[q]];
     __syncthreads();
@@ -509,6 +513,7 @@ __device__ __forceinline__ int greedy_nms_image(const int n, const int* list, co
   return nk;
 }
 
+template <int KMAX>
 __global__ __launch_bounds__(NMS_T) void nms_image_kernel(const float4* boxes, const float* scores, const int* classes,
                                                           int NC, float thr, float nms_thr, int max_det, int* list_g,
                                                           float* live_g, int* kept_idx, float* kept_sc, float* det,
@@ -523,7 +528,7 @@ __global__ __launch_bounds__(NMS_T) void nms_image_kernel(const float4* boxes, c
   det += (size_t)b * max_det * 6;
   const int total = compact_above(scores, NC, thr, list);
   __syncthreads();  // list[] (global) written by this block, read below by all its threads
-  const int nk = greedy_nms_image(total, list, boxes, scores, live_g + (size_t)b * NC, nms_thr, max_det, kept_idx, kept_sc);
+  const int nk = greedy_nms_image<KMAX>(total, list, boxes, scores, live_g + (size_t)b * NC, nms_thr, max_det, kept_idx, kept_sc);
   __syncthreads();  // kept_idx / kept_sc (global) written by this block
   for (int e = tid; e < max_det * 6; e += NMS_T) {
     const int r = e / 6, f = e - r * 6;
@@ -607,6 +612,7 @@ __global__ __launch_bounds__(NMS_T) void bucket_class_kernel(const float* scores
   }
 }
 
+template <int KMAX>
 __global__ __launch_bounds__(NMS_T) void nms_segment_kernel(const float4* boxes, const float* scores, int NC, int C,
                                                             float nms_thr, int max_det, const int* list_g, const int* off_g,
                                                             float* live_g, int* kept_idx, float* kept_sc, int* kept_n) {
@@ -616,7 +622,7 @@ __global__ __launch_bounds__(NMS_T) void nms_segment_kernel(const float4* boxes,
     if (threadIdx.x == 0) kept_n[blockIdx.x] = 0;
     return;
   }
-  const int nk = greedy_nms_block(n, list_g + (size_t)b * NC + o0, boxes + (size_t)b * NC, scores + (size_t)b * NC,
+  const int nk = greedy_nms_block<KMAX>(n, list_g + (size_t)b * NC + o0, boxes + (size_t)b * NC, scores + (size_t)b * NC,
                                   live_g + (size_t)b * NC + o0, nms_thr, max_det, kept_idx + (size_t)blockIdx.x * max_det,
                                   kept_sc + (size_t)blockIdx.x * max_det);
   if (threadIdx.x == 0) kept_n[blockIdx.x] = nk;
@@ -850,13 +856,20 @@ constexpr int PB_PX = 4;
 constexpr int PB_CHUNK = PB_T * PB_PX;
 constexpr int PB_GT = 32;
 constexpr int PB_MAXN = 64;
+constexpr int PB_MAXN_X = DISYOLO_MAX_DET;   // disyolo_mask_paste_iou_batch_x
 
+// MAXN = 64 * NW detections per job: a pixel keeps NW cover words, word w for detections 64 w .. 64 w + 63.  The walk over
+// the detections runs word after word, each word in ascending k, so it visits them in order across a word boundary: the
+// last covering detection owns the pixel of the merged map whatever word it sits in.
+template <int MAXN>
 __global__ __launch_bounds__(PB_T) void mask_paste_iou_batch_kernel(const disyolo_paste_job* jobs, int njobs, int mh, int mw,
                                                                     unsigned long long* conf) {
-  __shared__ unsigned int s_area[PB_MAXN];
-  __shared__ unsigned int s_inter[PB_MAXN * PB_GT];
+  constexpr int NW = MAXN / 64;
+  static_assert(MAXN % 64 == 0 && MAXN <= PB_T, "one thread per detection sets up and flushes the LDS counters");
+  __shared__ unsigned int s_area[MAXN];
+  __shared__ unsigned int s_inter[MAXN * PB_GT];
   __shared__ unsigned int s_conf[16];
-  __shared__ int s_cls[PB_MAXN];
+  __shared__ int s_cls[MAXN];
   int lo = 0, hi = njobs - 1;      // the last job whose first block is <= this block
   while (lo < hi) {
     const int mid = (lo + hi + 1) >> 1;
@@ -866,34 +879,38 @@ __global__ __launch_bounds__(PB_T) void mask_paste_iou_batch_kernel(const disyol
   const int tid = threadIdx.x, lane = tid & 63;
   const int W = j.image_w, total = j.image_h * j.image_w, n = j.n, ng = j.ng;
   const int chunk0 = ((int)blockIdx.x - j.block0) * PB_CHUNK;
-  if (tid < PB_MAXN) {
+  if (tid < MAXN) {
     s_area[tid] = 0;
     s_cls[tid] = tid < n ? j.classids[tid] : -1;
   }
   if (tid < 16) s_conf[tid] = 0;
   __syncthreads();
-  unsigned long long bits[PB_PX];
+  unsigned long long bits[PB_PX][NW];
 #pragma unroll
   for (int p = 0; p < PB_PX; ++p) {
     const int i = chunk0 + p * PB_T + tid;
     const bool valid = i < total;
     const int y = valid ? i / W : 0, x = valid ? i - y * W : 0;
-    unsigned long long b = 0;
     unsigned char mcls = 0;
-    for (int k = 0; k < n; ++k) {
-      const int* r = j.rects + k * 8;
-      unsigned char bit = 0;
-      // (a crop that leaves the mh x mw mask would read outside `masks`: such a row pastes nothing)
-      if (valid && r[0] >= 0 && r[1] >= 0 && r[2] <= mh && r[3] <= mw)
-        bit = paste_bit(j.masks + (size_t)k * mh * mw, mw, r, y, x);
-      if (bit) {
-        b |= 1ull << k;
-        mcls = (unsigned char)(s_cls[k] + 1);
+#pragma unroll
+    for (int w = 0; w < NW; ++w) {
+      unsigned long long b = 0;
+      const int kend = NW == 1 ? n : min(n, 64 * (w + 1));     // (one word: the plan holds n <= 64)
+      for (int k = 64 * w; k < kend; ++k) {
+        const int* r = j.rects + k * 8;
+        unsigned char bit = 0;
+        // (a crop that leaves the mh x mw mask would read outside `masks`: such a row pastes nothing)
+        if (valid && r[0] >= 0 && r[1] >= 0 && r[2] <= mh && r[3] <= mw)
+          bit = paste_bit(j.masks + (size_t)k * mh * mw, mw, r, y, x);
+        if (bit) {
+          b |= 1ull << (k - 64 * w);
+          mcls = (unsigned char)(s_cls[k] + 1);
+        }
+        const int c = __popcll(__ballot(bit));
+        if (lane == 0 && c) atomicAdd(&s_area[k], (unsigned)c);
       }
-      const int c = __popcll(__ballot(bit));
-      if (lane == 0 && c) atomicAdd(&s_area[k], (unsigned)c);
+      bits[p][w] = b;
     }
-    bits[p] = b;
     if (valid) {
       j.merged[i] = mcls;
       if (j.true_map) {
@@ -915,13 +932,20 @@ __global__ __launch_bounds__(PB_T) void mask_paste_iou_batch_kernel(const disyol
 #pragma unroll
       for (int p = 0; p < PB_PX; ++p) {
         const int i = chunk0 + p * PB_T + tid;
-        unsigned long long m = 0;
-        if (bits[p] && i < total && gp[i]) m = bits[p];
-        if (__ballot(m != 0) == 0) continue;      // (wave-uniform)
-        for (int k = 0; k < n; ++k) {
-          if (s_cls[k] != gc) continue;           // (block-uniform)
-          const int c = __popcll(__ballot((m >> k) & 1));
-          if (lane == 0 && c) atomicAdd(&s_inter[k * PB_GT + gg], (unsigned)c);
+        unsigned long long any = 0;
+#pragma unroll
+        for (int w = 0; w < NW; ++w) any |= bits[p][w];
+        const bool on = any && i < total && gp[i];
+#pragma unroll
+        for (int w = 0; w < NW; ++w) {
+          const unsigned long long m = on ? bits[p][w] : 0ull;
+          if (__ballot(m != 0) == 0) continue;      // (wave-uniform)
+          const int kend = NW == 1 ? n : min(n, 64 * (w + 1));     // (one word: the plan holds n <= 64)
+          for (int k = 64 * w; k < kend; ++k) {
+            if (s_cls[k] != gc) continue;           // (block-uniform)
+            const int c = __popcll(__ballot((m >> (k - 64 * w)) & 1));
+            if (lane == 0 && c) atomicAdd(&s_inter[k * PB_GT + gg], (unsigned)c);
+          }
         }
       }
     }
@@ -1004,16 +1028,27 @@ __global__ __launch_bounds__(256) void confusion_n_kernel(const unsigned char* t
 
 }  // namespace
 
-extern "C" size_t disyolo_detect_workspace_hw(int B, int H, int W, int num_class) {
+// the workspace with room for `keep` (>= max_det) kept rows per (image, class)
+static size_t detect_workspace_keep(int B, int H, int W, int num_class, int keep) {
   if (B <= 0 || H <= 0 || W <= 0 || H % 32 || W % 32) return 0;
   const size_t c1 = (size_t)(H / 32) * (W / 32);
   const size_t NC = 3 * (16 * c1 + 4 * c1 + c1);
   // boxes (16 B) + scores + classes, per-class list + live, per-class kept (idx, score, n)
   if (num_class <= 16)
-    return (size_t)B * NC * (16 + 4 + 4) + (size_t)B * num_class * NC * 8 + (size_t)B * num_class * (64 * 8 + 4) + 256;
+    return (size_t)B * NC * (16 + 4 + 4) + (size_t)B * num_class * NC * 8 + (size_t)B * num_class * ((size_t)keep * 8 + 4) + 256;
   // the same prefix, ONE bucketed list + live per image, the class offsets, per-class kept (idx, score, n)
   return (size_t)B * NC * (16 + 4 + 4) + (size_t)B * NC * 8 + (size_t)B * (WD_MAXC + 1) * 4 +
-         (size_t)B * num_class * (64 * 8 + 4) + 256;
+         (size_t)B * num_class * ((size_t)keep * 8 + 4) + 256;
+}
+
+extern "C" size_t disyolo_detect_workspace_hw(int B, int H, int W, int num_class) {
+  return detect_workspace_keep(B, H, W, num_class, 64);
+}
+
+// ... of disyolo_detect_x: the kept lists hold max_det rows, never fewer than the 64 of the other entry points
+extern "C" size_t disyolo_detect_workspace_x(int B, int H, int W, int num_class, int max_det) {
+  if (max_det <= 0 || max_det > DISYOLO_MAX_DET || num_class <= 0 || num_class > WD_MAXC) return 0;
+  return detect_workspace_keep(B, H, W, num_class, max_det > 64 ? max_det : 64);
 }
 
 extern "C" size_t disyolo_detect_workspace(int B, int S, int num_class) {
@@ -1040,37 +1075,67 @@ extern "C" int disyolo_detect_hw(const float* logits3, const float* logits2, con
 
 extern "C" int disyolo_detect_list_capacity(void) { return NMS_KA * NMS_T; }
 
+static int detect_run(const float* logits3, const float* logits2, const float* logits1, int B, int H, int W, int num_class,
+                      const float* anchors_host, const float* clip_window, float obj_thresh, float nms_thresh, int max_det,
+                      int nms_mode, float* detections, int32_t* det_count, void* workspace, size_t workspace_bytes,
+                      void* stream, bool wide);
+
 // ... with the choice of which candidates above the threshold survive (DISYOLO_NMS_*)
 extern "C" int disyolo_detect_nms_hw(const float* logits3, const float* logits2, const float* logits1, int B, int H, int W,
                                      int num_class, const float* anchors_host, const float* clip_window, float obj_thresh,
                                      float nms_thresh, int max_det, int nms_mode, float* detections, int32_t* det_count,
                                      void* workspace, size_t workspace_bytes, void* stream) {
+  return detect_run(logits3, logits2, logits1, B, H, W, num_class, anchors_host, clip_window, obj_thresh, nms_thresh, max_det,
+                    nms_mode, detections, det_count, workspace, workspace_bytes, stream, false);
+}
+
+// ... with up to DISYOLO_MAX_DET rows per image: the winners' lists of the greedy loops hold 256, and up to 16 classes
+// whose C * max_det kept rows pass the LDS rank merge's 512 go through the k-way merge of the longer class lists (its
+// layout is nms_class_kernel's kept lists).  The workspace is disyolo_detect_workspace_x's.  max_det <= 64 launches the
+// same kernel instances as disyolo_detect_nms_hw.
+extern "C" int disyolo_detect_x(const float* logits3, const float* logits2, const float* logits1, int B, int H, int W,
+                                int num_class, const float* anchors_host, const float* clip_window, float obj_thresh,
+                                float nms_thresh, int max_det, int nms_mode, float* detections, int32_t* det_count,
+                                void* workspace, size_t workspace_bytes, void* stream) {
+  return detect_run(logits3, logits2, logits1, B, H, W, num_class, anchors_host, clip_window, obj_thresh, nms_thresh, max_det,
+                    nms_mode, detections, det_count, workspace, workspace_bytes, stream, true);
+}
+
+static int detect_run(const float* logits3, const float* logits2, const float* logits1, int B, int H, int W, int num_class,
+                      const float* anchors_host, const float* clip_window, float obj_thresh, float nms_thresh, int max_det,
+                      int nms_mode, float* detections, int32_t* det_count, void* workspace, size_t workspace_bytes,
+                      void* stream, bool wide) {
   DY_REQUIRE(nms_mode == DISYOLO_NMS_PER_CLASS || nms_mode == DISYOLO_NMS_AGNOSTIC || nms_mode == DISYOLO_NMS_NONE,
              "detect: nms_mode must be 0 (per class), 1 (class-agnostic) or 2 (none) (got %d)", nms_mode);
   DY_REQUIRE(logits3 && logits2 && logits1 && anchors_host && clip_window && detections && det_count,
              "detect: null pointer");
   DY_REQUIRE(B > 0 && H > 0 && W > 0 && H % 32 == 0 && W % 32 == 0 && num_class > 0 && num_class <= WD_MAXC,
              "detect: bad sizes");
-  DY_REQUIRE(max_det > 0 && max_det <= 64 && (num_class > 16 || num_class * max_det <= MAX_KEEP),
-             "detect: max_det must be <= 64");
+  if (wide)
+    DY_REQUIRE(max_det > 0 && max_det <= DISYOLO_MAX_DET, "detect_x: max_det must be in 1..%d (got %d)", DISYOLO_MAX_DET,
+               max_det);
+  else
+    DY_REQUIRE(max_det > 0 && max_det <= 64 && (num_class > 16 || num_class * max_det <= MAX_KEEP),
+               "detect: max_det must be <= 64");
   DY_REQUIRE(obj_thresh >= 0.f, "detect: obj_thresh must be >= 0");
-  if (!workspace || workspace_bytes < disyolo_detect_workspace_hw(B, H, W, num_class)) {
+  const int keep = wide && max_det > 64 ? max_det : 64;     // rows of a kept list in the workspace
+  const size_t ws_need = detect_workspace_keep(B, H, W, num_class, keep);
+  if (!workspace || workspace_bytes < ws_need) {
     disyolo_set_error("detect: workspace too small");
     return DISYOLO_E_WORKSPACE;
   }
   if (nms_mode != DISYOLO_NMS_PER_CLASS) {
     // decode results, ONE list + live per image, max_det kept (idx, score): inside what any class count's workspace holds
     const size_t NC = (size_t)3 * 21 * (H / 32) * (W / 32);
-    DY_REQUIRE((size_t)B * NC * (16 + 4 + 4) + (size_t)B * NC * 8 + (size_t)B * max_det * 8 <=
-                   disyolo_detect_workspace_hw(B, H, W, num_class),
+    DY_REQUIRE((size_t)B * NC * (16 + 4 + 4) + (size_t)B * NC * 8 + (size_t)B * max_det * 8 <= ws_need,
                "detect: the workspace does not hold an image-wide list");
   }
   {
     std::array<float, 18> anc;
     for (int i = 0; i < 18; ++i) anc[i] = anchors_host[i];
     DY_RECORD_OR_RUN([=](void* s) {
-      return disyolo_detect_nms_hw(logits3, logits2, logits1, B, H, W, num_class, anc.data(), clip_window, obj_thresh,
-                                   nms_thresh, max_det, nms_mode, detections, det_count, workspace, workspace_bytes, s);
+      return detect_run(logits3, logits2, logits1, B, H, W, num_class, anc.data(), clip_window, obj_thresh, nms_thresh,
+                        max_det, nms_mode, detections, det_count, workspace, workspace_bytes, s, wide);
     });
   }
   DecodeParams p;
@@ -1095,6 +1160,7 @@ extern "C" int disyolo_detect_nms_hw(const float* logits3, const float* logits2,
   p.scores = (float*)ws;                  ws += (size_t)B * c0 * 4;
   p.classes = (int*)ws;                   ws += (size_t)B * c0 * 4;
   hipStream_t st = (hipStream_t)stream;
+  const bool k256 = max_det > 64;         // the instances with 256 winners per list
   if (nms_mode != DISYOLO_NMS_PER_CLASS) {
     int* list = (int*)ws;                 ws += (size_t)B * c0 * 4;
     float* live = (float*)ws;             ws += (size_t)B * c0 * 4;
@@ -1102,7 +1168,7 @@ extern "C" int disyolo_detect_nms_hw(const float* logits3, const float* logits2,
     float* kept_sc = (float*)ws;
     hipLaunchKernelGGL(decode_score_kernel, dim3(ceil_div(c0, 256), B), dim3(256), 0, st, p);
     DY_CHECK_LAUNCH();
-    hipLaunchKernelGGL(nms_image_kernel, dim3(B), dim3(NMS_T), 0, st, p.boxes, p.scores, p.classes, c0, obj_thresh,
+    hipLaunchKernelGGL(k256 ? nms_image_kernel<256> : nms_image_kernel<64>, dim3(B), dim3(NMS_T), 0, st, p.boxes, p.scores, p.classes, c0, obj_thresh,
                        nms_mode == DISYOLO_NMS_NONE ? INFINITY : nms_thresh, max_det, list, live, kept_idx, kept_sc,
                        detections, det_count);
     DY_CHECK_LAUNCH();
@@ -1112,15 +1178,15 @@ extern "C" int disyolo_detect_nms_hw(const float* logits3, const float* logits2,
     int* list = (int*)ws;                 ws += (size_t)B * c0 * 4;
     float* live = (float*)ws;             ws += (size_t)B * c0 * 4;
     int* off = (int*)ws;                  ws += (size_t)B * (WD_MAXC + 1) * 4;
-    int* kept_idx = (int*)ws;             ws += (size_t)B * num_class * 64 * 4;
-    float* kept_sc = (float*)ws;          ws += (size_t)B * num_class * 64 * 4;
+    int* kept_idx = (int*)ws;             ws += (size_t)B * num_class * keep * 4;
+    float* kept_sc = (float*)ws;          ws += (size_t)B * num_class * keep * 4;
     int* kept_n = (int*)ws;
     hipLaunchKernelGGL(decode_score_kernel, dim3(ceil_div(c0, 256), B), dim3(256), 0, st, p);
     DY_CHECK_LAUNCH();
     hipLaunchKernelGGL(bucket_class_kernel, dim3(B), dim3(NMS_T), 0, st, p.scores, p.classes, c0, num_class, obj_thresh,
                        list, off);
     DY_CHECK_LAUNCH();
-    hipLaunchKernelGGL(nms_segment_kernel, dim3(B * num_class), dim3(NMS_T), 0, st, p.boxes, p.scores, c0, num_class,
+    hipLaunchKernelGGL(k256 ? nms_segment_kernel<256> : nms_segment_kernel<64>, dim3(B * num_class), dim3(NMS_T), 0, st, p.boxes, p.scores, c0, num_class,
                        nms_thresh, max_det, list, off, live, kept_idx, kept_sc, kept_n);
     DY_CHECK_LAUNCH();
     hipLaunchKernelGGL(nms_merge_kway_kernel, dim3(B), dim3(64), 0, st, p.boxes, p.classes, c0, num_class, max_det,
@@ -1130,16 +1196,20 @@ extern "C" int disyolo_detect_nms_hw(const float* logits3, const float* logits2,
   }
   int* list = (int*)ws;                   ws += (size_t)B * num_class * c0 * 4;
   float* live = (float*)ws;               ws += (size_t)B * num_class * c0 * 4;
-  int* kept_idx = (int*)ws;               ws += (size_t)B * num_class * 64 * 4;
-  float* kept_sc = (float*)ws;            ws += (size_t)B * num_class * 64 * 4;
+  int* kept_idx = (int*)ws;               ws += (size_t)B * num_class * keep * 4;
+  float* kept_sc = (float*)ws;            ws += (size_t)B * num_class * keep * 4;
   int* kept_n = (int*)ws;
   hipLaunchKernelGGL(decode_score_kernel, dim3(ceil_div(c0, 256), B), dim3(256), 0, st, p);
   DY_CHECK_LAUNCH();
-  hipLaunchKernelGGL(nms_class_kernel, dim3(B * num_class), dim3(NMS_T), 0, st, p.boxes, p.scores, p.classes, c0,
+  hipLaunchKernelGGL(k256 ? nms_class_kernel<256> : nms_class_kernel<64>, dim3(B * num_class), dim3(NMS_T), 0, st, p.boxes, p.scores, p.classes, c0,
                      num_class, obj_thresh, nms_thresh, max_det, list, live, kept_idx, kept_sc, kept_n);
   DY_CHECK_LAUNCH();
-  hipLaunchKernelGGL(nms_merge_kernel, dim3(B), dim3(64), 0, st, p.boxes, p.classes, c0, num_class, max_det, kept_idx,
-                     kept_sc, kept_n, detections, det_count);
+  if (num_class * max_det <= MAX_KEEP)
+    hipLaunchKernelGGL(nms_merge_kernel, dim3(B), dim3(64), 0, st, p.boxes, p.classes, c0, num_class, max_det, kept_idx,
+                       kept_sc, kept_n, detections, det_count);
+  else      // (disyolo_detect_x alone) more survivors than the rank merge's LDS holds
+    hipLaunchKernelGGL(nms_merge_kway_kernel, dim3(B), dim3(64), 0, st, p.boxes, p.classes, c0, num_class, max_det,
+                       kept_idx, kept_sc, kept_n, detections, det_count);
   DY_CHECK_LAUNCH();
   return DISYOLO_OK;
 }
@@ -1194,12 +1264,12 @@ extern "C" size_t disyolo_paste_job_size(void) { return sizeof(disyolo_paste_job
 
 // validates a HOST table of jobs and lays the jobs' blocks out: block0 = the first block of each job; returns the number of
 // blocks of the launch, or a negative code
-extern "C" int disyolo_paste_job_plan(disyolo_paste_job* jobs, int njobs) {
+static int paste_job_plan_cap(disyolo_paste_job* jobs, int njobs, int cap) {
   DY_REQUIRE(jobs && njobs > 0, "paste_job_plan: null table or njobs <= 0");
   int64_t blocks = 0;
   for (int i = 0; i < njobs; ++i) {
     const disyolo_paste_job& j = jobs[i];
-    DY_REQUIRE(j.n >= 0 && j.n <= PB_MAXN, "paste job %d: n must be in 0..64 (got %d)", i, j.n);
+    DY_REQUIRE(j.n >= 0 && j.n <= cap, "paste job %d: n must be in 0..%d (got %d)", i, cap, j.n);
     DY_REQUIRE(j.ng >= 0, "paste job %d: ng < 0", i);
     DY_REQUIRE(j.image_h > 0 && j.image_w > 0 && (int64_t)j.image_h * j.image_w <= (1ll << 30), "paste job %d: bad image size", i);
     DY_REQUIRE(j.merged, "paste job %d: merged is NULL", i);
@@ -1212,6 +1282,16 @@ extern "C" int disyolo_paste_job_plan(disyolo_paste_job* jobs, int njobs) {
   return (int)blocks;
 }
 
+extern "C" int disyolo_paste_job_plan(disyolo_paste_job* jobs, int njobs) { return paste_job_plan_cap(jobs, njobs, PB_MAXN); }
+
+// ... for jobs of up to DISYOLO_MAX_DET detections (disyolo_mask_paste_iou_batch_x)
+extern "C" int disyolo_paste_job_plan_x(disyolo_paste_job* jobs, int njobs) {
+  return paste_job_plan_cap(jobs, njobs, PB_MAXN_X);
+}
+
+static int mask_paste_iou_batch_run(const disyolo_paste_job* jobs_host, const disyolo_paste_job* jobs, int njobs, int map_h,
+                                    int map_w, int64_t* conf, void* stream, int cap);
+
 extern "C" int disyolo_mask_paste_iou_batch(const disyolo_paste_job* jobs_host, const disyolo_paste_job* jobs, int njobs, int size,
                                             int64_t* conf, void* stream) {
   DY_REQUIRE(size > 0 || !(jobs_host && jobs && njobs > 0), "mask_paste_iou_batch: size must be > 0");
@@ -1220,18 +1300,32 @@ extern "C" int disyolo_mask_paste_iou_batch(const disyolo_paste_job* jobs_host, 
 
 extern "C" int disyolo_mask_paste_iou_batch_hw(const disyolo_paste_job* jobs_host, const disyolo_paste_job* jobs, int njobs,
                                                int map_h, int map_w, int64_t* conf, void* stream) {
+  return mask_paste_iou_batch_run(jobs_host, jobs, njobs, map_h, map_w, conf, stream, PB_MAXN);
+}
+
+// ... with up to DISYOLO_MAX_DET detections per job (a table planned by disyolo_paste_job_plan_x): the same counts layout;
+// a table whose jobs all hold <= 64 detections launches the one-word kernel of disyolo_mask_paste_iou_batch_hw
+extern "C" int disyolo_mask_paste_iou_batch_x(const disyolo_paste_job* jobs_host, const disyolo_paste_job* jobs, int njobs,
+                                              int map_h, int map_w, int64_t* conf, void* stream) {
+  return mask_paste_iou_batch_run(jobs_host, jobs, njobs, map_h, map_w, conf, stream, PB_MAXN_X);
+}
+
+static int mask_paste_iou_batch_run(const disyolo_paste_job* jobs_host, const disyolo_paste_job* jobs, int njobs, int map_h,
+                                    int map_w, int64_t* conf, void* stream, int cap) {
   DY_REQUIRE(jobs_host && jobs && njobs > 0, "mask_paste_iou_batch: null table or njobs <= 0");
   DY_REQUIRE(map_h > 0 && map_w > 0, "mask_paste_iou_batch: size must be > 0");
   // the host copy is what this call can check and size the grid from; it must be a planned table (disyolo_paste_job_plan)
   std::vector<disyolo_paste_job> plan(jobs_host, jobs_host + njobs);
-  const int blocks = disyolo_paste_job_plan(plan.data(), njobs);
+  const int blocks = paste_job_plan_cap(plan.data(), njobs, cap);
   if (blocks < 0) return blocks;
+  int nmax = 0;
   for (int i = 0; i < njobs; ++i) {
+    nmax = plan[i].n > nmax ? plan[i].n : nmax;
     DY_REQUIRE(plan[i].block0 == jobs_host[i].block0, "mask_paste_iou_batch: job %d is not planned (disyolo_paste_job_plan)", i);
     DY_REQUIRE(!jobs_host[i].true_map || conf, "mask_paste_iou_batch: job %d has a true_map but conf is NULL", i);
   }
-  DY_RECORD_OR_RUN([=](void* s) { return disyolo_mask_paste_iou_batch_hw(plan.data(), jobs, njobs, map_h, map_w, conf, s); });
-  hipLaunchKernelGGL(mask_paste_iou_batch_kernel, dim3(blocks), dim3(PB_T), 0, (hipStream_t)stream, jobs, njobs, map_h, map_w,
+  DY_RECORD_OR_RUN([=](void* s) { return mask_paste_iou_batch_run(plan.data(), jobs, njobs, map_h, map_w, conf, s, cap); });
+  hipLaunchKernelGGL(nmax > PB_MAXN ? mask_paste_iou_batch_kernel<PB_MAXN_X> : mask_paste_iou_batch_kernel<PB_MAXN>, dim3(blocks), dim3(PB_T), 0, (hipStream_t)stream, jobs, njobs, map_h, map_w,
                      (unsigned long long*)conf);
   DY_CHECK_LAUNCH();
   return DISYOLO_OK;

@@ -42,8 +42,10 @@ struct YoloLoss3 {
   YoloLossParams p[3];
   int gx[3];
 };
+// TB >= G: the true boxes staged in LDS (64 up to max_boxes = 64, DISYOLO_MAX_BOXES = 256 beyond)
+template <int TB>
 __device__ __forceinline__ void yolo_loss_body(const YoloLossParams& p, const int bx, const int gx) {
-  __shared__ float s_tb[64 * 4];
+  __shared__ float s_tb[TB * 4];
   __shared__ float s_red[4][5];
   const int b = blockIdx.y;
   for (int i = threadIdx.x; i < p.G * 4; i += 256) {
@@ -141,6 +143,7 @@ __device__ __forceinline__ void yolo_loss_body(const YoloLossParams& p, const in
     p.partial[((size_t)blockIdx.y * gx + bx) * 5 + threadIdx.x] = v;
   }
 }
+template <int TB>
 __global__ __launch_bounds__(256) void yolo_loss_kernel(YoloLoss3 P) {
   int bx = blockIdx.x, s = 0;
   if (bx >= P.gx[0]) {
@@ -151,7 +154,7 @@ __global__ __launch_bounds__(256) void yolo_loss_kernel(YoloLoss3 P) {
       s = 2;
     }
   }
-  yolo_loss_body(P.p[s], bx, P.gx[s]);
+  yolo_loss_body<TB>(P.p[s], bx, P.gx[s]);
 }
 
 // ---- class lists past the 32-channel rows: 3 (5 + C) <= ld <= 256, 1 <= C <= 80 ----
@@ -174,8 +177,9 @@ __device__ __forceinline__ float quad_sum(float v) {   // (v0 + v1) + (v2 + v3) 
   return v + __shfl_xor(v, 2, 64);
 }
 
+template <int TB>
 __device__ __forceinline__ void yolo_loss_wide_body(const YoloLossParams& p, const int ld, const int bx, const int gx) {
-  __shared__ float s_tb[64 * 4];
+  __shared__ float s_tb[TB * 4];
   __shared__ float s_red[4][5];
   __shared__ float s_t[WL_ROWS * WL_MAXD];   // logits of the chunk, then their gradients
   __shared__ float s_l[WL_ROWS * WL_MAXD];   // labels of the chunk
@@ -299,6 +303,7 @@ __device__ __forceinline__ void yolo_loss_wide_body(const YoloLossParams& p, con
   __syncthreads();
   if (tid < 5) p.partial[((size_t)blockIdx.y * gx + bx) * 5 + tid] = s_red[0][tid] + s_red[1][tid] + s_red[2][tid] + s_red[3][tid];
 }
+template <int TB>
 __global__ __launch_bounds__(256) void yolo_loss_wide_kernel(YoloLoss3 P, int ld) {
   int bx = blockIdx.x, s = 0;
   if (bx >= P.gx[0]) {
@@ -309,7 +314,7 @@ __global__ __launch_bounds__(256) void yolo_loss_wide_kernel(YoloLoss3 P, int ld
       s = 2;
     }
   }
-  yolo_loss_wide_body(P.p[s], ld, bx, P.gx[s]);
+  yolo_loss_wide_body<TB>(P.p[s], ld, bx, P.gx[s]);
 }
 
 __device__ __forceinline__ double wave_sum_d(double v) {
@@ -346,9 +351,11 @@ __device__ __forceinline__ unsigned hash32(unsigned x) {
   x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
   return x;
 }
-__global__ __launch_bounds__(64) void shuffle_perm_kernel(int* perm_a, int na, int* perm_b, int nb, unsigned seed,
-                                                          const int64_t* step) {
-  __shared__ unsigned keys[64];
+// T threads rank up to T keys: 64 for n <= 64, 256 beyond.  Key and rank of an index do not depend on T.
+template <int T>
+__global__ __launch_bounds__(T) void shuffle_perm_kernel(int* perm_a, int na, int* perm_b, int nb, unsigned seed,
+                                                         const int64_t* step) {
+  __shared__ unsigned keys[T];
   const int b = blockIdx.x, t = threadIdx.x;
   const unsigned st = step ? (unsigned)*step : 0u;
   for (int which = 0; which < 2; ++which) {
@@ -482,6 +489,146 @@ __global__ __launch_bounds__(64) void mask_rois_kernel(const float* det_g, int m
   for (int r = cnt; r < ROI_MAX; ++r)
     for (int k = 0; k < RW; ++k) out[r * RW + k] = 0;
   roi_count[b] = cnt;
+}
+
+// The selection for up to MR_MAX = 256 detections and ground-truth boxes: the same rows as mask_rois_kernel, with the two
+// parts that grow with the row count spread over the wave.  The trimmed row lists are built by ordered ballots, 64 rows a
+// round, into LDS; lane 0 then runs the order-defining pick (first n_det / n_gt in permuted order, <= ROI_MAX rows) and
+// leaves the RoI boxes in LDS; each RoI's IoU arg-max over the trimmed ground-truth rows is taken across the lanes -- lane l
+// walks rows l, l + 64, ... in ascending order with the serial form's strict "iou > best" (NaN never wins), and the lanes
+// combine by (greater IoU, then lower row), which is "the first maximum wins".  The IoU is the serial form's, operation by
+// operation.  (Serial, G = 256 costs ~10 RoIs x 256 dependent IoUs on one lane of the chain that holds up the mask subnet's
+// backward pass.)
+constexpr int MR_MAX = 256;
+template <int K>
+__global__ __launch_bounds__(64) void mask_rois_wave_kernel(const float* det_g, int max_det, const float* true_boxes_g, int G,
+                                                            const int* perm_det_g, const int* perm_gt_g, int B, int Hm, int Wm,
+                                                            int n_det, int n_gt, float iou_thr, int* rois, int* roi_count) {
+  constexpr int RW = roi_w(K);
+  __shared__ float s_det[MR_MAX * 6];
+  __shared__ float s_tb[MR_MAX * 5];
+  __shared__ int s_pd[MR_MAX], s_pg[MR_MAX];
+  __shared__ int s_prow[MR_MAX], s_grow[MR_MAX];
+  __shared__ float s_rb[ROI_MAX][4];
+  __shared__ int s_nr;
+  const int b = blockIdx.x, lane = threadIdx.x;
+  if (b >= B) return;
+  if (max_det > MR_MAX) max_det = MR_MAX;      // (the entry point refuses more)
+  if (G > MR_MAX) G = MR_MAX;
+  for (int i = lane; i < max_det * 6; i += 64) s_det[i] = det_g[(size_t)b * max_det * 6 + i];
+  for (int i = lane; i < G * 5; i += 64) s_tb[i] = true_boxes_g[(size_t)b * G * 5 + i];
+  for (int i = lane; i < max_det; i += 64) s_pd[i] = perm_det_g ? perm_det_g[b * max_det + i] : i;
+  for (int i = lane; i < G; i += 64) s_pg[i] = perm_gt_g ? perm_gt_g[b * G + i] : i;
+  __syncthreads();
+  // trimmed lists (rows whose |coords| sum is non-zero), in row order
+  const unsigned long long below = (1ull << lane) - 1ull;
+  int np = 0, ng = 0;
+  for (int base = 0; base < max_det; base += 64) {
+    const int r = base + lane;
+    bool f = false;
+    if (r < max_det) {
+      const float* d = s_det + r * 6;
+      f = fabsf(d[0]) + fabsf(d[1]) + fabsf(d[2]) + fabsf(d[3]) != 0.f;
+    }
+    const unsigned long long m = __ballot(f);
+    if (f) s_prow[np + __popcll(m & below)] = r;
+    np += __popcll(m);
+  }
+  for (int base = 0; base < G; base += 64) {
+    const int r = base + lane;
+    bool f = false;
+    if (r < G) {
+      const float* t = s_tb + r * 5;
+      f = fabsf(t[0]) + fabsf(t[1]) + fabsf(t[2]) + fabsf(t[3]) != 0.f;
+    }
+    const unsigned long long m = __ballot(f);
+    if (f) s_grow[ng + __popcll(m & below)] = r;
+    ng += __popcll(m);
+  }
+  __syncthreads();
+  // shuffled selection: first n_det proposals and first n_gt GT boxes in permuted order (sequential: it defines the order)
+  if (lane == 0) {
+    int nr = 0;
+    for (int q = 0, taken = 0; q < max_det && taken < n_det && nr < ROI_MAX; ++q) {
+      const int j = s_pd[q];
+      if (j < 0 || j >= np) continue;
+      const float* d = s_det + s_prow[j] * 6;
+      s_rb[nr][0] = d[0]; s_rb[nr][1] = d[1]; s_rb[nr][2] = d[2]; s_rb[nr][3] = d[3];
+      ++nr; ++taken;
+    }
+    for (int q = 0, taken = 0; q < G && taken < n_gt && nr < ROI_MAX; ++q) {
+      const int j = s_pg[q];
+      if (j < 0 || j >= ng) continue;
+      const float* t = s_tb + s_grow[j] * 5;
+      s_rb[nr][0] = t[1] - t[3] / 2.f; s_rb[nr][1] = t[0] - t[2] / 2.f;
+      s_rb[nr][2] = t[1] + t[3] / 2.f; s_rb[nr][3] = t[0] + t[2] / 2.f;
+      ++nr; ++taken;
+    }
+    s_nr = nr;
+  }
+  __syncthreads();
+  const int nr = s_nr;
+  int cnt = 0;
+  int* out = rois + (size_t)b * ROI_MAX * RW;
+  for (int r = 0; r < nr; ++r) {
+    const float r0 = s_rb[r][0], r1 = s_rb[r][1], r2 = s_rb[r][2], r3 = s_rb[r][3];
+    float best = -INFINITY;
+    int arg = 0x7fffffff;
+    for (int j = lane; j < ng; j += 64) {
+      const float* t = s_tb + s_grow[j] * 5;
+      const float gy1 = t[1] - t[3] / 2.f, gx1 = t[0] - t[2] / 2.f, gy2 = t[1] + t[3] / 2.f, gx2 = t[0] + t[2] / 2.f;
+      const float y1 = fmaxf(r0, gy1), x1 = fmaxf(r1, gx1);
+      const float y2 = fminf(r2, gy2), x2 = fminf(r3, gx2);
+      const float inter = fmaxf(x2 - x1, 0.f) * fmaxf(y2 - y1, 0.f);
+      const float a1 = (r2 - r0) * (r3 - r1);
+      const float a2 = (gy2 - gy1) * (gx2 - gx1);
+      const float iou = inter / (a1 + a2 - inter);
+      if (iou > best) {  // this lane's first maximum; NaN never wins
+        best = iou;
+        arg = j;
+      }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const float v2 = __shfl_xor(best, o, 64);
+      const int a2 = __shfl_xor(arg, o, 64);
+      if (v2 > best || (v2 == best && a2 < arg)) {
+        best = v2;
+        arg = a2;
+      }
+    }
+    if (arg == 0x7fffffff) arg = 0;     // nothing won (every IoU NaN or -inf): the serial form's arg = 0, best = -inf
+    if (ng > 0 && best >= iou_thr) {    // (wave-uniform)
+      if (lane == 0) {
+        // y-coordinates scale by the map's height, x-coordinates by its width (the reference's one `size` at Hm = Wm, :842)
+        const float szy = (float)Hm, szx = (float)Wm;
+        const float y1 = rintf(r0 * szy), x1 = rintf(r1 * szx);
+        const float y2 = rintf(r2 * szy), x2 = rintf(r3 * szx);
+        int gy[K + 1], gx[K + 1];
+        bin_edges<K>(y1, y2, gy);
+        bin_edges<K>(x1, x2, gx);
+        int* o = out + cnt * RW;
+        for (int k = 0; k <= K; ++k) {
+          o[k] = gy[k];
+          o[K + 1 + k] = gx[k];
+        }
+        o[2 * K + 2] = s_grow[arg];
+        // mask_object pixel count (:848): sum over the k*k bins, clipped to the map
+        int area = 0;
+        for (int by = 0; by < K; ++by)
+          for (int bx = 0; bx < K; ++bx) {
+            const int hh = min(gy[by + 1], Hm) - max(gy[by], 0), ww = min(gx[bx + 1], Wm) - max(gx[bx], 0);
+            if (hh > 0 && ww > 0) area += hh * ww;
+          }
+        o[2 * K + 3] = area;
+        o[2 * K + 4] = 1;
+        o[2 * K + 5] = 0;
+      }
+      ++cnt;
+    }
+  }
+  for (int e = cnt * RW + lane; e < ROI_MAX * RW; e += 64) out[e] = 0;
+  if (lane == 0) roi_count[b] = cnt;
 }
 
 // one thread = one score-map pixel; loops the image's positive RoIs.  score rows have k*k channels, dscore rows
@@ -631,10 +778,13 @@ static int yolo_loss_launch(const float* const logits[3], const float* const lab
     nblk[s] = P.gx[s] * B;
     part += (size_t)nblk[s] * 5;
   }
+  const bool tb256 = max_boxes > 64;      // (disyolo_yolo_loss_hw alone)
   if (ld)
-    hipLaunchKernelGGL(yolo_loss_wide_kernel, dim3(P.gx[0] + P.gx[1] + P.gx[2], B), dim3(256), 0, st, P, ld);
+    hipLaunchKernelGGL(tb256 ? yolo_loss_wide_kernel<DISYOLO_MAX_BOXES> : yolo_loss_wide_kernel<64>,
+                       dim3(P.gx[0] + P.gx[1] + P.gx[2], B), dim3(256), 0, st, P, ld);
   else
-    hipLaunchKernelGGL(yolo_loss_kernel, dim3(P.gx[0] + P.gx[1] + P.gx[2], B), dim3(256), 0, st, P);
+    hipLaunchKernelGGL(tb256 ? yolo_loss_kernel<DISYOLO_MAX_BOXES> : yolo_loss_kernel<64>,
+                       dim3(P.gx[0] + P.gx[1] + P.gx[2], B), dim3(256), 0, st, P);
   DY_CHECK_LAUNCH();
   hipLaunchKernelGGL(yolo_loss_final_kernel, dim3(1), dim3(320), 0, st, (const float*)workspace,
                      nblk[0] + nblk[1] + nblk[2], 1.f / (float)B, losses);
@@ -718,7 +868,8 @@ extern "C" int disyolo_yolo_loss_hw(const float* const logits[3], const float* c
                "yolo_loss_hw: bad sizes (dlogits_ld must be 0 or a multiple of 32 in [3 (5 + num_class), 256], got %d)",
                dlogits_ld);
   }
-  DY_REQUIRE(max_boxes > 0 && max_boxes <= 64, "yolo_loss_hw: max_boxes must be in 1..64");
+  DY_REQUIRE(max_boxes > 0 && max_boxes <= DISYOLO_MAX_BOXES, "yolo_loss_hw: max_boxes must be in 1..%d (got %d)",
+             DISYOLO_MAX_BOXES, max_boxes);
   if (!workspace || workspace_bytes < disyolo_yolo_loss_workspace_hw(B, H, W, num_class)) {
     disyolo_set_error("yolo_loss_hw: workspace too small");
     return DISYOLO_E_WORKSPACE;
@@ -740,10 +891,16 @@ extern "C" int disyolo_yolo_loss_hw(const float* const logits[3], const float* c
 
 extern "C" int disyolo_shuffle_perm(int32_t* perm_det, int n_det, int32_t* perm_gt, int n_gt, int B, uint32_t seed,
                                     const int64_t* step_counter, void* stream) {
-  DY_REQUIRE(perm_det && perm_gt && B > 0 && n_det > 0 && n_det <= 64 && n_gt > 0 && n_gt <= 64, "shuffle_perm: bad args");
+  DY_REQUIRE(perm_det && perm_gt && B > 0, "shuffle_perm: bad args");
+  DY_REQUIRE(n_det > 0 && n_det <= 256 && n_gt > 0 && n_gt <= 256, "shuffle_perm: n_det and n_gt must be in 1..256 (got %d, %d)",
+             n_det, n_gt);
   DY_RECORD_OR_RUN([=](void* s) { return disyolo_shuffle_perm(perm_det, n_det, perm_gt, n_gt, B, seed, step_counter, s); });
-  hipLaunchKernelGGL(shuffle_perm_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, perm_det, n_det, perm_gt, n_gt, seed,
-                     step_counter);
+  if (n_det <= 64 && n_gt <= 64)
+    hipLaunchKernelGGL(shuffle_perm_kernel<64>, dim3(B), dim3(64), 0, (hipStream_t)stream, perm_det, n_det, perm_gt, n_gt,
+                       seed, step_counter);
+  else
+    hipLaunchKernelGGL(shuffle_perm_kernel<256>, dim3(B), dim3(256), 0, (hipStream_t)stream, perm_det, n_det, perm_gt, n_gt,
+                       seed, step_counter);
   DY_CHECK_LAUNCH();
   return DISYOLO_OK;
 }
@@ -764,13 +921,17 @@ extern "C" int disyolo_mask_rois_hw(const float* detections, int max_det, const 
                                     void* stream) {
   DY_REQUIRE(detections && true_boxes && rois && roi_count, "mask_rois: null pointer");
   DY_REQUIRE(kmap_supported(k), "mask_rois: k must be one of k = 3, 5, 7 (got %d)", k);
-  DY_REQUIRE(B > 0 && max_det > 0 && max_det <= 64 && G > 0 && G <= 64 && map_h > 0 && map_w > 0, "mask_rois: bad sizes");
+  DY_REQUIRE(B > 0 && map_h > 0 && map_w > 0, "mask_rois: bad sizes");
+  DY_REQUIRE(max_det > 0 && max_det <= DISYOLO_MAX_DET && G > 0 && G <= DISYOLO_MAX_BOXES,
+             "mask_rois: bad sizes (max_det must be in 1..%d and G in 1..%d, got %d and %d)", DISYOLO_MAX_DET,
+             DISYOLO_MAX_BOXES, max_det, G);
   DY_REQUIRE(n_det >= 0 && n_gt >= 0 && n_det + n_gt <= ROI_MAX, "mask_rois: n_det + n_gt > %d", ROI_MAX);
   DY_RECORD_OR_RUN([=](void* s) {
     return disyolo_mask_rois_hw(detections, max_det, true_boxes, G, perm_det, perm_gt, B, map_h, map_w, k, n_det, n_gt,
                                 iou_thresh, rois, roi_count, s);
   });
   auto kern = k == 3 ? mask_rois_kernel<3> : k == 5 ? mask_rois_kernel<5> : mask_rois_kernel<7>;
+  if (max_det > 64 || G > 64) kern = k == 3 ? mask_rois_wave_kernel<3> : k == 5 ? mask_rois_wave_kernel<5> : mask_rois_wave_kernel<7>;
   hipLaunchKernelGGL(kern, dim3(B), dim3(64), 0, (hipStream_t)stream, detections, max_det, true_boxes, G, perm_det,
                      perm_gt, B, map_h, map_w, n_det, n_gt, iou_thresh, rois, roi_count);
   DY_CHECK_LAUNCH();

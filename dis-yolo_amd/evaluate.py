@@ -258,10 +258,11 @@ class MAP(object):
             j["counts"] = counts.data_ptr() + cnt_off[b] * 4
             j["n"], j["ng"] = max_det, 0 if gt is None else int(gt.shape[0])
             j["image_h"], j["image_w"] = image_h, image_w
-        L.paste_job_plan(jobs)
+        wide = max_det > 64                                  # more detections than one cover word per pixel holds
+        L.paste_job_plan(jobs, wide=wide)
         hbuf[:jobs.nbytes] = jobs.view(np.uint8)
         dbuf.copy_(torch.from_numpy(hbuf))                                                       # the one upload
-        L.mask_paste_iou_batch(jobs, dbuf, size, conf if (tms and fused_conf) else None)
+        L.mask_paste_iou_batch(jobs, dbuf, size, conf if (tms and fused_conf) else None, wide=wide)
         if tms and not fused_conf:
             for tm, merged in zip(tms, out):
                 self._add_confusion(tm, merged, conf)

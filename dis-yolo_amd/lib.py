@@ -17,6 +17,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DISYOLO_LIB", os.path.join(_HERE, "libdisyolo_hip.so"))
 
 GRAD_LD = 32
+MAX_BOXES = 256            # DISYOLO_MAX_BOXES: ground-truth boxes per image (yolo_loss, mask_rois, shuffle_perm)
+MAX_DET = 256              # DISYOLO_MAX_DET: detections per image (detect, mask_rois, the batched paste)
 ROI_MAX = 16
 ROI_W = 12
 K_MAPS = (3, 5, 7)          # position-sensitive grids the mask path covers (the reference's list)
@@ -140,6 +142,9 @@ _SIGS = {
     "disyolo_detect_list_capacity": (C.c_int, []),
     "disyolo_detect_nms_hw": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 4 + [C.c_void_p] * 2 +
                               [C.c_float, C.c_float, C.c_int, C.c_int] + [C.c_void_p] * 3 + [C.c_size_t, C.c_void_p]),
+    "disyolo_detect_workspace_x": (C.c_size_t, [C.c_int] * 5),
+    "disyolo_detect_x": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 4 + [C.c_void_p] * 2 +
+                         [C.c_float, C.c_float, C.c_int, C.c_int] + [C.c_void_p] * 3 + [C.c_size_t, C.c_void_p]),
     "disyolo_yolo_loss_workspace": (C.c_size_t, [C.c_int] * 3),
     "disyolo_yolo_loss_workspace_hw": (C.c_size_t, [C.c_int] * 4),
     "disyolo_yolo_loss_hw": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p, C.c_float] +
@@ -177,6 +182,8 @@ _SIGS = {
     "disyolo_paste_job_plan": (C.c_int, [C.c_void_p, C.c_int]),
     "disyolo_mask_paste_iou_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "disyolo_mask_paste_iou_batch_hw": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "disyolo_paste_job_plan_x": (C.c_int, [C.c_void_p, C.c_int]),
+    "disyolo_mask_paste_iou_batch_x": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "disyolo_adam_step": (C.c_int, [C.c_void_p] * 4 + [C.c_int64, C.c_int64] + [C.c_float] * 5 + [C.c_int64, C.c_float,
                                                                                              C.c_void_p]),
     "disyolo_adam_step_dev": (C.c_int, [C.c_void_p] * 4 + [C.c_int64, C.c_int64] + [C.c_float] * 5 + [C.c_void_p, C.c_float,
@@ -951,20 +958,22 @@ PASTE_JOB = np.dtype([("masks", np.uint64), ("rects", np.uint64), ("classids", n
 assert PASTE_JOB.itemsize == 88      # (disyolo_paste_job, include/disyolo.h)
 
 
-def paste_job_plan(jobs) -> int:
-    """jobs: numpy array of PASTE_JOB records (host); checks them and fills ``block0``; returns the launch's block count"""
+def paste_job_plan(jobs, wide: bool = False) -> int:
+    """jobs: numpy array of PASTE_JOB records (host); checks them and fills ``block0``; returns the launch's block count.
+    ``wide``: jobs of up to 256 detections (disyolo_paste_job_plan_x) instead of 64"""
     if jobs.dtype != PASTE_JOB or not jobs.flags["C_CONTIGUOUS"] or jobs.ndim != 1:
         raise DisyoloError("paste_job_plan: jobs must be a contiguous 1-d array of PASTE_JOB records")
-    rc = load().disyolo_paste_job_plan(jobs.ctypes.data, int(jobs.shape[0]))
+    plan = load().disyolo_paste_job_plan_x if wide else load().disyolo_paste_job_plan
+    rc = plan(jobs.ctypes.data, int(jobs.shape[0]))
     if rc < 0:
         _check(rc, "paste_job_plan")
     return rc
 
 
-def mask_paste_iou_batch(jobs, jobs_dev, size, conf=None) -> None:
+def mask_paste_iou_batch(jobs, jobs_dev, size, conf=None, wide: bool = False) -> None:
     """jobs: the planned PASTE_JOB records on the host; jobs_dev: a uint8 CUDA tensor that starts with the same bytes (uploaded by
     the caller on this stream); size: the masks' size, an int or (Hm, Wm); conf: int64 [16] CUDA or None.  One launch for all
-    jobs (disyolo_mask_paste_iou_batch_hw)."""
+    jobs (disyolo_mask_paste_iou_batch_hw; ``wide``: disyolo_mask_paste_iou_batch_x, jobs of up to 256 detections)."""
     if jobs.dtype != PASTE_JOB or not jobs.flags["C_CONTIGUOUS"] or jobs.ndim != 1:
         raise DisyoloError("mask_paste_iou_batch: jobs must be a contiguous 1-d array of PASTE_JOB records")
     _need(jobs_dev, torch.uint8, "jobs_dev")
@@ -974,8 +983,8 @@ def mask_paste_iou_batch(jobs, jobs_dev, size, conf=None) -> None:
         _need(conf, torch.int64, "conf")
         _need_shape(conf, (16,), "conf")
     mh, mw = hw_of(size)
-    _check(load().disyolo_mask_paste_iou_batch_hw(jobs.ctypes.data, _p(jobs_dev), int(jobs.shape[0]), mh, mw, _p(conf),
-                                                  _stream()), "mask_paste_iou_batch")
+    launch = load().disyolo_mask_paste_iou_batch_x if wide else load().disyolo_mask_paste_iou_batch_hw
+    _check(launch(jobs.ctypes.data, _p(jobs_dev), int(jobs.shape[0]), mh, mw, _p(conf), _stream()), "mask_paste_iou_batch")
 
 
 def letterbox(rgb_u8, out, size):
@@ -1089,8 +1098,17 @@ def hw_of(size):
     return int(h), int(w)
 
 
-def detect_workspace(B, S, num_class) -> int:
+def detect_takes_x(num_class: int, max_det: int) -> bool:
+    """whether ``detect`` calls disyolo_detect_x: more rows than the entry points of before take -- above 64, or, up to 16
+    classes, num_class * max_det above the 512 survivors of their LDS rank merge (which they refuse)"""
+    return max_det > 64 or (num_class <= 16 and num_class * max_det > 512)
+
+
+def detect_workspace(B, S, num_class, max_det: int = 0) -> int:
+    """bytes of the filter's workspace; it grows with ``max_det`` above 64 (the kept lists)"""
     H, W = hw_of(S)
+    if detect_takes_x(num_class, max_det):
+        return load().disyolo_detect_workspace_x(B, H, W, num_class, max_det)
     return load().disyolo_detect_workspace_hw(B, H, W, num_class)
 
 
@@ -1110,12 +1128,23 @@ def detect_list_capacity() -> int:
 def detect(logits3, logits2, logits1, B, S, num_class, anchors_host, clip_window, obj_thresh, nms_thresh, max_det,
            detections, det_count, ws: Workspace, nms: str = "per_class") -> None:
     """``S``: the net's input size, an int or (H, W).  ``nms``: "per_class" (greedy NMS inside each arg-max class),
-    "agnostic" (one greedy NMS over all of an image's candidates) or "none" (the max_det highest scores)"""
+    "agnostic" (one greedy NMS over all of an image's candidates) or "none" (the max_det highest scores).
+    Sizes that disyolo_detect_nms_hw takes go to it as ever; ``max_det`` of 65..256, and up to 16 classes with
+    num_class * max_det > 512, take disyolo_detect_x and its workspace (``detect_takes_x``)"""
     H, W = hw_of(S)
     mode = nms_mode(nms)
+    anc = (C.c_float * 18)(*[float(v) for v in anchors_host])
+    if detect_takes_x(num_class, max_det):
+        need = load().disyolo_detect_workspace_x(B, H, W, num_class, max_det)
+        if not need:
+            raise DisyoloError("detect: max_det must be in 1..%d (got %d)" % (MAX_DET, max_det))
+        buf = ws.get(need)
+        _check(load().disyolo_detect_x(_p(logits3), _p(logits2), _p(logits1), B, H, W, num_class, anc, _p(clip_window),
+                                       obj_thresh, nms_thresh, max_det, mode, _p(detections), _p(det_count), _p(buf),
+                                       buf.numel(), _stream()), "detect")
+        return
     need = load().disyolo_detect_workspace_hw(B, H, W, num_class)
     buf = ws.get(need)
-    anc = (C.c_float * 18)(*[float(v) for v in anchors_host])
     _check(load().disyolo_detect_nms_hw(_p(logits3), _p(logits2), _p(logits1), B, H, W, num_class, anc, _p(clip_window),
                                         obj_thresh, nms_thresh, max_det, mode, _p(detections), _p(det_count), _p(buf),
                                         buf.numel(), _stream()), "detect")

@@ -176,18 +176,53 @@ def check_image_size(image_size) -> Tuple[int, int]:
     return sides
 
 
+MAX_LIMIT = 256      # DISYOLO_MAX_BOXES = DISYOLO_MAX_DET (include/disyolo.h): boxes and detections per image
+
+
+def check_anchors(anchors) -> np.ndarray:
+    """the nine anchors as the net and the loader take them: float32 [9, 2], (w, h) in net pixels, finite and positive;
+    rows [0:3] belong to the H/8 grid"""
+    try:
+        a = np.asarray(anchors, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("anchors must be 9 rows of 2 finite positive numbers (w, h) (got %r)" % (anchors,))
+    if a.shape != (9, 2):
+        raise ValueError("anchors must be 9 rows of 2 finite positive numbers (w, h) (got shape %s)" % (a.shape,))
+    with np.errstate(over="ignore"):
+        a32 = a.astype(np.float32)
+    if not np.all(np.isfinite(a)) or not np.all(a > 0) or not np.all(np.isfinite(a32)) or not np.all(a32 > 0):
+        raise ValueError("anchors must be 9 rows of 2 finite positive numbers (w, h)")
+    return np.ascontiguousarray(a32)
+
+
+def check_limit(value, name: str) -> int:
+    """``max_box_per_image`` / ``max_detection``: an int in 1..256 (bools are refused)"""
+    if isinstance(value, bool) or not isinstance(value, (int, np.integer)):
+        raise ValueError("%s must be an int in 1..%d (got %r)" % (name, MAX_LIMIT, value))
+    if not 1 <= int(value) <= MAX_LIMIT:
+        raise ValueError("%s must be in 1..%d (got %d)" % (name, MAX_LIMIT, int(value)))
+    return int(value)
+
+
 class YOLONet(object):
     def __init__(self, training: bool = False, device=None, image_size=None,
                  batch_size: Optional[int] = None, stage: int = 1, lock: Optional[Dict[int, bool]] = None,
                  seed: int = 0, xavier_locked: bool = True, plan_only: bool = False, dtype: str = "bf16",
                  backbone_pair: bool = False, k_map: Optional[int] = None, mask_stride: Optional[int] = None,
-                 classes: Optional[Sequence[str]] = None, nms: Optional[str] = None):
+                 classes: Optional[Sequence[str]] = None, nms: Optional[str] = None, anchors=None,
+                 max_box_per_image: Optional[int] = None, max_detection: Optional[int] = None):
         # 1. parameters (yolo/yolo3_net_pos.py:15-38)
         self.batchsize = int(batch_size if batch_size is not None else cfg.BATCH_SIZE)
         # the class list (CLASSES of yolo/config.py): cfg.CLASSES unless given; it sizes the three heads
         self.classes = check_classes(cfg.CLASSES if classes is None else classes)
         self.num_class = len(self.classes)
-        self.anchors = np.asarray(cfg.ANCHORS, dtype=np.float32)
+        # the three dataset-shaped constants of yolo/config.py, per net: the anchors (dimension clusters at this net's
+        # size: train_data.cluster_anchors), the ground-truth boxes an image carries (G) and the detections it yields (D);
+        # the cfg values at construction unless given
+        self.anchors = check_anchors(cfg.ANCHORS if anchors is None else anchors)
+        self.max_box_per_image = check_limit(cfg.MAX_BOX_PER_IMAGE if max_box_per_image is None else max_box_per_image,
+                                             "max_box_per_image")
+        self.max_detection = check_limit(cfg.MAX_DETECTION if max_detection is None else max_detection, "max_detection")
         self.num_anchor = 3
         self.output_depth = (self.num_class + 5) * self.num_anchor
         # k_map x k_map position-sensitive score maps (conv82 emits k_map^2 channels); cfg.K_MAP unless given
@@ -527,17 +562,17 @@ class YOLONet(object):
             self._zeros32 = torch.zeros(l1.cout, dtype=F32, device=dev)
         # detection / loss buffers
         self.clip_window = torch.zeros(B, 4, dtype=F32, device=dev)
-        self.detections = torch.zeros(B, cfg.MAX_DETECTION, 6, dtype=F32, device=dev)
+        self.detections = torch.zeros(B, self.max_detection, 6, dtype=F32, device=dev)
         self.det_count = torch.zeros(B, dtype=torch.int32, device=dev)
         self.masks = None
-        self.keep = torch.zeros(B, cfg.MAX_DETECTION, dtype=torch.int32, device=dev)
+        self.keep = torch.zeros(B, self.max_detection, dtype=torch.int32, device=dev)
         if self.training:
-            G = cfg.MAX_BOX_PER_IMAGE
+            G = self.max_box_per_image
             self.labels = [torch.zeros(B, H // d, W // d, 3, 5 + self.num_class, dtype=F32, device=dev)
                            for d in (8, 16, 32)]                   # yolo3, yolo2, yolo1
             self.true_boxes = torch.zeros(B, G, 5, dtype=F32, device=dev)
             self.true_masks = torch.zeros(B, G, H, W, dtype=torch.uint8, device=dev)
-            self.perm_det = torch.arange(cfg.MAX_DETECTION, dtype=torch.int32, device=dev).repeat(B, 1).contiguous()
+            self.perm_det = torch.arange(self.max_detection, dtype=torch.int32, device=dev).repeat(B, 1).contiguous()
             self.perm_gt = torch.arange(G, dtype=torch.int32, device=dev).repeat(B, 1).contiguous()
             self.rois = torch.zeros(B, L.ROI_MAX, L.roi_w(self.k), dtype=torch.int32, device=dev)
             self.roi_count = torch.zeros(B, dtype=torch.int32, device=dev)
@@ -569,7 +604,7 @@ class YOLONet(object):
                 need = max(need, L.load().disyolo_conv_first_wgrad_workspace(B, H, W, l1.cout))
             self.ws.get(int(need))
             self.ws_aux.get(int(need))
-        self.ws_det.get(int(max(L.detect_workspace(B, (H, W), self.num_class), 1 << 20)))
+        self.ws_det.get(int(max(L.detect_workspace(B, (H, W), self.num_class, self.max_detection), 1 << 20)))
         self._build_dgrad_descs()
         self.refresh_weights()
 
@@ -1164,7 +1199,7 @@ class YOLONet(object):
 
     def _detect(self, det_thresh: float) -> None:
         L.detect(self.by_idx[75].act, self.by_idx[67].act, self.by_idx[59].act, self.B, (self.H, self.W), self.num_class,
-                 self.anchors.reshape(-1), self.clip_window, float(det_thresh), cfg.IOU_THRESHOLD, cfg.MAX_DETECTION,
+                 self.anchors.reshape(-1), self.clip_window, float(det_thresh), cfg.IOU_THRESHOLD, self.max_detection,
                  self.detections, self.det_count, self.ws_det, nms=self.nms)
 
     def _use_half(self, h: int) -> None:
@@ -1240,8 +1275,8 @@ class YOLONet(object):
             self.forward(images, clip_window, det_thresh, is_training=False)
             Hm, Wm = self.mask_map_size()
             if self.masks is None:
-                self.masks = torch.zeros(self.B, cfg.MAX_DETECTION, Hm, Wm, dtype=F32, device=self.device)
-            L.psroi_assemble(self.by_idx[self.score_layer].act, self.detections, self.B, cfg.MAX_DETECTION, (Hm, Wm), self.k,
+                self.masks = torch.zeros(self.B, self.max_detection, Hm, Wm, dtype=F32, device=self.device)
+            L.psroi_assemble(self.by_idx[self.score_layer].act, self.detections, self.B, self.max_detection, (Hm, Wm), self.k,
                              self.masks, self.keep)
         return self.detections, self.keep, self.masks
 
@@ -1270,7 +1305,7 @@ class YOLONet(object):
         keep [B,30] (BASELINE.json config 4)."""
         Hm, Wm = self.mask_map_size()
         if self.masks is None:
-            self.masks = torch.zeros(self.B, cfg.MAX_DETECTION, Hm, Wm, dtype=F32, device=self.device)
+            self.masks = torch.zeros(self.B, self.max_detection, Hm, Wm, dtype=F32, device=self.device)
         prog = L.CmdList()
         # a hipGraph is captured from ONE lane: the graph executor runs a captured side lane on a stream of its own choosing,
         # and whether that stream's hardware queue runs beside the launch stream's or stalls it is out of the caller's hands
@@ -1283,7 +1318,7 @@ class YOLONet(object):
             with prog:
                 self._forward_layers(False)
                 self._detect(det_thresh)
-                L.psroi_assemble(self.by_idx[self.score_layer].act, self.detections, self.B, cfg.MAX_DETECTION, (Hm, Wm), self.k,
+                L.psroi_assemble(self.by_idx[self.score_layer].act, self.detections, self.B, self.max_detection, (Hm, Wm), self.k,
                                  self.masks, self.keep)
         finally:
             self.use_side_lane = side_lane
@@ -1369,8 +1404,8 @@ class YOLONet(object):
         (torch RNG).  A recorded step built with ``auto_shuffle`` does this on the device."""
         self.sync_lanes()
         B = self.B
-        self.perm_det.copy_(torch.rand(B, cfg.MAX_DETECTION, device=self.device, generator=generator).argsort(dim=1))
-        self.perm_gt.copy_(torch.rand(B, cfg.MAX_BOX_PER_IMAGE, device=self.device, generator=generator).argsort(dim=1))
+        self.perm_det.copy_(torch.rand(B, self.max_detection, device=self.device, generator=generator).argsort(dim=1))
+        self.perm_gt.copy_(torch.rand(B, self.max_box_per_image, device=self.device, generator=generator).argsort(dim=1))
 
     shuffle_seed = None   # set to an int: compute_losses reshuffles the RoI order on the device each step
 
@@ -1393,13 +1428,13 @@ class YOLONet(object):
             L.shuffle_perm(self.perm_det, self.perm_gt, self.B, int(self.shuffle_seed) & 0xffffffff, self.step_dev)
         self._detect(det_thresh)
         Sm = self.mask_map_size()
-        L.mask_rois(self.detections, cfg.MAX_DETECTION, self.true_boxes, cfg.MAX_BOX_PER_IMAGE, self.perm_det,
+        L.mask_rois(self.detections, self.max_detection, self.true_boxes, self.max_box_per_image, self.perm_det,
                     self.perm_gt, self.B, Sm, cfg.MASK_ROI_DET, cfg.MASK_ROI_GT, cfg.MASK_ROI_IOU, self.rois,
                     self.roi_count, k=self.k)
         if side:
             L.lane_sync(0, 1)
         m = self.by_idx[self.score_layer]
-        L.psroi_loss(m.act, self.true_masks, cfg.MAX_BOX_PER_IMAGE, self.rois, self.roi_count, self.B, Sm, self.k,
+        L.psroi_loss(m.act, self.true_masks, self.max_box_per_image, self.rois, self.roi_count, self.B, Sm, self.k,
                      self.mask_scale, m.dx, self.mask_loss, self.ws_aux if side else self.ws, mask_stride=self.mask_stride)
         # the mask subnet's backward waits for THIS point of the side lane (not for the weight gradients
         # that lane picks up afterwards: a whole-lane sync there kept the main lane idle for 250-500 us)
@@ -1408,11 +1443,11 @@ class YOLONet(object):
             L.set_lane(0)
         scales = (self.object_scale, self.noobject_scale, self.class_scale, self.coord_scale)
         if self.output_depth > L.GRAD_LD:      # rows past 32 channels (more than 5 classes): the heads' own pitch
-            L.yolo_loss_wide([h.act for h in heads], self.labels, self.true_boxes, cfg.MAX_BOX_PER_IMAGE, self.B, (self.H, self.W),
+            L.yolo_loss_wide([h.act for h in heads], self.labels, self.true_boxes, self.max_box_per_image, self.B, (self.H, self.W),
                              self.num_class, heads[0].cout_pad, self.anchors.reshape(-1), cfg.IGNORE_THRESH, scales,
                              [h.dx for h in heads], self.losses, self.ws)
         else:
-            L.yolo_loss([h.act for h in heads], self.labels, self.true_boxes, cfg.MAX_BOX_PER_IMAGE, self.B, (self.H, self.W),
+            L.yolo_loss([h.act for h in heads], self.labels, self.true_boxes, self.max_box_per_image, self.B, (self.H, self.W),
                         self.num_class, self.anchors.reshape(-1), cfg.IGNORE_THRESH, scales,
                         [h.dx for h in heads], self.losses, self.ws)
         self._mask_loss_pending = side

@@ -92,6 +92,15 @@ class Solver(object):
             if n is not None and n != net.num_class:
                 raise ValueError("Solver: the net has %d classes but %s has %d; build all three with the same class list"
                                  % (net.num_class, what, n))
+        # ... and one set of anchors and one count of ground-truth rows: the loader's target grids are assigned with its
+        # anchors, and its true_boxes / true_masks have its G rows
+        g = getattr(data, "max_box_per_image", None)
+        if g is not None and g != net.max_box_per_image:
+            raise ValueError("Solver: the net takes %d boxes per image but data has %d; build both with the same "
+                             "max_box_per_image" % (net.max_box_per_image, g))
+        a = getattr(data, "anchors", None)
+        if a is not None and not np.array_equal(np.asarray(a, np.float32).reshape(-1), net.anchors.reshape(-1)):
+            raise ValueError("Solver: the net's anchors differ from data's; build both with the same anchors")
         self.start_iter = 1
         self.max_iter = cfg.MAX_ITER if max_iter is None else max_iter
         self.summary_iter = cfg.SUMMARY_ITER if summary_iter is None else summary_iter

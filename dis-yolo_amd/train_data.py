@@ -60,6 +60,74 @@ def extract_bboxes(mask: torch.Tensor):
     return int(cols[0]), int(rows[0]), int(cols[-1]) + 1, int(rows[-1]) + 1
 
 
+def letterbox_boxes(labels: Sequence[Dict], image_size) -> np.ndarray:
+    """float64 [N, 2]: the (w, h) of every instance of ``labels`` (``defect_train``'s records) in the pixels of a net of
+    ``image_size`` (an int or (H, W)), i.e. scaled by the letter-box factor ``evaluate.image_read`` applies to the record's
+    image.  An instance's box spans its polygon points, x2 / y2 one past the last one like ``extract_bboxes``.  A record
+    gives its image size as ``'image'`` (the array), ``'image_size'`` = (h, w) or ``'imname'`` (decoded)."""
+    from .net import check_image_size
+    net_h, net_w = check_image_size(image_size)
+    out = []
+    for label in labels:
+        if "image" in label:
+            image_h, image_w = np.asarray(label["image"]).shape[:2]
+        elif "image_size" in label:
+            image_h, image_w = label["image_size"]
+        else:
+            from .evaluate import load_image_rgb
+            image_h, image_w = load_image_rgb(label["imname"]).shape[:2]
+        image_h, image_w = int(image_h), int(image_w)
+        # the letter box of disyolo_letterbox_hw: the width binds when net_w / image_w < net_h / image_h
+        if net_w / image_w < net_h / image_h:
+            new_w, new_h = net_w, (image_h * net_w) // image_w
+        else:
+            new_w, new_h = (image_w * net_h) // image_h, net_h
+        for polys in label["polygons"]:
+            xs = np.concatenate([np.asarray(p["all_points_x"], np.float64) for p in polys]) if polys else np.zeros(0)
+            ys = np.concatenate([np.asarray(p["all_points_y"], np.float64) for p in polys]) if polys else np.zeros(0)
+            if xs.size == 0:
+                continue
+            out.append(((xs.max() + 1 - xs.min()) * new_w / image_w, (ys.max() + 1 - ys.min()) * new_h / image_h))
+    return np.asarray(out, np.float64).reshape(-1, 2)
+
+
+def cluster_anchors(labels, image_size, n: int = 9) -> np.ndarray:
+    """The "dimension clustering" that yolo/config.py names for its ANCHORS and the reference does not ship: k-means over the
+    instances' (w, h) at the net's size with the distance 1 - IoU of co-centred boxes (YOLOv2).  ``labels``: ``defect_train``'s
+    records (``letterbox_boxes`` scales their boxes to ``image_size``).  Deterministic -- no random draw:
+      * initial centroids: the boxes at the n evenly spaced quantiles (i + 1/2) / n of the boxes sorted by area;
+      * a box joins the centroid of highest IoU (the first among equals); a centroid becomes the mean of its boxes, an empty
+        cluster keeps its centroid;
+      * stop when no assignment changes, or after 300 rounds.
+    Returns float32 [n, 2], (w, h) in net pixels sorted by area ascending: rows [0:3] for the H/8 grid, as YOLONet's and
+    defect_train's ``anchors`` take them.  Host numpy, once per dataset."""
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 1:
+        raise ValueError("cluster_anchors: n must be a positive int (got %r)" % (n,))
+    boxes = letterbox_boxes(labels, image_size)
+    if len(boxes) < n:
+        raise ValueError("cluster_anchors: %d clusters need at least as many instances (got %d)" % (n, len(boxes)))
+    if not np.all(np.isfinite(boxes)) or not np.all(boxes > 0):
+        raise ValueError("cluster_anchors: every instance must have a finite positive width and height")
+    area = boxes[:, 0] * boxes[:, 1]
+    order = np.argsort(area, kind="stable")
+    pick = np.minimum(((np.arange(n) + 0.5) / n * len(boxes)).astype(np.int64), len(boxes) - 1)
+    cent = boxes[order[pick]].copy()
+    assign = np.full(len(boxes), -1, np.int64)
+    for _ in range(300):
+        inter = np.minimum(boxes[:, None, 0], cent[None, :, 0]) * np.minimum(boxes[:, None, 1], cent[None, :, 1])
+        iou = inter / (area[:, None] + (cent[:, 0] * cent[:, 1])[None, :] - inter)
+        new = np.argmax(iou, axis=1)                           # smallest 1 - IoU, the first among equals
+        if np.array_equal(new, assign):
+            break
+        assign = new
+        for c in range(n):
+            mine = boxes[assign == c]
+            if len(mine):
+                cent[c] = mine.mean(axis=0)
+    cent = cent[np.argsort(cent[:, 0] * cent[:, 1], kind="stable")]
+    return np.ascontiguousarray(cent.astype(np.float32))
+
+
 class defect_train(object):
     """labels: [{'image': RGB uint8 array [H,W,3] (or 'imname': path decoded with PIL), 'class_names': [...],
     'polygons': [[{'type', 'all_points_x', 'all_points_y'}, ...] per instance]}] -- the ``gt_labels`` structure of
@@ -68,17 +136,19 @@ class defect_train(object):
     def __init__(self, labels: List[Dict], batch_size: Optional[int] = None, image_size=None, device=None,
                  rng: Optional[np.random.RandomState] = None, flipped: Optional[bool] = None,
                  blur_noise_light: Optional[bool] = None, cache_bytes: int = 16 << 30,
-                 classes: Optional[Sequence[str]] = None):
+                 classes: Optional[Sequence[str]] = None, anchors=None, max_box_per_image: Optional[int] = None):
         self.batch_size = cfg.BATCH_SIZE if batch_size is None else batch_size
         # image_size: an int S or a pair (net_h, net_w), like YOLONet's; the attribute keeps the caller's form
         from .net import check_image_size
         self.image_size = cfg.IMAGE_SIZE if image_size is None else image_size
         self.net_h, self.net_w = check_image_size(self.image_size)
         self.base_grid = self.net_h // 32 if self.net_h == self.net_w else (self.net_h // 32, self.net_w // 32)
-        self.max_box_per_image = cfg.MAX_BOX_PER_IMAGE
-        self.anchors = cfg.ANCHORS
+        # the net's anchors and its ground-truth rows per image (YOLONet's options of the same names); cfg's unless given
+        from .net import check_anchors, check_classes, check_limit
+        self.max_box_per_image = check_limit(cfg.MAX_BOX_PER_IMAGE if max_box_per_image is None else max_box_per_image,
+                                             "max_box_per_image")
+        self.anchors = check_anchors(cfg.ANCHORS if anchors is None else anchors)
         self.num_anchor = 3
-        from .net import check_classes
         self.classes = check_classes(cfg.CLASSES if classes is None else classes)     # cfg.CLASSES unless given
         self.num_class = len(self.classes)
         self.class_to_ind = dict(zip(self.classes, range(self.num_class)))
@@ -236,7 +306,7 @@ class defect_train(object):
                 y2 = max(min(float(y2) * sy + dy, net_h - 1), 0)
                 bx[j] = [(x2 + x1) / 2.0, (y2 + y1) / 2.0, x2 - x1, y2 - y1]
             # (the non-zero rows of the three grids, {(yi, xi, anchor): row}: pixel units, like the reference here)
-            grids = assign_target_entries(bx, cls, S, self.num_class)
+            grids = assign_target_entries(bx, cls, S, self.num_class, self.anchors)
             # ---- step 2: flip (:187-226) -- the grids are mirrored and the stored centres reflected
             flip = 1
             if self.flipped:

@@ -4,6 +4,7 @@ inference net -> detections + instance masks for one image.
 
     python examples/train_synthetic.py [--steps 40] [--size 192 | --size 128x192] [--batch 4] [--out /tmp/disyolo_example] [--lock 62-64]
                                        [--classes crack,spall,rebar,stain,joint,void]
+                                       [--max-boxes 100] [--max-det 100] [--anchors auto | --anchors w,h,w,h,... (9 pairs)]
 
 It mirrors what the reference's ``train_yolo3_mask.py:237-248`` (train) and ``calculate_test_map.py`` (test) do
 with a real dataset; swap ``synthetic_labels`` for ``disyolo_amd.pre_process.load_verify_contour(path, 'train')``
@@ -21,7 +22,7 @@ import disyolo_amd  # noqa: E402,F401
 from disyolo_amd import checkpoint, config as cfg, postprocess  # noqa: E402
 from disyolo_amd.net import YOLONet  # noqa: E402
 from disyolo_amd.solver import Solver  # noqa: E402
-from disyolo_amd.train_data import defect_train  # noqa: E402
+from disyolo_amd.train_data import cluster_anchors, defect_train  # noqa: E402
 
 
 def synthetic_labels(rng, n, classes=None):
@@ -65,6 +66,18 @@ def parse_size(text):
     return int(text)
 
 
+def parse_anchors(text):
+    """"auto" -> "auto" (cluster the dataset's boxes); "w,h,w,h,..." -> float32 [9, 2]; "" -> None (cfg.ANCHORS)"""
+    if not text:
+        return None
+    if text == "auto":
+        return "auto"
+    vals = [float(v) for v in text.split(",")]
+    if len(vals) != 18:
+        raise argparse.ArgumentTypeError("--anchors takes 'auto' or 18 numbers w,h,... (got %d)" % len(vals))
+    return np.asarray(vals, np.float32).reshape(9, 2)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=40)
@@ -82,17 +95,30 @@ def main():
     ap.add_argument("--nms", default=cfg.NMS_METHOD, choices=("per_class", "agnostic", "none"),
                     help="detection filter: greedy NMS inside each class (cfg.NMS_METHOD), one class-agnostic NMS per image, "
                          "or no suppression; it picks the mask-loss RoIs in training and what is pasted at test time")
+    ap.add_argument("--max-boxes", type=int, default=cfg.MAX_BOX_PER_IMAGE,
+                    help="ground-truth instances an image carries, 1..256 (cfg.MAX_BOX_PER_IMAGE): net and loader")
+    ap.add_argument("--max-det", type=int, default=cfg.MAX_DETECTION,
+                    help="detections an image yields, 1..256 (cfg.MAX_DETECTION)")
+    ap.add_argument("--anchors", type=parse_anchors, default=None,
+                    help="the nine anchors (w, h) in net pixels, smallest first: 'auto' clusters the dataset's boxes at --size "
+                         "(train_data.cluster_anchors), or 18 numbers w,h,...; cfg.ANCHORS unless given")
     args = ap.parse_args()
     classes = [c.strip() for c in args.classes.split(",")]
     dev = torch.device("cuda:0")
     rng = np.random.RandomState(0)
     labels = synthetic_labels(rng, 16, classes)
+    anchors = args.anchors
+    if isinstance(anchors, str):
+        anchors = cluster_anchors(labels, args.size)
+        print("anchors from the dataset's boxes at this size:", np.round(anchors, 1).tolist())
+    limits = dict(anchors=anchors, max_box_per_image=args.max_boxes)
 
     # --- train: stage 1 (conv1-52 locked), batches built on the GPU from the polygon records
     data = defect_train(labels, batch_size=args.batch, image_size=args.size, device=dev, rng=np.random.RandomState(1),
-                        classes=classes)
+                        classes=classes, **limits)
     net = YOLONet(training=True, device=dev, image_size=args.size, batch_size=args.batch, stage=1, seed=0, k_map=args.k_map,
-                  mask_stride=args.mask_stride, lock=parse_lock(args.lock), classes=classes, nms=args.nms)
+                  mask_stride=args.mask_stride, lock=parse_lock(args.lock), classes=classes, nms=args.nms, max_detection=args.max_det,
+                  **limits)
     if net.pass_through_layers():
         print("locked layers the gradient crosses:", net.pass_through_layers())
     solver = Solver(net, data, output_dir=args.out, max_iter=args.steps, summary_iter=max(1, args.steps // 4),
@@ -105,7 +131,7 @@ def main():
     prefix = checkpoint.latest_checkpoint(os.path.join(args.out, "checkpoint"))
     print("restoring", prefix)
     inf = YOLONet(training=False, device=dev, image_size=args.size, batch_size=1, stage=1, seed=123, k_map=args.k_map,
-                  mask_stride=args.mask_stride, classes=classes, nms=args.nms)
+                  mask_stride=args.mask_stride, classes=classes, nms=args.nms, max_detection=args.max_det, **limits)
     checkpoint.restore_net(inf, prefix)
     rec = labels[0]
     from disyolo_amd.evaluate import image_read

@@ -418,6 +418,21 @@ int disyolo_detect_nms_hw(const float* logits3, const float* logits2, const floa
                           int num_class, const float* anchors_host, const float* clip_window,
                           float obj_thresh, float nms_thresh, int max_det, int nms_mode, float* detections,
                           int32_t* det_count, void* workspace, size_t workspace_bytes, void* stream);
+/* Per-net limits: a net takes up to DISYOLO_MAX_BOXES ground-truth boxes and writes up to DISYOLO_MAX_DET detections per
+ * image.  The entry points above keep their limit of 64; the _x forms below (and disyolo_yolo_loss_hw, disyolo_mask_rois_hw,
+ * disyolo_shuffle_perm, widened in place) take the whole range, and compute the same bits where both forms take a size. */
+#define DISYOLO_MAX_BOXES 256
+#define DISYOLO_MAX_DET 256
+/* disyolo_detect_nms_hw for 1 <= max_det <= DISYOLO_MAX_DET, every nms_mode: the same rows, zero padding and det_count
+ * (score descending, ties to the lower candidate index).  The workspace is disyolo_detect_workspace_x's, which grows with
+ * max_det above 64 (the kept lists per (image, class)); 0 for sizes the filter refuses.  Up to 16 classes the survivors merge
+ * by rank in LDS while num_class * max_det <= 512 and by the k-way merge of the longer class lists beyond -- also at
+ * max_det <= 64, where disyolo_detect_nms_hw refuses num_class <= 16 with num_class * max_det > 512. */
+size_t disyolo_detect_workspace_x(int B, int H, int W, int num_class, int max_det);
+int disyolo_detect_x(const float* logits3, const float* logits2, const float* logits1, int B, int H, int W,
+                     int num_class, const float* anchors_host, const float* clip_window,
+                     float obj_thresh, float nms_thresh, int max_det, int nms_mode, float* detections,
+                     int32_t* det_count, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- YOLO loss + gradient (loss_yolo, yolo/yolo3_net_pos.py:631-747) ---- */
 /* labels: f32 [B,g,g,3,5+C] per scale (yolo3, yolo2, yolo1); true_boxes f32 [B,20,5].
@@ -443,7 +458,9 @@ int disyolo_yolo_loss_wide(const float* const logits[3], const float* const labe
 /* both losses on a net of H x W pixels (positive multiples of 32): labels, logits and dlogits
  * [B,gh,gw,...] per scale with (gh, gw) = (H/8, W/8), (H/16, W/16), (H/32, W/32); grid_factor = [gw, gh],
  * net_factor = [W, H] as in the reference (:646, :709-718).  dlogits_ld = 0 runs the 32-channel kernel of
- * disyolo_yolo_loss, any other value the wide one; those two are the H = W = S calls of this one. */
+ * disyolo_yolo_loss, any other value the wide one; those two are the H = W = S calls of this one, with max_boxes <= 64.
+ * This one takes 1 <= max_boxes <= DISYOLO_MAX_BOXES: above 64 an instance of the same kernel that stages 256 true boxes
+ * runs -- the same arithmetic, partial layout and summation order. */
 size_t disyolo_yolo_loss_workspace_hw(int B, int H, int W, int num_class);
 int disyolo_yolo_loss_hw(const float* const logits[3], const float* const labels[3],
                          const float* true_boxes, int max_boxes, int B, int H, int W, int num_class,
@@ -467,14 +484,17 @@ int disyolo_mask_rois(const float* detections, int max_det, const float* true_bo
                       void* stream);
 /* RoI selection on a score map of map_h x map_w: y-coordinates are scaled by map_h, x-coordinates by map_w,
  * each through tf.round; bin edges per axis; the area is the pixel count clipped to the map.
- * disyolo_mask_rois_k is its map_h = map_w call. */
+ * disyolo_mask_rois_k is its map_h = map_w call.  max_det <= DISYOLO_MAX_DET, G <= DISYOLO_MAX_BOXES: with either above 64
+ * a wave builds the trimmed row lists with ordered ballots and takes each RoI's IoU arg-max across its lanes (first maximum
+ * wins, NaN never wins); up to 64 the single-lane form runs as before.  The same rows either way. */
 int disyolo_mask_rois_hw(const float* detections, int max_det, const float* true_boxes, int G,
                          const int32_t* perm_det, const int32_t* perm_gt, int B, int map_h, int map_w, int k,
                          int n_det, int n_gt, float iou_thresh, int32_t* rois, int32_t* roi_count,
                          void* stream);
 /* tf.random_shuffle replacement (:781-782): uniformly random permutations perm_det int32
  * [B,n_det], perm_gt int32 [B,n_gt] from a counter-based hash of (seed, *step_counter, image);
- * step_counter (device int64, may be NULL) makes every replay of a recorded step reshuffle */
+ * step_counter (device int64, may be NULL) makes every replay of a recorded step reshuffle.  n_det, n_gt <= 256; the keys and
+ * the rank rule do not depend on which of the two block sizes (64 threads up to n = 64, 256 beyond) ranks them. */
 int disyolo_shuffle_perm(int32_t* perm_det, int n_det, int32_t* perm_gt, int n_gt, int B, uint32_t seed,
                          const int64_t* step_counter, void* stream);
 /* masked BCE over assembled logits + gradient wrt the score maps (:799-858).
@@ -561,6 +581,12 @@ int disyolo_mask_paste_iou_batch(const disyolo_paste_job* jobs_host, const disyo
 /* the batched paste from masks of map_h x map_w; disyolo_mask_paste_iou_batch is its map_h = map_w call */
 int disyolo_mask_paste_iou_batch_hw(const disyolo_paste_job* jobs_host, const disyolo_paste_job* jobs, int njobs, int map_h,
                                     int map_w, int64_t* conf, void* stream);
+/* both for jobs of up to DISYOLO_MAX_DET rows (n <= 256): a pixel keeps one 64-bit cover word per 64 detections and walks the
+ * words in order, so the last covering detection still owns the merged pixel across a word boundary; counts has the same
+ * layout.  A table must be planned by the _x plan to be launched by the _x launch. */
+int disyolo_paste_job_plan_x(disyolo_paste_job* jobs_host, int njobs);
+int disyolo_mask_paste_iou_batch_x(const disyolo_paste_job* jobs_host, const disyolo_paste_job* jobs, int njobs, int map_h,
+                                   int map_w, int64_t* conf, void* stream);
 /* image_read of the test / validation drivers (calculate_test_map.py:149-176; utils/val_data.py:36-63):
  * rgb uint8 [image_h, image_w, 3] (device) -> out f32 [size, size, 3] (device): aspect-preserving
  * bilinear resize (cv2.resize INTER_LINEAR on the float32 image) centred in the letter box, padding
