@@ -734,6 +734,322 @@ __global__ void psroi_loss_final_kernel(const float* img_loss, int B, float* los
   loss[0] = (float)(tot / (double)B);
 }
 
+// ---- the wide forms: up to ROI_CAP RoIs per image (disyolo_mask_rois_x / disyolo_psroi_loss_x) -------------------------
+constexpr int ROI_CAP = DISYOLO_ROI_CAP;
+static_assert(ROI_CAP == 512, "s_idx holds table rows as shorts; LDS of the wide kernels is sized for 512 rows");
+
+// Ordered compaction over the NW waves of a block: the number of threads below this one whose flag is set, and the
+// block's total.  s_w[NW] is scratch; the barrier in front keeps a call from overwriting the counts of the call before.
+template <int NW>
+__device__ __forceinline__ int block_rank(bool f, int* s_w, int& total) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const unsigned long long m = __ballot(f);
+  __syncthreads();
+  if (lane == 0) s_w[w] = __popcll(m);
+  __syncthreads();
+  int before = 0, all = 0;
+#pragma unroll
+  for (int q = 0; q < NW; ++q) {
+    const int c = s_w[q];
+    before += q < w ? c : 0;
+    all += c;
+  }
+  total = all;
+  return before + __popcll(m & ((1ull << lane) - 1ull));
+}
+
+// The selection for n_det + n_gt <= roi_cap <= ROI_CAP: the rows mask_rois_kernel would write, one block of MRB_NW = 16 waves
+// per image (with four waves the arg-max of 512 RoIs x 256 boxes was 128 rounds a wave and the call 167 us).  Wave 0 builds
+// the trimmed detection list and wave 1 the trimmed box list by ordered ballots; the pick (the first n entries of a
+// permutation that index a trimmed row) is an ordered compaction too, wave 0 over perm_det and wave 1 over perm_gt; every
+// thread then fills the box of its RoI.  The IoU arg-max of RoI r runs on wave r % MRB_NW with the lanes over the trimmed
+// boxes, by mask_rois_wave_kernel's lane rule and combine (the lower row wins a tie, NaN never wins) and the serial form's
+// IoU, operation by operation.  The positives are compacted in RoI order by a block-wide ordered prefix, and the thread that
+// owns an RoI writes its row.
+constexpr int MRB_NW = 16, MRB_NT = MRB_NW * 64;
+template <int K>
+__global__ __launch_bounds__(MRB_NT) void mask_rois_block_kernel(const float* det_g, int max_det, const float* true_boxes_g,
+                                                              int G, const int* perm_det_g, const int* perm_gt_g, int B,
+                                                              int Hm, int Wm, int n_det, int n_gt, float iou_thr,
+                                                              int roi_cap, int* rois, int* roi_count) {
+  constexpr int RW = roi_w(K);
+  __shared__ float s_det[MR_MAX * 6];
+  __shared__ float s_tb[MR_MAX * 5];
+  __shared__ int s_pd[MR_MAX], s_pg[MR_MAX];
+  __shared__ int s_prow[MR_MAX], s_grow[MR_MAX];
+  __shared__ int s_dpick[MR_MAX], s_gpick[MR_MAX];     // picked rows of s_det / s_tb, in pick order
+  __shared__ float s_rb[ROI_CAP][4];
+  __shared__ int s_arg[ROI_CAP];                       // assigned row of s_tb, -1 for a negative
+  __shared__ int s_n[4];                               // np, ng, picked detections, picked boxes
+  __shared__ int s_w[MRB_NW];
+  const int b = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  if (b >= B) return;
+  if (max_det > MR_MAX) max_det = MR_MAX;      // (the entry point refuses more)
+  if (G > MR_MAX) G = MR_MAX;
+  if (n_det > MR_MAX) n_det = MR_MAX;          // a count above the row count takes every row
+  if (n_gt > MR_MAX) n_gt = MR_MAX;
+  for (int i = t; i < max_det * 6; i += MRB_NT) s_det[i] = det_g[(size_t)b * max_det * 6 + i];
+  for (int i = t; i < G * 5; i += MRB_NT) s_tb[i] = true_boxes_g[(size_t)b * G * 5 + i];
+  for (int i = t; i < max_det; i += MRB_NT) s_pd[i] = perm_det_g ? perm_det_g[b * max_det + i] : i;
+  for (int i = t; i < G; i += MRB_NT) s_pg[i] = perm_gt_g ? perm_gt_g[b * G + i] : i;
+  __syncthreads();
+  const unsigned long long below = (1ull << lane) - 1ull;
+  // trimmed lists (rows whose |coords| sum is non-zero), in row order: wave 0 the detections, wave 1 the boxes
+  if (wave < 2) {
+    const int n = wave ? G : max_det, pitch = wave ? 5 : 6;
+    const float* src = wave ? s_tb : s_det;
+    int* list = wave ? s_grow : s_prow;
+    int cnt = 0;
+    for (int base = 0; base < n; base += 64) {
+      const int r = base + lane;
+      bool f = false;
+      if (r < n) {
+        const float* d = src + r * pitch;
+        f = fabsf(d[0]) + fabsf(d[1]) + fabsf(d[2]) + fabsf(d[3]) != 0.f;
+      }
+      const unsigned long long m = __ballot(f);
+      if (f) list[cnt + __popcll(m & below)] = r;
+      cnt += __popcll(m);
+    }
+    if (lane == 0) s_n[wave] = cnt;
+  }
+  __syncthreads();
+  const int np = s_n[0], ng = s_n[1];
+  // the pick: the first n_det / n_gt entries of the permutation that index a trimmed row, in permuted order
+  if (wave < 2) {
+    const int n = wave ? G : max_det, have = wave ? ng : np, want = wave ? n_gt : n_det;
+    const int* perm = wave ? s_pg : s_pd;
+    const int* list = wave ? s_grow : s_prow;
+    int* pick = wave ? s_gpick : s_dpick;
+    int taken = 0;
+    for (int base = 0; base < n && taken < want; base += 64) {     // (wave-uniform)
+      const int q = base + lane;
+      const int j = q < n ? perm[q] : -1;
+      const bool f = j >= 0 && j < have;
+      const unsigned long long m = __ballot(f);
+      const int pos = taken + __popcll(m & below);
+      if (f && pos < want) pick[pos] = list[j];
+      taken += __popcll(m);
+    }
+    if (lane == 0) s_n[2 + wave] = min(taken, want);
+  }
+  __syncthreads();
+  const int nd = s_n[2], nr = nd + s_n[3];     // nr <= n_det + n_gt <= roi_cap
+  for (int r = t; r < nr; r += MRB_NT) {
+    if (r < nd) {
+      const float* d = s_det + s_dpick[r] * 6;
+      s_rb[r][0] = d[0]; s_rb[r][1] = d[1]; s_rb[r][2] = d[2]; s_rb[r][3] = d[3];
+    } else {
+      const float* g = s_tb + s_gpick[r - nd] * 5;
+      s_rb[r][0] = g[1] - g[3] / 2.f; s_rb[r][1] = g[0] - g[2] / 2.f;
+      s_rb[r][2] = g[1] + g[3] / 2.f; s_rb[r][3] = g[0] + g[2] / 2.f;
+    }
+  }
+  __syncthreads();
+  for (int r = wave; r < nr; r += MRB_NW) {
+    const float r0 = s_rb[r][0], r1 = s_rb[r][1], r2 = s_rb[r][2], r3 = s_rb[r][3];
+    float best = -INFINITY;
+    int arg = 0x7fffffff;
+    for (int j = lane; j < ng; j += 64) {
+      const float* g = s_tb + s_grow[j] * 5;
+      const float gy1 = g[1] - g[3] / 2.f, gx1 = g[0] - g[2] / 2.f, gy2 = g[1] + g[3] / 2.f, gx2 = g[0] + g[2] / 2.f;
+      const float y1 = fmaxf(r0, gy1), x1 = fmaxf(r1, gx1);
+      const float y2 = fminf(r2, gy2), x2 = fminf(r3, gx2);
+      const float inter = fmaxf(x2 - x1, 0.f) * fmaxf(y2 - y1, 0.f);
+      const float a1 = (r2 - r0) * (r3 - r1);
+      const float a2 = (gy2 - gy1) * (gx2 - gx1);
+      const float iou = inter / (a1 + a2 - inter);
+      if (iou > best) {  // this lane's first maximum; NaN never wins
+        best = iou;
+        arg = j;
+      }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const float v2 = __shfl_xor(best, o, 64);
+      const int a2 = __shfl_xor(arg, o, 64);
+      if (v2 > best || (v2 == best && a2 < arg)) {
+        best = v2;
+        arg = a2;
+      }
+    }
+    if (arg == 0x7fffffff) arg = 0;     // nothing won (every IoU NaN or -inf): the serial form's arg = 0, best = -inf
+    if (lane == 0) s_arg[r] = (ng > 0 && best >= iou_thr) ? s_grow[arg] : -1;
+  }
+  __syncthreads();
+  int* out = rois + (size_t)b * roi_cap * RW;
+  int cnt = 0;
+  for (int base = 0; base < nr; base += MRB_NT) {       // (block-uniform)
+    const int r = base + t;
+    const bool f = r < nr && s_arg[r] >= 0;
+    int total;
+    const int row = cnt + block_rank<MRB_NW>(f, s_w, total);
+    if (f) {
+      // y-coordinates scale by the map's height, x-coordinates by its width (the reference's one `size` at Hm = Wm, :842)
+      const float szy = (float)Hm, szx = (float)Wm;
+      const float y1 = rintf(s_rb[r][0] * szy), x1 = rintf(s_rb[r][1] * szx);
+      const float y2 = rintf(s_rb[r][2] * szy), x2 = rintf(s_rb[r][3] * szx);
+      int gy[K + 1], gx[K + 1];
+      bin_edges<K>(y1, y2, gy);
+      bin_edges<K>(x1, x2, gx);
+      int* o = out + row * RW;
+      for (int k = 0; k <= K; ++k) {
+        o[k] = gy[k];
+        o[K + 1 + k] = gx[k];
+      }
+      o[2 * K + 2] = s_arg[r];
+      // mask_object pixel count (:848): sum over the k*k bins, clipped to the map
+      int area = 0;
+      for (int by = 0; by < K; ++by)
+        for (int bx = 0; bx < K; ++bx) {
+          const int hh = min(gy[by + 1], Hm) - max(gy[by], 0), ww = min(gx[bx + 1], Wm) - max(gx[bx], 0);
+          if (hh > 0 && ww > 0) area += hh * ww;
+        }
+      o[2 * K + 3] = area;
+      o[2 * K + 4] = 1;
+      o[2 * K + 5] = 0;
+    }
+    cnt += total;
+  }
+  for (int e = cnt * RW + t; e < roi_cap * RW; e += MRB_NT) out[e] = 0;
+  if (t == 0) roi_count[b] = cnt;
+}
+
+// The mask loss and its gradient over a table of up to ROI_CAP rows.  One thread per score-map pixel, as in
+// psroi_loss_kernel, but a pixel no longer tests every slot: the block culls the table to the rows that meet its pixel span
+// (its row range, and its column range when it lies within one row of the map) by an ordered compaction, copies those rows
+// to LDS in ascending RoI order, and every thread walks that list alone with psroi_loss_kernel's arithmetic.  A pixel so
+// adds the terms of the RoIs that cover it in the narrow kernel's order: dscore has the same bits on a table both can take.
+// The k*k gradient accumulators stay in registers.  Per RoI of the list the four waves' sums are combined in wave order,
+// again as the narrow kernel does; the block writes one partial per RoI of the table, zeros for the culled ones.
+template <int K>
+__global__ __launch_bounds__(256) void psroi_loss_wide_kernel(const float* score, const uint8_t* true_masks, int G,
+                                                              const int* rois, const int* roi_count, int roi_cap, int B,
+                                                              int Hm, int Wm, int st, float mask_scale, bf16* dscore,
+                                                              float* partial) {
+  constexpr int RW = roi_w(K), KK = K * K, LD = dscore_ld(K);
+  static_assert(RW % 4 == 0, "RoI rows are copied 16 bytes at a time");
+  __shared__ int4 s_roi4[ROI_CAP * RW / 4];   // the culled rows, compacted
+  __shared__ short s_idx[ROI_CAP];            // table row of each list entry
+  __shared__ float s_red[4][ROI_CAP];         // per wave, per list entry
+  __shared__ float s_out[ROI_CAP];            // per table row
+  __shared__ int s_w[4];
+  int* s_roi = reinterpret_cast<int*>(s_roi4);
+  const int b = blockIdx.y, t = threadIdx.x;
+  const int cnt = min(max(roi_count[b], 0), roi_cap);
+  const int npx = Hm * Wm;
+  const int i0 = blockIdx.x * 256, i1 = min(i0 + 255, npx - 1);
+  const int ylo = i0 / Wm, yhi = i1 / Wm;
+  const int xlo = ylo == yhi ? i0 - ylo * Wm : 0, xhi = ylo == yhi ? i1 - ylo * Wm : Wm - 1;
+  const int* tab = rois + (size_t)b * roi_cap * RW;
+  int nl = 0;
+  for (int base = 0; base < cnt; base += 256) {      // (block-uniform)
+    const int r = base + t;
+    bool f = false;
+    if (r < cnt) {
+      const int* o = tab + r * RW;
+      f = o[0] <= yhi && o[K] > ylo && o[K + 1] <= xhi && o[2 * K + 1] > xlo;
+    }
+    int total;
+    const int e = nl + block_rank<4>(f, s_w, total);
+    if (f) {
+      const int4* src = reinterpret_cast<const int4*>(tab + r * RW);
+#pragma unroll
+      for (int q = 0; q < RW / 4; ++q) s_roi4[e * (RW / 4) + q] = src[q];
+      s_idx[e] = (short)r;
+    }
+    nl += total;
+  }
+  for (int r = t; r < roi_cap; r += 256) s_out[r] = 0.f;
+  __syncthreads();
+  const int i = i0 + t;
+  const bool live = i < npx && cnt > 0;
+  const int y = i / Wm, x = i - y * Wm;
+  const float* sc = score + ((size_t)b * npx + (live ? i : 0)) * KK;
+  const int SH = st * Hm, SW = st * Wm;
+  const float coef0 = mask_scale / ((float)B * (float)cnt);
+  float g[KK];
+#pragma unroll
+  for (int k = 0; k < KK; ++k) g[k] = 0.f;
+  for (int e = 0; e < nl; ++e) {
+    const int* o = s_roi + e * RW;
+    float term = 0.f;
+    const bool in = live && y >= o[0] && y < o[K] && x >= o[K + 1] && x < o[2 * K + 1];
+    if (in) {
+      int by = 0, bx = 0;
+#pragma unroll
+      for (int j = 1; j < K; ++j) {
+        by += y >= o[j];
+        bx += x >= o[K + 1 + j];
+      }
+      const int ch = by * K + bx;
+      const float logit = sc[ch];
+      // GT mask down-sampled by exact st-x legacy bilinear == [::st, ::st] (:773-775)
+      const float gt = true_masks[(((size_t)b * G + o[2 * K + 2]) * SH + st * y) * SW + st * x] ? 1.f : 0.f;
+      const float inv_area = 1.f / (float)o[2 * K + 3];
+      term = sigmoid_ce(gt, logit) * inv_area;
+      const float dv = (sigmoidf_(logit) - gt) * inv_area * coef0;
+#pragma unroll
+      for (int k = 0; k < KK; ++k) g[k] += (k == ch) ? dv : 0.f;
+    }
+    float s = 0.f;
+    if (__ballot(in) != 0ull) s = wave_sum(term);     // (wave-uniform)
+    if ((t & 63) == 0) s_red[t >> 6][e] = s;
+  }
+  if (i < npx) {
+    uint4* o = reinterpret_cast<uint4*>(dscore + ((size_t)b * npx + i) * LD);
+#pragma unroll
+    for (int c = 0; c < LD / 8; ++c) {
+      float v[8];
+#pragma unroll
+      for (int k = 0; k < 8; ++k) v[k] = c * 8 + k < KK ? g[c * 8 + k] : 0.f;
+      o[c] = pack8(v);
+    }
+  }
+  __syncthreads();
+  for (int e = t; e < nl; e += 256) s_out[s_idx[e]] = s_red[0][e] + s_red[1][e] + s_red[2][e] + s_red[3][e];
+  __syncthreads();
+  float* prow = partial + ((size_t)b * gridDim.x + blockIdx.x) * roi_cap;
+  for (int r = t; r < roi_cap; r += 256) prow[r] = s_out[r];
+}
+
+// per image, for the wide table: 64 RoIs x 16 partial-row slices a pass (psroi_loss_image_kernel's shape, 16 RoIs x 16
+// slices, four times over).  Slice l sums blocks l, l + 16, ... of its RoI in f64, the 16 slice sums are added in slice
+// order, an RoI whose area is 0 counts as NaN; the RoI sums are then added lane-strided in RoI order and
+// combined by a fixed tree.  (One thread per RoI over all the blocks was 324 dependent loads a thread at 288^2: 450 us.)
+__global__ __launch_bounds__(1024) void psroi_loss_image_wide_kernel(const float* partial, const int* rois,
+                                                                     const int* roi_count, int roi_cap, int nblk, int rw,
+                                                                     float mask_scale, float* img_loss) {
+  __shared__ double sh[ROI_CAP];
+  __shared__ double sh_part[16][64];
+  const int b = blockIdx.x, t = threadIdx.x, q = t & 63, l = t >> 6;
+  const int cnt = min(max(roi_count[b], 0), roi_cap);
+  for (int base = 0; base < cnt; base += 64) {        // (block-uniform)
+    const int r = base + q;
+    double acc = 0.0;
+    if (r < cnt) {
+#pragma unroll 4
+      for (int k = l; k < nblk; k += 16) acc += (double)partial[((size_t)b * nblk + k) * roi_cap + r];
+    }
+    sh_part[l][q] = acc;
+    __syncthreads();
+    if (l == 0 && r < cnt) {
+      double s = 0.0;
+#pragma unroll
+      for (int k = 0; k < 16; ++k) s += sh_part[k][q];
+      if (rois[((size_t)b * roi_cap + r) * rw + rw - 3] == 0) s = NAN;   // the area word
+      sh[r] = s;
+    }
+    __syncthreads();
+  }
+  if (t < 64) {
+    double img = 0.0;
+    for (int r = t; r < cnt; r += 64) img += sh[r];
+    img = wave_sum_d(img);
+    if (t == 0) img_loss[b] = cnt > 0 ? (float)((double)mask_scale * img / (double)cnt) : 0.f;
+  }
+}
+
 }  // namespace
 
 extern "C" size_t disyolo_yolo_loss_workspace_hw(int B, int H, int W, int num_class) {
@@ -995,6 +1311,69 @@ extern "C" int disyolo_psroi_loss_hw(const float* score, const uint8_t* true_mas
   float* img_loss = (float*)workspace + (size_t)B * nblk * ROI_MAX;
   hipLaunchKernelGGL(psroi_loss_image_kernel, dim3(B), dim3(256), 0, st, (const float*)workspace, rois, roi_count,
                      nblk, roi_w(k), mask_scale, img_loss);
+  DY_CHECK_LAUNCH();
+  hipLaunchKernelGGL(psroi_loss_final_kernel, dim3(1), dim3(64), 0, st, (const float*)img_loss, B, loss);
+  DY_CHECK_LAUNCH();
+  return DISYOLO_OK;
+}
+
+// ---- up to DISYOLO_ROI_CAP RoIs per image ----
+extern "C" int disyolo_mask_rois_x(const float* detections, int max_det, const float* true_boxes, int G,
+                                   const int32_t* perm_det, const int32_t* perm_gt, int B, int map_h, int map_w, int k,
+                                   int n_det, int n_gt, float iou_thresh, int roi_cap, int32_t* rois, int32_t* roi_count,
+                                   void* stream) {
+  DY_REQUIRE(detections && true_boxes && rois && roi_count, "mask_rois_x: null pointer");
+  DY_REQUIRE(kmap_supported(k), "mask_rois_x: k must be one of k = 3, 5, 7 (got %d)", k);
+  DY_REQUIRE(B > 0 && map_h > 0 && map_w > 0, "mask_rois_x: bad sizes");
+  DY_REQUIRE(max_det > 0 && max_det <= DISYOLO_MAX_DET && G > 0 && G <= DISYOLO_MAX_BOXES,
+             "mask_rois_x: bad sizes (max_det must be in 1..%d and G in 1..%d, got %d and %d)", DISYOLO_MAX_DET,
+             DISYOLO_MAX_BOXES, max_det, G);
+  DY_REQUIRE(roi_cap > 0 && roi_cap <= ROI_CAP, "mask_rois_x: roi_cap must be in 1..%d (got %d)", ROI_CAP, roi_cap);
+  DY_REQUIRE(n_det >= 0 && n_gt >= 0 && n_det <= ROI_CAP && n_gt <= ROI_CAP && n_det + n_gt <= roi_cap,
+             "mask_rois_x: n_det + n_gt > roi_cap (got %d + %d, roi_cap %d)", n_det, n_gt, roi_cap);
+  DY_RECORD_OR_RUN([=](void* s) {
+    return disyolo_mask_rois_x(detections, max_det, true_boxes, G, perm_det, perm_gt, B, map_h, map_w, k, n_det, n_gt,
+                               iou_thresh, roi_cap, rois, roi_count, s);
+  });
+  auto kern = k == 3 ? mask_rois_block_kernel<3> : k == 5 ? mask_rois_block_kernel<5> : mask_rois_block_kernel<7>;
+  hipLaunchKernelGGL(kern, dim3(B), dim3(MRB_NT), 0, (hipStream_t)stream, detections, max_det, true_boxes, G, perm_det,
+                     perm_gt, B, map_h, map_w, n_det, n_gt, iou_thresh, roi_cap, rois, roi_count);
+  DY_CHECK_LAUNCH();
+  return DISYOLO_OK;
+}
+
+extern "C" size_t disyolo_psroi_loss_workspace_x(int B, int map_h, int map_w, int roi_cap) {
+  if (B <= 0 || map_h <= 0 || map_w <= 0 || roi_cap <= 0 || roi_cap > ROI_CAP) return 0;
+  return ((size_t)B * ceil_div((size_t)map_h * map_w, 256) * roi_cap + B) * sizeof(float);
+}
+
+extern "C" int disyolo_psroi_loss_x(const float* score, const uint8_t* true_masks, int G, const int32_t* rois,
+                                    const int32_t* roi_count, int roi_cap, int B, int map_h, int map_w, int mask_stride,
+                                    int k, float mask_scale, void* dscore, float* loss, void* workspace,
+                                    size_t workspace_bytes, void* stream) {
+  DY_REQUIRE(score && true_masks && rois && roi_count && dscore && loss, "psroi_loss_x: null pointer");
+  DY_REQUIRE(B > 0 && map_h > 0 && map_w > 0 && (int64_t)map_h * map_w <= (1ll << 30) && G > 0, "psroi_loss_x: bad sizes");
+  DY_REQUIRE(roi_cap > 0 && roi_cap <= ROI_CAP, "psroi_loss_x: roi_cap must be in 1..%d (got %d)", ROI_CAP, roi_cap);
+  DY_REQUIRE(kmap_supported(k), "psroi_loss_x: k must be one of k = 3, 5, 7 (got %d)", k);
+  DY_REQUIRE(mask_stride == 1 || mask_stride == 2 || mask_stride == 4,
+             "psroi_loss_x: mask_stride must be one of 1, 2, 4 (got %d)", mask_stride);
+  if (!workspace || workspace_bytes < disyolo_psroi_loss_workspace_x(B, map_h, map_w, roi_cap)) {
+    disyolo_set_error("psroi_loss_x: workspace too small");
+    return DISYOLO_E_WORKSPACE;
+  }
+  DY_RECORD_OR_RUN([=](void* s) {
+    return disyolo_psroi_loss_x(score, true_masks, G, rois, roi_count, roi_cap, B, map_h, map_w, mask_stride, k, mask_scale,
+                                dscore, loss, workspace, workspace_bytes, s);
+  });
+  hipStream_t st = (hipStream_t)stream;
+  const int nblk = ceil_div((size_t)map_h * map_w, 256);
+  auto kern = k == 3 ? psroi_loss_wide_kernel<3> : k == 5 ? psroi_loss_wide_kernel<5> : psroi_loss_wide_kernel<7>;
+  hipLaunchKernelGGL(kern, dim3(nblk, B), dim3(256), 0, st, score, true_masks, G, rois, roi_count, roi_cap, B, map_h, map_w,
+                     mask_stride, mask_scale, (bf16*)dscore, (float*)workspace);
+  DY_CHECK_LAUNCH();
+  float* img_loss = (float*)workspace + (size_t)B * nblk * roi_cap;
+  hipLaunchKernelGGL(psroi_loss_image_wide_kernel, dim3(B), dim3(1024), 0, st, (const float*)workspace, rois, roi_count,
+                     roi_cap, nblk, roi_w(k), mask_scale, img_loss);
   DY_CHECK_LAUNCH();
   hipLaunchKernelGGL(psroi_loss_final_kernel, dim3(1), dim3(64), 0, st, (const float*)img_loss, B, loss);
   DY_CHECK_LAUNCH();

@@ -21,6 +21,7 @@ MAX_BOXES = 256            # DISYOLO_MAX_BOXES: ground-truth boxes per image (yo
 MAX_DET = 256              # DISYOLO_MAX_DET: detections per image (detect, mask_rois, the batched paste)
 ROI_MAX = 16
 ROI_W = 12
+ROI_CAP = 512              # DISYOLO_ROI_CAP: rows of the RoI table the _x forms of mask_rois / psroi_loss take
 K_MAPS = (3, 5, 7)          # position-sensitive grids the mask path covers (the reference's list)
 MASK_STRIDES = (1, 2, 4)    # GT mask -> score map sampling steps psroi_loss_s covers (score maps at S, S/2, S/4)
 # which candidates above the score threshold the detection filter keeps (DISYOLO_NMS_* of disyolo.h; filter_detections,
@@ -164,6 +165,11 @@ _SIGS = {
     "disyolo_psroi_loss_workspace_hw": (C.c_size_t, [C.c_int] * 3),
     "disyolo_psroi_loss_hw": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p] + [C.c_int] * 5 +
                               [C.c_float] + [C.c_void_p] * 3 + [C.c_size_t, C.c_void_p]),
+    "disyolo_mask_rois_x": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p] + [C.c_int] * 6 +
+                            [C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "disyolo_psroi_loss_workspace_x": (C.c_size_t, [C.c_int] * 4),
+    "disyolo_psroi_loss_x": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p] + [C.c_int] * 6 +
+                             [C.c_float] + [C.c_void_p] * 3 + [C.c_size_t, C.c_void_p]),
     "disyolo_psroi_assemble_hw": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p] * 3),
     "disyolo_psroi_loss": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p] + [C.c_int] * 3 +
                            [C.c_float] + [C.c_void_p] * 3 + [C.c_size_t, C.c_void_p]),
@@ -1205,6 +1211,34 @@ def psroi_loss(score, true_masks, G, rois, roi_count, B, map_size, k, mask_scale
     buf = ws.get(need)
     _check(load().disyolo_psroi_loss_hw(_p(score), _p(true_masks), G, _p(rois), _p(roi_count), B, Hm, Wm, mask_stride, k,
                                         mask_scale, _p(dscore), _p(loss), _p(buf), buf.numel(), _stream()), "psroi_loss")
+
+
+def mask_rois_x(detections, max_det, true_boxes, G, perm_det, perm_gt, B, map_size, n_det, n_gt, iou_thresh, rois,
+                roi_count, k: int = 3) -> None:
+    """mask_rois for n_det + n_gt up to ROI_CAP: rois int32 [B, roi_cap, roi_w(k)] with roi_cap >= n_det + n_gt"""
+    if rois.dim() != 3 or rois.shape[0] != B or rois.shape[2] != roi_w(k):
+        raise DisyoloError("mask_rois_x: rois must be [%d, roi_cap, %d] (got %s)" % (B, roi_w(k), tuple(rois.shape)))
+    Hm, Wm = hw_of(map_size)
+    _check(load().disyolo_mask_rois_x(_p(detections), max_det, _p(true_boxes), G, _p(perm_det), _p(perm_gt), B, Hm, Wm,
+                                      k, n_det, n_gt, iou_thresh, rois.shape[1], _p(rois), _p(roi_count), _stream()),
+           "mask_rois_x")
+
+
+def psroi_loss_workspace_x(B, map_size, roi_cap) -> int:
+    Hm, Wm = hw_of(map_size)
+    return int(load().disyolo_psroi_loss_workspace_x(B, Hm, Wm, roi_cap))
+
+
+def psroi_loss_x(score, true_masks, G, rois, roi_count, B, map_size, k, mask_scale, dscore, loss, ws: Workspace,
+                 mask_stride: int = 2) -> None:
+    """psroi_loss on a table rois int32 [B, roi_cap, roi_w(k)] of up to ROI_CAP rows"""
+    Hm, Wm = hw_of(map_size)
+    roi_cap = rois.shape[1]
+    need = load().disyolo_psroi_loss_workspace_x(B, Hm, Wm, roi_cap)
+    buf = ws.get(need)
+    _check(load().disyolo_psroi_loss_x(_p(score), _p(true_masks), G, _p(rois), _p(roi_count), roi_cap, B, Hm, Wm,
+                                       mask_stride, k, mask_scale, _p(dscore), _p(loss), _p(buf), buf.numel(), _stream()),
+           "psroi_loss_x")
 
 
 def psroi_assemble(score, detections, B, max_det, map_size, k, masks, keep) -> None:

@@ -204,13 +204,37 @@ def check_limit(value, name: str) -> int:
     return int(value)
 
 
+MAX_MASK_ROI = 256   # per kind: every detection (DISYOLO_MAX_DET) and every box (DISYOLO_MAX_BOXES) of an image
+
+
+def check_mask_roi_count(value, name: str) -> int:
+    """``mask_roi_det`` / ``mask_roi_gt``: an int in 0..256 (bools are refused); 0 leaves that kind of RoI out"""
+    if isinstance(value, bool) or not isinstance(value, (int, np.integer)):
+        raise ValueError("%s must be an int in 0..%d (got %r)" % (name, MAX_MASK_ROI, value))
+    if not 0 <= int(value) <= MAX_MASK_ROI:
+        raise ValueError("%s must be in 0..%d (got %d)" % (name, MAX_MASK_ROI, int(value)))
+    return int(value)
+
+
+def check_mask_roi_iou(value) -> float:
+    """``mask_roi_iou``: loss_mask's iou_threshold (yolo/yolo3_net_pos.py:750), a finite float in (0, 1]"""
+    if isinstance(value, bool) or not isinstance(value, (int, float, np.integer, np.floating)):
+        raise ValueError("mask_roi_iou must be a float in (0, 1] (got %r)" % (value,))
+    v = float(value)
+    if not (math.isfinite(v) and 0.0 < v <= 1.0):
+        raise ValueError("mask_roi_iou must be in (0, 1] (got %r)" % (value,))
+    return v
+
+
 class YOLONet(object):
     def __init__(self, training: bool = False, device=None, image_size=None,
                  batch_size: Optional[int] = None, stage: int = 1, lock: Optional[Dict[int, bool]] = None,
                  seed: int = 0, xavier_locked: bool = True, plan_only: bool = False, dtype: str = "bf16",
                  backbone_pair: bool = False, k_map: Optional[int] = None, mask_stride: Optional[int] = None,
                  classes: Optional[Sequence[str]] = None, nms: Optional[str] = None, anchors=None,
-                 max_box_per_image: Optional[int] = None, max_detection: Optional[int] = None):
+                 max_box_per_image: Optional[int] = None, max_detection: Optional[int] = None,
+                 mask_roi_det: Optional[int] = None, mask_roi_gt: Optional[int] = None,
+                 mask_roi_iou: Optional[float] = None):
         # 1. parameters (yolo/yolo3_net_pos.py:15-38)
         self.batchsize = int(batch_size if batch_size is not None else cfg.BATCH_SIZE)
         # the class list (CLASSES of yolo/config.py): cfg.CLASSES unless given; it sizes the three heads
@@ -223,8 +247,19 @@ class YOLONet(object):
         self.max_box_per_image = check_limit(cfg.MAX_BOX_PER_IMAGE if max_box_per_image is None else max_box_per_image,
                                              "max_box_per_image")
         self.max_detection = check_limit(cfg.MAX_DETECTION if max_detection is None else max_detection, "max_detection")
+        # the mask loss's RoIs per image (`add_proposals[:7]`, `add_gt_boxes[:3]`, yolo/yolo3_net_pos.py:783) and loss_mask's
+        # iou_threshold (:750): the cfg values at construction unless given.  A count above the number of non-zero rows takes
+        # them all; 0 leaves that kind out.  Up to 16 RoIs run on the table and kernels of DISYOLO_ROI_MAX, more on the
+        # _x forms with a table of exactly mask_roi_det + mask_roi_gt rows
+        self.mask_roi_det = check_mask_roi_count(cfg.MASK_ROI_DET if mask_roi_det is None else mask_roi_det, "mask_roi_det")
+        self.mask_roi_gt = check_mask_roi_count(cfg.MASK_ROI_GT if mask_roi_gt is None else mask_roi_gt, "mask_roi_gt")
+        if self.mask_roi_det + self.mask_roi_gt < 1:
+            raise ValueError("mask_roi_det + mask_roi_gt must be at least 1 (got %d + %d)"
+                             % (self.mask_roi_det, self.mask_roi_gt))
+        self.mask_roi_iou = check_mask_roi_iou(cfg.MASK_ROI_IOU if mask_roi_iou is None else mask_roi_iou)
+        self.mask_roi_rows = max(self.mask_roi_det + self.mask_roi_gt, L.ROI_MAX)
         self.num_anchor = 3
-        self.output_depth = (self.num_class + 5) * self.num_anchor
+        self.output_depth =(self.num_class + 5) * self.num_anchor
         # k_map x k_map position-sensitive score maps (conv82 emits k_map^2 channels); cfg.K_MAP unless given
         self.k = int(k_map if k_map is not None else cfg.K_MAP)
         if self.k not in L.K_MAPS:
@@ -574,7 +609,7 @@ class YOLONet(object):
             self.true_masks = torch.zeros(B, G, H, W, dtype=torch.uint8, device=dev)
             self.perm_det = torch.arange(self.max_detection, dtype=torch.int32, device=dev).repeat(B, 1).contiguous()
             self.perm_gt = torch.arange(G, dtype=torch.int32, device=dev).repeat(B, 1).contiguous()
-            self.rois = torch.zeros(B, L.ROI_MAX, L.roi_w(self.k), dtype=torch.int32, device=dev)
+            self.rois = torch.zeros(B, self.mask_roi_rows, L.roi_w(self.k), dtype=torch.int32, device=dev)
             self.roi_count = torch.zeros(B, dtype=torch.int32, device=dev)
             self._in_sets = None
             if self.pair:     # the per-batch inputs of the trainable part, once per half
@@ -602,6 +637,8 @@ class YOLONet(object):
                     need = max(need, L.load().disyolo_bn_act_bwd_workspace(B * l.Ho * l.Wo, l.cout))
             if not l1.lock:
                 need = max(need, L.load().disyolo_conv_first_wgrad_workspace(B, H, W, l1.cout))
+            if self.mask_roi_rows > L.ROI_MAX:      # the wide mask loss: one partial per (block, table row)
+                need = max(need, L.psroi_loss_workspace_x(B, self.mask_map_size(), self.mask_roi_rows))
             self.ws.get(int(need))
             self.ws_aux.get(int(need))
         self.ws_det.get(int(max(L.detect_workspace(B, (H, W), self.num_class, self.max_detection), 1 << 20)))
@@ -1428,14 +1465,18 @@ class YOLONet(object):
             L.shuffle_perm(self.perm_det, self.perm_gt, self.B, int(self.shuffle_seed) & 0xffffffff, self.step_dev)
         self._detect(det_thresh)
         Sm = self.mask_map_size()
-        L.mask_rois(self.detections, self.max_detection, self.true_boxes, self.max_box_per_image, self.perm_det,
-                    self.perm_gt, self.B, Sm, cfg.MASK_ROI_DET, cfg.MASK_ROI_GT, cfg.MASK_ROI_IOU, self.rois,
-                    self.roi_count, k=self.k)
+        # more than DISYOLO_ROI_MAX RoIs per image: the _x pair on the table of mask_roi_det + mask_roi_gt rows
+        wide = self.mask_roi_rows > L.ROI_MAX
+        (L.mask_rois_x if wide else L.mask_rois)(
+            self.detections, self.max_detection, self.true_boxes, self.max_box_per_image, self.perm_det,
+            self.perm_gt, self.B, Sm, self.mask_roi_det, self.mask_roi_gt, self.mask_roi_iou, self.rois,
+            self.roi_count, k=self.k)
         if side:
             L.lane_sync(0, 1)
         m = self.by_idx[self.score_layer]
-        L.psroi_loss(m.act, self.true_masks, self.max_box_per_image, self.rois, self.roi_count, self.B, Sm, self.k,
-                     self.mask_scale, m.dx, self.mask_loss, self.ws_aux if side else self.ws, mask_stride=self.mask_stride)
+        (L.psroi_loss_x if wide else L.psroi_loss)(
+            m.act, self.true_masks, self.max_box_per_image, self.rois, self.roi_count, self.B, Sm, self.k,
+            self.mask_scale, m.dx, self.mask_loss, self.ws_aux if side else self.ws, mask_stride=self.mask_stride)
         # the mask subnet's backward waits for THIS point of the side lane (not for the weight gradients
         # that lane picks up afterwards: a whole-lane sync there kept the main lane idle for 250-500 us)
         self._mask_mark = L.lane_mark(1) if side else -1

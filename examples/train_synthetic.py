@@ -78,6 +78,15 @@ def parse_anchors(text):
     return np.asarray(vals, np.float32).reshape(9, 2)
 
 
+def parse_mask_rois(text):
+    """"40,20" -> (40, 20) = (mask_roi_det, mask_roi_gt): the detections and the ground-truth boxes of an image the mask loss
+    trains on per step, each 0..256, at least one in all (the reference's `[:7]` and `[:3]`, yolo/yolo3_net_pos.py:783)"""
+    parts = text.split(",")
+    if len(parts) != 2:
+        raise argparse.ArgumentTypeError("--mask-rois takes N_DET,N_GT (got %r)" % text)
+    return int(parts[0]), int(parts[1])
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=40)
@@ -102,6 +111,9 @@ def main():
     ap.add_argument("--anchors", type=parse_anchors, default=None,
                     help="the nine anchors (w, h) in net pixels, smallest first: 'auto' clusters the dataset's boxes at --size "
                          "(train_data.cluster_anchors), or 18 numbers w,h,...; cfg.ANCHORS unless given")
+    ap.add_argument("--mask-rois", type=parse_mask_rois, default=(cfg.MASK_ROI_DET, cfg.MASK_ROI_GT), metavar="N_DET,N_GT",
+                    help="RoIs per image of the mask loss: the first N_DET detections and the first N_GT ground-truth boxes in "
+                         "shuffled order, each 0..256 (cfg.MASK_ROI_DET, cfg.MASK_ROI_GT); 256,256 takes them all")
     args = ap.parse_args()
     classes = [c.strip() for c in args.classes.split(",")]
     dev = torch.device("cuda:0")
@@ -118,7 +130,7 @@ def main():
                         classes=classes, **limits)
     net = YOLONet(training=True, device=dev, image_size=args.size, batch_size=args.batch, stage=1, seed=0, k_map=args.k_map,
                   mask_stride=args.mask_stride, lock=parse_lock(args.lock), classes=classes, nms=args.nms, max_detection=args.max_det,
-                  **limits)
+                  mask_roi_det=args.mask_rois[0], mask_roi_gt=args.mask_rois[1], **limits)
     if net.pass_through_layers():
         print("locked layers the gradient crosses:", net.pass_through_layers())
     solver = Solver(net, data, output_dir=args.out, max_iter=args.steps, summary_iter=max(1, args.steps // 4),

@@ -521,6 +521,25 @@ int disyolo_psroi_loss_hw(const float* score, const uint8_t* true_masks, int G, 
                           const int32_t* roi_count, int B, int map_h, int map_w, int mask_stride, int k,
                           float mask_scale, void* dscore, float* loss, void* workspace,
                           size_t workspace_bytes, void* stream);
+/* The mask loss on more than DISYOLO_ROI_MAX RoIs per image (the reference's `[:7]` and `[:3]`, :783, as two counts of the
+ * net).  The entry points above keep their table of DISYOLO_ROI_MAX rows; the _x forms take a table of roi_cap rows,
+ * n_det + n_gt <= roi_cap <= DISYOLO_ROI_CAP, with the same row layout: positives first in RoI order, rows from
+ * roi_count[b] on zero.  A count above the number of non-zero rows takes them all.  On a table both forms can take, the
+ * selection writes the same rows and the loss the same dscore bits.
+ * disyolo_mask_rois_x: rois int32 [B,roi_cap,DISYOLO_ROI_W_K(k)]; one block of sixteen waves per image (ordered compaction
+ * for the trimmed lists, the pick and the positives; the IoU arg-max of an RoI across a wave's lanes).
+ * disyolo_psroi_loss_x: every block culls the table to the rows that meet its 256 pixels and walks those alone, in RoI
+ * order; its workspace holds one f32 partial per (block, table row). */
+#define DISYOLO_ROI_CAP 512
+int disyolo_mask_rois_x(const float* detections, int max_det, const float* true_boxes, int G,
+                        const int32_t* perm_det, const int32_t* perm_gt, int B, int map_h, int map_w, int k,
+                        int n_det, int n_gt, float iou_thresh, int roi_cap, int32_t* rois, int32_t* roi_count,
+                        void* stream);
+size_t disyolo_psroi_loss_workspace_x(int B, int map_h, int map_w, int roi_cap);
+int disyolo_psroi_loss_x(const float* score, const uint8_t* true_masks, int G, const int32_t* rois,
+                         const int32_t* roi_count, int roi_cap, int B, int map_h, int map_w, int mask_stride, int k,
+                         float mask_scale, void* dscore, float* loss, void* workspace,
+                         size_t workspace_bytes, void* stream);
 /* inference assembly (val_test, :862-938): masks f32 [B,max_det,Sm,Sm] = sigmoid(selected
  * channel) inside the box, 0.5 outside; keep int32 [B,max_det] = 1 for rows with h>0 and w>0.
  * k = 3, 5 or 7; score f32 [B,Sm,Sm,k*k]. */
