@@ -182,6 +182,17 @@ _SIGS = {
                                         C.c_void_p, C.c_void_p, C.c_void_p]),
     "disyolo_letterbox": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "disyolo_letterbox_hw": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "disyolo_tile_gather": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
+                                      C.c_int, C.c_void_p]),
+    "disyolo_tile_paste_bits": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
+                                          C.c_void_p]),
+    "disyolo_tile_seam_counts": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                           C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
+                                           C.c_void_p]),
+    "disyolo_tile_compose_blocks": (C.c_int, [C.c_int64]),
+    "disyolo_tile_compose": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                       C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                       C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "disyolo_confusion16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "disyolo_confusion_n": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p]),
     "disyolo_paste_job_size": (C.c_size_t, []),
@@ -1006,6 +1017,118 @@ def letterbox(rgb_u8, out, size):
     _check(load().disyolo_letterbox_hw(_p(rgb_u8), int(rgb_u8.shape[0]), int(rgb_u8.shape[1]), _p(out), nh, nw, win,
                                        _stream()), "letterbox")
     return np.array(list(win), np.float32)
+
+
+def _table(host, cols: int, name: str, dev, device):
+    """a host int32 table the library checks before it launches, and its device copy (uploaded here when not given)"""
+    host = np.ascontiguousarray(host, dtype=np.int32)
+    if host.ndim != (1 if cols == 1 else 2) or (cols > 1 and host.shape[1] != cols):
+        raise DisyoloError("%s must be an int32 table with %d column(s) (got shape %s)" % (name, cols, host.shape))
+    if dev is None:
+        dev = torch.from_numpy(host).to(device)
+    _need(dev, torch.int32, name)
+    _need_shape(dev, host.shape, name)
+    return host, dev
+
+
+def tile_gather(rgb_u8, origins_dev, t0: int, t1: int, out, size) -> None:
+    """rgb_u8 uint8 CUDA [h,w,3]; origins_dev int32 CUDA [T,2]; out f32 CUDA [t1-t0,net_h,net_w,3]: tiles t0 .. t1-1 (an index
+    >= T is a pad tile) in one launch (disyolo_tile_gather)"""
+    _need(rgb_u8, torch.uint8, "rgb")
+    _need(origins_dev, torch.int32, "origins")
+    _need(out, torch.float32, "out")
+    nh, nw = hw_of(size)
+    if rgb_u8.dim() != 3 or rgb_u8.shape[2] != 3 or origins_dev.dim() != 2 or origins_dev.shape[1] != 2:
+        raise DisyoloError("tile_gather: rgb must be [h,w,3] uint8 and origins [T,2] int32")
+    _need_shape(out, (int(t1) - int(t0), nh, nw, 3), "out")
+    _check(load().disyolo_tile_gather(_p(rgb_u8), int(rgb_u8.shape[0]), int(rgb_u8.shape[1]), _p(origins_dev),
+                                      int(origins_dev.shape[0]), int(t0), int(t1), _p(out), nh, nw, _stream()), "tile_gather")
+
+
+def tile_paste_bits(masks, rects, size, planes) -> None:
+    """masks f32 CUDA [n,Hm,Wm]; rects int32 CUDA [n,8]; planes uint32 bits as int32 CUDA [n,net_h,net_w/32]
+    (disyolo_tile_paste_bits); n = 0 launches nothing"""
+    nh, nw = hw_of(size)
+    n = int(rects.shape[0])
+    mh, mw = 1, 1
+    if n:
+        _need(masks, torch.float32, "masks")
+        _need(rects, torch.int32, "rects")
+        _need(planes, torch.int32, "planes")
+        if masks.dim() != 3 or int(masks.shape[0]) != n:
+            raise DisyoloError("tile_paste_bits: masks must be [n,Hm,Wm] with one mask per rect")
+        _need_shape(rects, (n, 8), "rects")
+        _need_shape(planes, (n, nh, max(nw // 32, 0)), "planes")
+        mh, mw = int(masks.shape[1]), int(masks.shape[2])
+    _check(load().disyolo_tile_paste_bits(_p(masks) if n else None, n, mh, mw, _p(rects) if n else None, nh, nw,
+                                          _p(planes) if n else None, _stream()), "tile_paste_bits")
+
+
+def tile_seam_counts(pairs, inst_tile, origins, image_hw, planes, size, inst_tile_dev=None, origins_dev=None):
+    """pairs [P,2], inst_tile [N], origins [T,2]: host int32 tables (checked before the launch; the device copies of the last
+    two may be passed in); planes int32 CUDA [N,net_h,net_w/32] -> counts int32 CUDA [P,3] = |A n R|, |B n R|, |A n B|
+    (disyolo_tile_seam_counts)"""
+    nh, nw = hw_of(size)
+    dev = planes.device
+    pairs, pairs_d = _table(np.asarray(pairs, np.int32).reshape(-1, 2), 2, "pairs", None, dev)
+    inst_tile, inst_tile_dev = _table(inst_tile, 1, "inst_tile", inst_tile_dev, dev)
+    origins, origins_dev = _table(origins, 2, "origins", origins_dev, dev)
+    P, N = int(pairs.shape[0]), int(inst_tile.shape[0])
+    if P:
+        _need(planes, torch.int32, "planes")
+        _need_shape(planes, (N, nh, max(nw // 32, 0)), "planes")
+    counts = torch.zeros(P, 3, dtype=torch.int32, device=dev)
+    _check(load().disyolo_tile_seam_counts(pairs.ctypes.data, _p(pairs_d), P, inst_tile.ctypes.data, _p(inst_tile_dev), N,
+                                           origins.ctypes.data, _p(origins_dev), int(origins.shape[0]), int(image_hw[0]),
+                                           int(image_hw[1]), _p(planes), nh, nw, _p(counts), _stream()), "tile_seam_counts")
+    return counts
+
+
+COMPOSE_CHUNK = 1024      # pixels of a group's box per block of disyolo_tile_compose (disyolo_tile_compose_blocks)
+
+
+def tile_compose_plan(boxes, member_start):
+    """boxes int32 [G,4] (y1,x1,y2,x2 in the image), member_start [G+1] (CSR) -> (groups int32 [G,8] = m0, m1, the box, block0,
+    off16 as disyolo_tile_compose takes them, the arena's size in bytes)"""
+    boxes = np.asarray(boxes, np.int64).reshape(-1, 4)
+    start = np.asarray(member_start, np.int64).reshape(-1)
+    G = int(boxes.shape[0])
+    if start.shape[0] != G + 1:
+        raise DisyoloError("tile_compose_plan: member_start must have one entry more than there are boxes")
+    if load().disyolo_tile_compose_blocks(COMPOSE_CHUNK) != 1 or load().disyolo_tile_compose_blocks(COMPOSE_CHUNK + 1) != 2:
+        raise DisyoloError("tile_compose_plan: the library's chunk is not %d pixels: rebuild it" % COMPOSE_CHUNK)
+    area = np.maximum(boxes[:, 2] - boxes[:, 0], 0) * np.maximum(boxes[:, 3] - boxes[:, 1], 0)
+    blocks = np.concatenate([[0], np.cumsum((area + COMPOSE_CHUNK - 1) // COMPOSE_CHUNK)])
+    off16 = np.concatenate([[0], np.cumsum((area + 15) // 16)])
+    if blocks[-1] >= 1 << 31 or off16[-1] >= 1 << 31:
+        raise DisyoloError("tile_compose_plan: the groups' boxes hold too many pixels for one launch")
+    groups = np.zeros((G, 8), np.int32)
+    groups[:, 0], groups[:, 1], groups[:, 2:6], groups[:, 6], groups[:, 7] = start[:-1], start[1:], boxes, blocks[:-1], off16[:-1]
+    return groups, int(off16[-1]) * 16
+
+
+def tile_compose(groups, members, inst_tile, origins, planes, size, image_hw, arena, owner, inst_tile_dev=None,
+                 origins_dev=None) -> None:
+    """groups [G,8] (tile_compose_plan), members [M], inst_tile [N], origins [T,2]: host int32 tables (checked before the
+    launch); planes int32 CUDA [N,net_h,net_w/32]; arena uint8 CUDA; owner int32 CUDA [h,w] (disyolo_tile_compose)"""
+    nh, nw = hw_of(size)
+    dev = owner.device
+    groups, groups_d = _table(np.asarray(groups, np.int32).reshape(-1, 8), 8, "groups", None, dev)
+    members, members_d = _table(members, 1, "members", None, dev)
+    inst_tile, inst_tile_dev = _table(inst_tile, 1, "inst_tile", inst_tile_dev, dev)
+    origins, origins_dev = _table(origins, 2, "origins", origins_dev, dev)
+    G, N = int(groups.shape[0]), int(inst_tile.shape[0])
+    _need(owner, torch.int32, "owner")
+    _need_shape(owner, (int(image_hw[0]), int(image_hw[1])), "owner")
+    if G:
+        _need(arena, torch.uint8, "arena")
+        _need(planes, torch.int32, "planes")
+        _need_shape(planes, (N, nh, max(nw // 32, 0)), "planes")
+    _check(load().disyolo_tile_compose(groups.ctypes.data, _p(groups_d), G, members.ctypes.data, _p(members_d),
+                                       int(members.shape[0]), inst_tile.ctypes.data, _p(inst_tile_dev), N, origins.ctypes.data,
+                                       _p(origins_dev), int(origins.shape[0]), _p(planes) if G else None, nh, nw,
+                                       int(image_hw[0]), int(image_hw[1]), _p(arena) if G else None,
+                                       int(arena.numel()) if G else 0, _p(owner), _stream()), "tile_compose")
 
 
 def polygon_mask(px, py, poly_start, poly_is_out, image_h: int, image_w: int, mask) -> None:

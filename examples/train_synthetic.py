@@ -5,6 +5,7 @@ inference net -> detections + instance masks for one image.
     python examples/train_synthetic.py [--steps 40] [--size 192 | --size 128x192] [--batch 4] [--out /tmp/disyolo_example] [--lock 62-64]
                                        [--classes crack,spall,rebar,stain,joint,void]
                                        [--max-boxes 100] [--max-det 100] [--anchors auto | --anchors w,h,w,h,... (9 pairs)]
+                                       [--tiled 500x700]
 
 It mirrors what the reference's ``train_yolo3_mask.py:237-248`` (train) and ``calculate_test_map.py`` (test) do
 with a real dataset; swap ``synthetic_labels`` for ``disyolo_amd.pre_process.load_verify_contour(path, 'train')``
@@ -114,6 +115,9 @@ def main():
     ap.add_argument("--mask-rois", type=parse_mask_rois, default=(cfg.MASK_ROI_DET, cfg.MASK_ROI_GT), metavar="N_DET,N_GT",
                     help="RoIs per image of the mask loss: the first N_DET detections and the first N_GT ground-truth boxes in "
                          "shuffled order, each 0..256 (cfg.MASK_ROI_DET, cfg.MASK_ROI_GT); 256,256 takes them all")
+    ap.add_argument("--tiled", type=parse_size, default=None, metavar="HxW",
+                    help="also run the trained net over one synthetic image of this size, larger than the net, cut into "
+                         "overlapping tiles whose instances are merged over the seams (disyolo_amd.tiles.detect_tiled)")
     args = ap.parse_args()
     classes = [c.strip() for c in args.classes.split(",")]
     dev = torch.device("cuda:0")
@@ -153,6 +157,21 @@ def main():
     h, w = rec["image"].shape[:2]
     entries, merged = postprocess.paste_detections(det_boxes[0], det_masks[0], h, w, args.size)
     print("%d detections on a %dx%d image; class map has %d labelled pixels" % (len(entries), h, w, int((merged > 0).sum())))
+
+    # --- an image larger than the net: tiles of the net's size, an instance that runs through several tiles becomes one
+    if args.tiled is not None:
+        from disyolo_amd import tiles
+        th, tw = (args.tiled, args.tiled) if isinstance(args.tiled, int) else args.tiled
+        big = np.tile(rec["image"], (-(-th // h), -(-tw // w), 1))[:th, :tw]        # the first record, repeated to HxW
+        nh, nw = inf.H, inf.W
+        res = tiles.detect_tiled(inf, big, overlap=(nh // 8, nw // 8), det_thresh=0.05)
+        joined = sum(len(m) > 1 for m in res.members)
+        print("tiled: %d tiles of %dx%d on a %dx%d image -> %d instances (%d of them joined over a seam); class map has %d "
+              "labelled pixels" % (len(res.tiles), nh, nw, th, tw, len(res), joined, int((res.merged > 0).sum())))
+        for g in range(min(len(res), 3)):
+            y1, x1, y2, x2 = res.boxes[g]
+            print("  %s %.2f box (%d, %d)-(%d, %d), %d pixels, from tiles %s" % (
+                classes[res.classid[g]], res.score[g], y1, x1, y2, x2, int(res.mask(g).sum()), sorted({t for t, _ in res.members[g]})))
 
 
 if __name__ == "__main__":

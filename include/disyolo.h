@@ -617,6 +617,37 @@ int disyolo_letterbox(const uint8_t* rgb, int image_h, int image_w, float* out, 
  * net_h = net_w call. */
 int disyolo_letterbox_hw(const uint8_t* rgb, int image_h, int image_w, float* out, int net_h, int net_w,
                          float* window_host, void* stream);
+/* ---- tiled detection: an image larger than the net (csrc/tiles.hip, dis-yolo_amd/tiles.py; defined by tests/tiles_ref.py) ----
+ * origins int32 [T, 2] = (y0, x0) of the tiles, row-major (tiles.plan_tiles); a tile is net_h x net_w pixels, net_w % 32 == 0.
+ * Tables the kernels follow indices through are passed twice, like disyolo_paste_job tables: the `_host` copy is what the call
+ * checks before any launch, the device copy (the same bytes, uploaded by the caller on `stream`) is what the kernel reads.
+ *
+ * tile_gather: rgb uint8 [image_h, image_w, 3] (device) -> out f32 [t1 - t0, net_h, net_w, 3] (device), tiles t0 .. t1 - 1 in
+ * one launch: a pixel inside the image is (float)((double)v / 255.0) -- bit for bit disyolo_letterbox at scale 1 --, a pixel
+ * outside it 127 through the same division, and a tile index >= T a whole pad tile (it fills the last batch of an image). */
+int disyolo_tile_gather(const uint8_t* rgb, int image_h, int image_w, const int32_t* origins, int T, int t0, int t1, float* out,
+                        int net_h, int net_w, void* stream);
+/* masks f32 [n, map_h, map_w], rects int32 [n, 8] (disyolo_mask_paste's, the tile as the image) -> planes uint32
+ * [n, net_h, net_w / 32]: bit i of word j of a row = the paste's bit at column 32 j + i.  A crop rect outside the map gives an
+ * empty plane.  n = 0 is allowed. */
+int disyolo_tile_paste_bits(const float* masks, int n, int map_h, int map_w, const int32_t* rects, int net_h, int net_w,
+                            uint32_t* planes, void* stream);
+/* pairs int32 [P, 2] = instance numbers (a, b) < N, inst_tile int32 [N] = each instance's tile < T -> counts int32 [P, 3] =
+ * |A n R|, |B n R|, |A n B|, R = the two tiles' windows n the image.  Integer sums: order-independent. */
+int disyolo_tile_seam_counts(const int32_t* pairs_host, const int32_t* pairs, int P, const int32_t* inst_tile_host,
+                             const int32_t* inst_tile, int N, const int32_t* origins_host, const int32_t* origins, int T,
+                             int image_h, int image_w, const uint32_t* planes, int net_h, int net_w, int32_t* counts,
+                             void* stream);
+/* groups int32 [G, 8] = {m0, m1, y1, x1, y2, x2, block0, off16} in rank order: members[m0 .. m1) int32 are the group's instances,
+ * the box is in image pixels, block0 = the sum of disyolo_tile_compose_blocks(box area) over the groups before it, off16 * 16 the
+ * group's offset in `arena` (room for the area rounded up to 16 bytes).  Writes the OR of the members cropped to the box as bytes
+ * 0 / 1, row-major, and owner int32 [image_h, image_w] = 0 or 1 + the index of the LAST covering group (zeroed here, then
+ * integer atomicMax: disyolo_mask_paste's rule, order-independent). */
+int disyolo_tile_compose_blocks(int64_t area);
+int disyolo_tile_compose(const int32_t* groups_host, const int32_t* groups, int G, const int32_t* members_host,
+                         const int32_t* members, int M, const int32_t* inst_tile_host, const int32_t* inst_tile, int N,
+                         const int32_t* origins_host, const int32_t* origins, int T, const uint32_t* planes, int net_h, int net_w,
+                         int image_h, int image_w, uint8_t* arena, int64_t arena_bytes, int32_t* owner, void* stream);
 /* semantic-segmentation accuracy of evaluate (calculate_test_map.py:303-346): adds the 4x4 pixel
  * confusion counts of two uint8 class maps (0 = background, 1..3 = classes; other values are
  * ignored) to conf int64 [16], conf[true*4 + pred]; the caller zeroes conf before the first image
