@@ -245,7 +245,7 @@ def broadcast_parameters(net, src: int = 0, process_group=None) -> None:
     for t in [net.arena] + [p for n, p in net.params.items() if p.data_ptr() < net.arena.data_ptr()
                             or p.data_ptr() >= net.arena.data_ptr() + net.arena.numel() * 4]:
         dist.broadcast(t, src=src, group=process_group)
-    if not getattr(net, "plan_only", False):
+    if not net.plan_only:
         net.refresh_weights()
 
 
@@ -259,18 +259,18 @@ def enable_data_parallel(net, process_group=None, bucket_mb: float = 12.0, wire:
     ``inlist``: the exchange as commands of the recorded step (RCCL called from the kernel library, no list cuts);
     default: on for a CUDA net over an RCCL ("nccl") process group unless DISYOLO_DP_INLIST=0, off otherwise (gloo
     groups and plan-only CPU nets keep the cut list: torch.distributed issues their collectives)."""
-    if getattr(net, "pair", False):
+    if net.pair:
         # the pair step alternates two single-GPU lists and its eager form has no exchange point
         raise DisyoloError("backbone_pair is a single-GPU option: build the net without it for data parallelism")
     wire = wire or os.environ.get("DISYOLO_DP_WIRE", "f32")
     algo = algo or os.environ.get("DISYOLO_DP_ALGO", "allreduce")
     if inlist is None:
         inlist = (os.environ.get("DISYOLO_DP_INLIST", "1") != "0" and net.device.type == "cuda"
-                  and not getattr(net, "plan_only", False) and dist.get_backend(process_group) == "nccl")
+                  and not net.plan_only and dist.get_backend(process_group) == "nccl")
     # the in-launch batch norm (launches whose blocks wait for each other) is a single-GPU-process feature as shipped: beside RCCL's
     # own persistent kernels, which wait for OTHER ranks, its residency argument has never been exercised on more than one GPU
     # (no multi-GPU box in any round) -- more than one rank runs the separate batch-norm launches
-    if dist.get_world_size(process_group) > 1 and getattr(net, "bn_inkernel", False) and not getattr(net, "plan_only", False):
+    if dist.get_world_size(process_group) > 1 and net.bn_inkernel and not net.plan_only:
         net.bn_inkernel = False
         if any(l.fused_fwd for l in net.layers):
             net._apply_tiles()

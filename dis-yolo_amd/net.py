@@ -41,7 +41,7 @@ class Layer:
                  "act", "stats", "stats_rows", "desc", "grad", "grad_set", "need_grad", "dw", "dbias", "dgamma",
                  "dbeta", "dx", "pad_t", "pad_l", "dgrad_descs", "wgrad_desc", "cout_pad",
                  "act8", "w8", "s_w", "s_out", "escale", "desc8", "dual16", "bn_sums", "bwd_local", "bwd_global", "bwd_part", "bwd_part_rows", "wq",
-                 "csync", "fused_fwd", "csync_bwd", "fused_bwd", "passthru")
+                 "csync", "fused_fwd", "csync_bwd", "fused_bwd", "passthru", "trains", "train_bn", "keeps_raw", "on_path")
 
     def __init__(self, idx, cin, cout, k, stride, kind, src, src_up=None, shortcut=None):
         self.idx, self.cin, self.cout, self.k, self.stride, self.kind = idx, cin, cout, k, stride, kind
@@ -322,7 +322,7 @@ class YOLONet(object):
             self.lock[int(i)] = bool(v)
         self.layers = build_topology(self.num_class, self.k, self.mask_stride)
         self.by_idx = {l.idx: l for l in self.layers}
-        self._mark_pass_through()
+        self._needs_grad_into = self._mark_pass_through(self.layers, self.lock, self.training)
         if self.dtype == "fp8":
             self._check_fp8_lock()
         self._lr = float(cfg.LEARNING_RATE)
@@ -333,6 +333,10 @@ class YOLONet(object):
         self._prog = None       # recorded command list of one training step
         self._prog_marks = []   # [(command index, layer)] all-reduce trigger points
         self._graph = None      # hipGraph of the recorded step (single GPU)
+        self._infer_prog = self._infer_thresh = self._infer_graph = None     # recorded inference (build_infer_program)
+        self._fp8_entry = None  # the bf16 layer in front of the first fp8 layer (_plan_fp8)
+        self._mask_loss_pending = False     # compute_losses left dscore on the side lane: backward() waits for _mask_mark
+        self._mask_mark = -1
         self.opt_chunks = None      # slices of the arena the optimizer sweeps one by one (_plan_opt_chunks)
         # build_program(overlap_tail=True): the recorded step does not join its side lane at the end -- the optimizer's last
         # sweeps and the last weight gradients keep running while the NEXT replay's locked-backbone forward starts; the
@@ -465,20 +469,30 @@ class YOLONet(object):
     def trainable_names(self) -> List[str]:
         return list(self.arena_slices)
 
-    def _mark_pass_through(self) -> None:
-        """``needs_grad_into[i]``: a trainable layer sits at or upstream of layer i's output (0 = the image).  A LOCKED layer
+    @staticmethod
+    def _mark_pass_through(layers: List[Layer], lock: Dict[int, bool], training: bool) -> Dict[int, bool]:
+        """returns ``needs_grad_into[i]``: a trainable layer sits at or upstream of layer i's output (0 = the image).  A LOCKED layer
         of a training net with such an input is "pass-through": it trains nothing, but the loss gradient crosses it on its
         way to the trainable layers upstream (TF autodiff does that unasked).  It runs like a trainable layer in inference
         mode -- conv -> raw, bn_act_fwd with the folded moving statistics -- and keeps raw, dx and its flipped weights for
-        the backward pass (bn_frozen_bwd + the ordinary data-gradient convs)."""
+        the backward pass (bn_frozen_bwd + the ordinary data-gradient convs).
+
+        The other roles of a layer in its net are fixed here too (all False in an inference net): ``trains``; ``train_bn``
+        (... with batch norm); ``on_path`` (the loss gradient crosses it: it trains or is pass-through); ``keeps_raw`` (...
+        and is batch-normalised: its conv output is kept for the backward pass).  A function of the layer table, the lock
+        map and ``training`` alone."""
         up_to = {0: False}
-        for l in self.layers:
-            l.lock = self.lock[l.idx]
+        for l in layers:
+            l.lock = lock[l.idx]
             ins = [i for i in (l.src, l.src_up, l.shortcut) if i is not None]
             into = any(up_to[i] for i in ins)
-            l.passthru = bool(self.training and l.lock and into)
+            l.passthru = bool(training and l.lock and into)
+            l.trains = training and not l.lock
+            l.train_bn = l.trains and l.kind != "lin"
+            l.on_path = l.trains or l.passthru
+            l.keeps_raw = l.on_path and l.kind != "lin"
             up_to[l.idx] = into or (not l.lock)
-        self._needs_grad_into = up_to
+        return up_to
 
     def pass_through_layers(self) -> List[int]:
         """locked layers the backward pass crosses (empty for the reference's two stages)"""
@@ -537,8 +551,6 @@ class YOLONet(object):
         self.B = B
         self.images = torch.zeros(2 * B if self.pair else B, H, W, 3, dtype=F32, device=dev)
         self._plan_sizes(H, W)
-        # which activations need a gradient: any trainable layer at or upstream of a consumer
-        has_trainable_upto = self._needs_grad_into       # (_mark_pass_through)
         # activation tensors are views into ONE allocation: a process that has allocated and freed a lot of
         # device memory gets later allocations on worse-mapped memory (B = 32 inference 4.8 -> 3.9 k img/s after
         # 13 GB of tensors were created and freed, no compute involved: tools/micro/infer_after_alloc.py), and
@@ -547,8 +559,7 @@ class YOLONet(object):
         batch_of = lambda l: 2 * B if (self.pair and l.idx <= self._pair_P) else B
         for l in self.layers:
             n = batch_of(l) * l.Ho * l.Wo * l.cout
-            tb = self.training and (not l.lock or l.passthru) and l.kind != "lin"      # (keeps its conv output: l.raw)
-            need += ((n * (4 if l.kind == "lin" else 2) + 255) // 256) * 256 * (2 if tb else 1)
+            need += ((n * (4 if l.kind == "lin" else 2) + 255) // 256) * 256 * (2 if l.keeps_raw else 1)      # (act, l.raw)
         self._act_arena = torch.zeros(need, dtype=torch.uint8, device=dev)
         cursor = [0]
 
@@ -559,20 +570,18 @@ class YOLONet(object):
             return t
 
         for l in self.layers:
-            M = B * l.Ho * l.Wo
-            train_bn = self.training and (not l.lock) and l.kind != "lin"
             if l.kind == "lin":
                 l.act = zeros4(B, l.Ho, l.Wo, l.cout, F32)
             else:
                 l.act = zeros4(batch_of(l), l.Ho, l.Wo, l.cout, BF16)
-                l.raw = zeros4(B, l.Ho, l.Wo, l.cout, BF16) if (train_bn or l.passthru) else None
+                l.raw = zeros4(B, l.Ho, l.Wo, l.cout, BF16) if l.keeps_raw else None
             if l.idx > 1:
                 K = l.k * l.k * l.cin
                 l.wp = torch.zeros(l.cout, K, dtype=BF16, device=dev)
             # (a batch-normalised layer of 16 * odd channels -- m = 1's conv82 / conv83 -- keeps its own width: its gradient is
             # the 16-channel source of its data-gradient conv, which the conv takes as it is)
             l.cout_pad = l.cout if (l.cout % 32 == 0 or (l.kind != "lin" and l.cout % 16 == 0)) else ((l.cout + 31) // 32) * 32
-            if self.training and (not l.lock or l.passthru or l.kind == "lin"):
+            if l.on_path or (self.training and l.kind == "lin"):
                 # gradient wrt this layer's conv output (bf16, row pitch cout_pad: GRAD_LD for the heads and for conv82 up to
                 # k_map = 5, 64 for the 49 score maps of k_map = 7).  The four linear layers own it locked or not: the loss
                 # kernels write it
@@ -580,17 +589,17 @@ class YOLONet(object):
                     l.dx = torch.zeros(B, l.Ho, l.Wo, l.cout_pad, dtype=BF16, device=dev)
                 else:
                     l.dx = torch.zeros(B, l.Ho, l.Wo, l.cout, dtype=BF16, device=dev)
-            if self.training and has_trainable_upto[l.idx] and l.kind != "lin":
+            if l.on_path and l.kind != "lin":      # (a trainable layer at or upstream of it: the gradient wrt its output)
                 l.grad = torch.zeros(B, l.Ho, l.Wo, l.cout, dtype=BF16, device=dev)
-            needs_dgrad = self.training and (not l.lock or l.passthru) and l.idx > 1 and (
-                has_trainable_upto[l.src] or (l.src_up is not None and has_trainable_upto[l.src_up]))
-            if needs_dgrad:
+            # (its data gradient is needed: a trainable layer at or upstream of one of its sources, _mark_pass_through)
+            if l.on_path and l.idx > 1 and (self._needs_grad_into[l.src]
+                                            or (l.src_up is not None and self._needs_grad_into[l.src_up])):
                 l.wdg = torch.zeros(l.cin, l.k * l.k * l.cout_pad, dtype=BF16, device=dev)
         self._build_descs()
         if self.dtype == "fp8":
             self._plan_fp8()
         l1 = self.by_idx[1]
-        if self.training and not l1.lock:
+        if l1.trains:
             l1.stats_rows = L.colstats_rows(B * H * W, l1.cout)
             l1.stats = torch.zeros(l1.stats_rows, l1.cout, 2, dtype=F32, device=dev)
             self._ones32 = torch.ones(l1.cout, dtype=F32, device=dev)
@@ -633,9 +642,9 @@ class YOLONet(object):
             for l in self.layers:
                 if l.wgrad_desc is not None:
                     need = max(need, L.conv2d_wgrad_workspace(l.wgrad_desc))
-                if l.dx is not None and l.kind != "lin" and not l.lock:
+                if l.train_bn:
                     need = max(need, L.load().disyolo_bn_act_bwd_workspace(B * l.Ho * l.Wo, l.cout))
-            if not l1.lock:
+            if l1.trains:
                 need = max(need, L.load().disyolo_conv_first_wgrad_workspace(B, H, W, l1.cout))
             if self.mask_roi_rows > L.ROI_MAX:      # the wide mask loss: one partial per (block, table row)
                 need = max(need, L.psroi_loss_workspace_x(B, self.mask_map_size(), self.mask_roi_rows))
@@ -737,44 +746,41 @@ class YOLONet(object):
             x0 = self._input_of(l, l.src)
             x1 = self._input_of(l, l.src_up) if l.src_up is not None else None
             res = self._input_of(l, l.shortcut) if l.shortcut is not None else None
-            train_bn = self.training and (not l.lock) and l.kind != "lin"
+            # the layer's own conv: source(s), packed weights, kernel size and stride are common to every form of it
+            desc = lambda out, **kw: L.make_conv_desc(x0, l.wp, out, l.k, l.stride, x1=x1, **kw)
             if l.kind == "lin":
-                l.desc = L.make_conv_desc(x0, l.wp, l.act, l.k, l.stride, x1=x1, shift=l.bias, out_f32=True)
-            elif train_bn:
+                l.desc = desc(l.act, shift=l.bias, out_f32=True)
+            elif l.train_bn:
                 if l.stats is None:
-                    d0 = L.make_conv_desc(x0, l.wp, l.raw, l.k, l.stride, x1=x1)
-                    l.stats_rows = L.conv2d_stats_rows(d0)
+                    l.stats_rows = L.conv2d_stats_rows(desc(l.raw))
                     l.stats = torch.zeros(l.stats_rows, l.cout, 2, dtype=F32, device=dev)
-                l.desc = L.make_conv_desc(x0, l.wp, l.raw, l.k, l.stride, x1=x1, stats=l.stats)
+                l.desc = desc(l.raw, stats=l.stats)
                 l.fused_fwd = False
                 if (self.bn_inkernel and not self.sync_bn and res is None and l.idx not in self.HEAD_LAYERS
-                        and not getattr(self, "plan_only", False) and l.stride == 1):
+                        and not self.plan_only and l.stride == 1):
                     # the tile: the table's if its grid can run the in-launch exchange (one block per CU, all resident),
                     # else the covering tile with the largest such grid (the statistics buffer follows the tile's rows)
-                    tile = self._fused_tile(lambda t: L.make_conv_desc(x0, l.wp, l.raw, l.k, l.stride, x1=x1, tile=t), l.k)
+                    tile = self._fused_tile(lambda t: desc(l.raw, tile=t), l.k)
                     if tile is not None:
-                        d0 = L.make_conv_desc(x0, l.wp, l.raw, l.k, l.stride, x1=x1, tile=tile)
-                        rows = L.conv2d_stats_rows(d0)
+                        rows = L.conv2d_stats_rows(desc(l.raw, tile=tile))
                         l.stats_rows = rows
                         if l.stats.shape[0] < rows:      # (never shrunk: autotune() sizes it for every candidate's rows)
                             l.stats = torch.zeros(rows, l.cout, 2, dtype=F32, device=dev)
                         if l.csync is None:
                             l.csync = L.cluster_sync_buffer(l.cout, dev)
-                        l.desc = L.make_conv_desc(x0, l.wp, l.raw, l.k, l.stride, x1=x1, stats=l.stats, tile=tile,
-                                                  bn_fused=dict(y_act=l.act, gamma=l.gamma, beta=l.beta, mm=l.mm, mv=l.mv,
-                                                                scale=l.scale, shift=l.shift, mean=l.mean, rstd=l.rstd,
-                                                                decay=cfg.BN_DECAY, eps=cfg.BN_EPSILON, sync=l.csync),
-                                                  alpha=cfg.ALPHA)
+                        l.desc = desc(l.raw, stats=l.stats, tile=tile,
+                                      bn_fused=dict(y_act=l.act, gamma=l.gamma, beta=l.beta, mm=l.mm, mv=l.mv,
+                                                    scale=l.scale, shift=l.shift, mean=l.mean, rstd=l.rstd,
+                                                    decay=cfg.BN_DECAY, eps=cfg.BN_EPSILON, sync=l.csync), alpha=cfg.ALPHA)
                         l.fused_fwd = True
             elif l.passthru:
                 # a locked layer the backward pass crosses: the conv output is kept (l.raw), the folded moving statistics and
                 # the activation follow in bn_act_fwd -- never part of a fused launch, no statistics, no moving-average update
-                l.desc = L.make_conv_desc(x0, l.wp, l.raw, l.k, l.stride, x1=x1)
+                l.desc = desc(l.raw)
             else:
-                l.desc = L.make_conv_desc(x0, l.wp, l.act, l.k, l.stride, x1=x1, scale=l.scale, shift=l.shift,
-                                          residual=res, leaky=True, alpha=cfg.ALPHA)
-            if self.training and not l.lock:
-                l.wgrad_desc = L.make_conv_desc(x0, l.wp, l.act, l.k, l.stride, x1=x1)
+                l.desc = desc(l.act, scale=l.scale, shift=l.shift, residual=res, leaky=True, alpha=cfg.ALPHA)
+            if l.trains:
+                l.wgrad_desc = desc(l.act)
 
     # tiles tried for a launch that runs batch norm in its epilogue when the table's own cannot (its grid must be one block
     # per CU at most): GEMM tiles 64x128, 128x64, 64x64, 96x128, 128x128, 192x128; for 3x3 layers the patch kernels first
@@ -921,7 +927,7 @@ class YOLONet(object):
                 # the shallow stride-2 layers (conv2, conv5): data gradient as one 2x2-tap conv over dy (lib.dgrad_s2_quad)
                 if (l.k == 3 and l.stride == 2 and l.H % 2 == 0 and l.W % 2 == 0 and l.pad_t == 0 and l.pad_l == 0
                         and L.dgrad_s2_quad_ok(self.B, l.Ho, l.Wo, l.cout, l.cin)):
-                    if getattr(l, "wq", None) is None:
+                    if l.wq is None:
                         l.wq = torch.zeros(4 * l.cin, 9 * l.cout, dtype=BF16, device=self.device)
                     kw["quad"] = l
                 l.dgrad_descs.append(("direct", tgt, kw))
@@ -998,7 +1004,7 @@ class YOLONet(object):
         _forward_layer does for the layer-by-layer path)"""
         for i in idxs:
             l = self.by_idx[i]
-            if self.training and not l.lock and l.kind != "lin":
+            if l.train_bn:
                 L.bn_fold(l.gamma, l.beta, l.mm, l.mv, cfg.BN_EPSILON, l.scale, l.shift)
 
     SLOT_ALL = 15
@@ -1022,9 +1028,9 @@ class YOLONet(object):
                     self._xstep_reader[src] = l.idx
         if slot >= self.SLOT_ALL:
             raise L.DisyoloError("overlap_tail: too many backbone outputs feed trainable layers")
-        order = [x.idx for x in self.backward_order() if not x.lock]
+        order = [x.idx for x in self.backward_order() if x.trains]
         for src in self._xstep_slot:
-            readers = [x.idx for x in self.layers if x.idx > P and not x.lock and src in (x.src, x.src_up, x.shortcut)]
+            readers = [x.idx for x in self.layers if x.idx > P and x.trains and src in (x.src, x.src_up, x.shortcut)]
             self._xstep_reader[src] = max(readers, key=order.index)
         # where the next replay's main lane waits.  A wait that is enqueued before its event has completed costs the waiting
         # stream ~3 us whether or not it ever blocks (tools/micro/event_cost.hip), so the waits are merged: the side lane is
@@ -1081,16 +1087,14 @@ class YOLONet(object):
     def _fp8_handover(self, l) -> None:
         """the bf16 layer in front of the first fp8 layer: its output once more as e4m3 (what conv FP8_FROM reads)"""
         if self.dtype == "fp8" and self.fp8_ready:
-            q = getattr(self, "_fp8_entry", None)
+            q = self._fp8_entry
             if q is not None and l.idx == q.idx:
                 L.quant_fp8(q.act, q.act8, q.s_out)
 
     def _inference_mode(self, idxs, is_training: bool) -> bool:
         """every one of these layers normalises with its folded moving statistics in this pass and need not keep its conv
         output (a pass-through layer does in a training pass: it stays out of every fused launch)"""
-        train = is_training and self.training
-        return all(not (train and self.by_idx[i].passthru) and (self.by_idx[i].kind == "lin" or not (train and not self.by_idx[i].lock))
-                   for i in idxs)
+        return not (is_training and any(self.by_idx[i].keeps_raw or self.by_idx[i].passthru for i in idxs))
 
     def _fusion_plan(self, is_training: bool, first: int, last: int):
         """layer index -> fused launch that replaces the layer (None: covered by a later entry).  Groups of layers whose
@@ -1117,7 +1121,7 @@ class YOLONet(object):
         plan = {}
         if first <= 1 and last >= 2 and self._can_fuse_first_two(is_training):
             plan[1], plan[2] = None, self._forward_first_two
-        if self.fuse_blocks and not getattr(self, "plan_only", False):
+        if self.fuse_blocks and not self.plan_only:
             l2, l4 = self.by_idx[2], self.by_idx[4]
             if (first <= 3 and last >= 4 and self._inference_mode((3, 4), is_training)
                     and L.block32_fused_ok(self.B, l4.Ho, l4.Wo, l2.cout, 0, 0)):
@@ -1145,12 +1149,11 @@ class YOLONet(object):
         return L.conv12_fused_ok(self.B, self.H, self.W)
 
     def _forward_layer(self, l, is_training: bool) -> None:
-        B = self.B
         if self.dtype == "fp8" and self.fp8_ready and l.act8 is not None and l.idx >= self.FP8_FROM:
             self._forward_layer_fp8(l)
             return
-        train_bn = is_training and self.training and (not l.lock) and l.kind != "lin"
-        M = B * l.Ho * l.Wo
+        train_bn = is_training and l.train_bn
+        M = self.B * l.Ho * l.Wo
         res = self._input_of(l, l.shortcut) if l.shortcut is not None else None
         if l.idx == 1:
             if train_bn:
@@ -1159,7 +1162,7 @@ class YOLONet(object):
                 self._bn_finalize(l, M)
                 L.bn_act_fwd(l.raw, l.scale, l.shift, None, l.act, M, l.cout, cfg.ALPHA)
             else:
-                if not l.lock and self.training:
+                if l.trains:
                     L.bn_fold(l.gamma, l.beta, l.mm, l.mv, cfg.BN_EPSILON, l.scale, l.shift)
                 L.conv_first_fwd(self.images, l.w, l.scale, l.shift, l.act, alpha=cfg.ALPHA)
             return
@@ -1175,9 +1178,9 @@ class YOLONet(object):
             self._bn_finalize(l, M)
             L.bn_act_fwd(l.raw, l.scale, l.shift, res, l.act, M, l.cout, cfg.ALPHA)
         else:
-            if self.training and (not l.lock or l.passthru):
+            if l.on_path:
                 # a training-mode plan evaluated with is_training=False: moving statistics
-                if not l.lock:
+                if l.trains:
                     L.bn_fold(l.gamma, l.beta, l.mm, l.mv, cfg.BN_EPSILON, l.scale, l.shift)
                 d = L.make_conv_desc(self._input_of(l, l.src), l.wp, l.act, l.k, l.stride,
                                      x1=self._input_of(l, l.src_up) if l.src_up is not None else None,
@@ -1220,14 +1223,14 @@ class YOLONet(object):
         if self._prog is not None:
             raise L.DisyoloError("enable SyncBN before build_program()")
         for l in self.layers:
-            if self.training and not l.lock and l.kind != "lin":
-                l.bn_sums = torch.zeros(l.cout, 2, dtype=torch.float64, device=self.device)
+            if l.train_bn:
+                l.bn_sums =torch.zeros(l.cout, 2, dtype=torch.float64, device=self.device)
                 l.bwd_local = torch.zeros(l.cout, 2, dtype=torch.float64, device=self.device)
                 l.bwd_global = torch.zeros(l.cout, 2, dtype=torch.float64, device=self.device)
         self.sync_bn = True
         # the statistics now cross the ranks between the conv and the normalisation: the in-launch batch norm (whose
         # exchange stays inside one launch) is off -- rebuild the descriptors that carry it
-        if not getattr(self, "plan_only", False) and any(l.fused_fwd for l in self.layers):
+        if not self.plan_only and any(l.fused_fwd for l in self.layers):
             self._apply_tiles()
 
     def mask_map_size(self) -> Tuple[int, int]:
@@ -1303,8 +1306,7 @@ class YOLONet(object):
         """the device half of ``evaluation``: network + detection filter + mask assembly on a batch; returns the fixed-shape
         outputs where they are, (detections [B,30,6], keep [B,30], masks [B,30,Hm,Wm]) -- what MAP.collect_batch takes"""
         thr = float(np.asarray(det_thresh).reshape(-1)[0])
-        if (not self.training and getattr(self, "_infer_prog", None) is not None and getattr(self, "_infer_thresh", None) == thr
-                and not self.pair):
+        if not self.training and self._infer_prog is not None and self._infer_thresh == thr and not self.pair:
             # an inference net whose forward + filter + assembly were recorded for this threshold (build_infer_program):
             # one replay instead of ~90 launches from Python -- the same kernels on the same buffers
             self.infer(images, clip_window)
@@ -1493,8 +1495,15 @@ class YOLONet(object):
                         [h.dx for h in heads], self.losses, self.ws)
         self._mask_loss_pending = side
 
-    def _accumulate_into(self, tgt: Layer, desc_kw: dict, dx: torch.Tensor, cin_eff: int, k: int, in_div: int,
-                         final: bool = False) -> None:
+    def _bn_bwd_part(self, tgt: Layer, d) -> tuple:
+        """size tgt.bwd_part for the partial-sum rows of descriptor ``d``; returns (rows, the conv's ``bn_bwd`` operands)"""
+        rows = L.conv2d_stats_rows(d)
+        need = rows * tgt.cout * 2
+        if tgt.bwd_part is None or tgt.bwd_part.numel() < need:
+            tgt.bwd_part = torch.empty(need, dtype=torch.float32, device=self.device)
+        return rows, (tgt.raw, tgt.scale, tgt.shift, tgt.mean, tgt.rstd, tgt.bwd_part, cfg.ALPHA)
+
+    def _accumulate_into(self, tgt: Layer, desc_kw: dict, dx: torch.Tensor, k: int, in_div: int, final: bool = False) -> None:
         """one data-gradient conv writing (first contribution) or accumulating into tgt.grad.  ``final``: this is
         the last contribution to tgt.grad and tgt is batch-normalised -- if the conv runs the 3x3 patch kernel, its
         epilogue also emits tgt's batch-norm backward sums (bn_act_bwd then skips its column reduction)"""
@@ -1506,38 +1515,26 @@ class YOLONet(object):
             L.dgrad_s2_quad(dx, ql.wq, tgt.grad, accumulate=not first)
             return
         res = None if (first or "tmp" in desc_kw) else tgt.grad
-        d = L.make_conv_desc(dx, desc_kw["w"], out, k, 1, in_div=in_div, pads=desc_kw["pads"], out_hw=desc_kw["out_hw"],
-                             residual=res)
+        # the conv over dx with the flipped operand: only the output, the tile and the batch-norm riders vary
+        desc = lambda y=out, **kw: L.make_conv_desc(dx, desc_kw["w"], y, k, 1, in_div=in_div, pads=desc_kw["pads"],
+                                                    out_hw=desc_kw["out_hw"], residual=res, **kw)
+        d = desc()
         whole, tile_f = False, None
         if (final and L.TUNER is None and self.bn_inkernel and self.bn_inkernel_bwd and not self.sync_bn
                 and self.bn_fuse_check is None and not self._shortcut_feeds_grad(tgt) and in_div == 1):
-            tile_f = self._fused_tile(lambda t: L.make_conv_desc(dx, desc_kw["w"], out, k, 1, in_div=in_div, pads=desc_kw["pads"],
-                                                                 out_hw=desc_kw["out_hw"], residual=res, tile=t), k, bwd=True)
+            tile_f = self._fused_tile(lambda t: desc(tile=t), k, bwd=True)
             whole = tile_f is not None
         if final and L.TUNER is None and not whole and L.conv2d_bn_bwd_stats_ok(d):     # (the tuner swaps tiles under the descriptor)
-            rows = L.conv2d_stats_rows(d)
-            need = rows * tgt.cout * 2
-            if tgt.bwd_part is None or tgt.bwd_part.numel() < need:
-                tgt.bwd_part = torch.empty(need, dtype=torch.float32, device=self.device)
-            tgt.bwd_part_rows = rows
-            d = L.make_conv_desc(dx, desc_kw["w"], out, k, 1, in_div=in_div, pads=desc_kw["pads"], out_hw=desc_kw["out_hw"],
-                                 residual=res,
-                                 bn_bwd=(tgt.raw, tgt.scale, tgt.shift, tgt.mean, tgt.rstd, tgt.bwd_part, cfg.ALPHA))
+            tgt.bwd_part_rows, bn_bwd = self._bn_bwd_part(tgt, d)
+            d = desc(bn_bwd=bn_bwd)
         elif whole:
             # the target's WHOLE batch-norm backward inside this conv (DISYOLO_CONV_BN_BWD_FUSED): the sums are exchanged
             # within the launch and the conv writes tgt.dx; backward() then skips tgt's three batch-norm launches
-            d = L.make_conv_desc(dx, desc_kw["w"], out, k, 1, in_div=in_div, pads=desc_kw["pads"], out_hw=desc_kw["out_hw"],
-                                 residual=res, tile=tile_f)
-            rows = L.conv2d_stats_rows(d)
-            need = rows * tgt.cout * 2
-            if tgt.bwd_part is None or tgt.bwd_part.numel() < need:
-                tgt.bwd_part = torch.empty(need, dtype=torch.float32, device=self.device)
+            _, bn_bwd = self._bn_bwd_part(tgt, desc(tile=tile_f))
             if tgt.csync_bwd is None:
                 tgt.csync_bwd = L.cluster_sync_buffer(tgt.cout, self.device)
-            d = L.make_conv_desc(dx, desc_kw["w"], tgt.dx, k, 1, in_div=in_div, pads=desc_kw["pads"], out_hw=desc_kw["out_hw"],
-                                 residual=res, tile=tile_f,
-                                 bn_bwd=(tgt.raw, tgt.scale, tgt.shift, tgt.mean, tgt.rstd, tgt.bwd_part, cfg.ALPHA),
-                                 bn_bwd_fused=dict(dgamma=tgt.dgamma, dbeta=tgt.dbeta, sync=tgt.csync_bwd))
+            d = desc(tgt.dx, tile=tile_f, bn_bwd=bn_bwd,
+                     bn_bwd_fused=dict(dgamma=tgt.dgamma, dbeta=tgt.dbeta, sync=tgt.csync_bwd))
             tgt.fused_bwd = True
         L.conv2d_fwd(d)
 
@@ -1563,7 +1560,7 @@ class YOLONet(object):
         data-gradient conv straight into it, "up" = through the 2x upsampling, "add" = a shortcut's add)"""
         last: Dict[int, Tuple[int, str]] = {}
         for l in visit:
-            if l.lock and not l.passthru:
+            if not l.on_path:
                 continue
             if l.kind != "lin" and l.shortcut is not None and self.by_idx[l.shortcut].grad is not None:
                 last[l.shortcut] = (l.idx, "add")
@@ -1578,202 +1575,205 @@ class YOLONet(object):
         return heads + [l for l in reversed(self.layers) if l.idx not in self.HEAD_LAYERS]
 
     def backward(self, on_layer_done=None, sweep: bool = False) -> None:
-        """TF autodiff of total_loss restated layer by layer in reverse order.  Gradients of
-        the trainable variables land in ``grad_arena``.  ``on_layer_done(layer)`` is called
-        after a layer's parameter gradients are enqueued (used to overlap the RCCL
-        all-reduce with the rest of the backward pass).  ``sweep`` (train_step, recorded steps): the
-        optimizer update of an arena slice is issued as soon as the slice's gradients are final
-        (optimizer_step() then only sweeps what is left and finishes the step)."""
-        B = self.B
-        for l in self.layers:
-            l.grad_set = False
-        # any topological order of the reversed graph is valid.  The three detection heads
-        # (75,74 / 67,66 / 59,58) depend on the YOLO loss only, so they go first while the side
-        # lane still runs the detection filter and the mask loss; the mask subnet follows.
+        """TF autodiff of total_loss restated layer by layer in reverse order.  Gradients of the trainable variables land in
+        ``grad_arena``.  ``on_layer_done(layer)`` is called after a layer's parameter gradients are enqueued (used to overlap
+        the RCCL all-reduce with the rest of the backward pass).  ``sweep`` (train_step, recorded steps): the optimizer update
+        of an arena slice is issued as soon as the slice's gradients are final (optimizer_step() then only sweeps what is left
+        and finishes the step)."""
+        # any topological order of the reversed graph is valid.  The three detection heads (75,74 / 67,66 / 59,58) depend on the
+        # YOLO loss only, so they go first while the side lane still runs the detection filter and the mask loss
         visit = self.backward_order()
-        order = [l for l in visit if not l.lock]
+        order = [l for l in visit if l.trains]
+        pos_of = {l.idx: i for i, l in enumerate(order)}
         final_of = {} if self.sync_bn else self._final_writers(visit)
         for l in self.layers:
-            l.bwd_part_rows = 0
-            l.fused_bwd = False
+            l.grad_set, l.bwd_part_rows, l.fused_bwd = False, 0, False
         # (data parallelism with a cut list: the sweep must follow the bucket's all-reduce -- it stays in optimizer_step;
         # with the exchange in the list the slice's all-reduce and its sweep go to the exchange lane together)
         inl = self.dp is not None and self.dp.inlist
-        overlap_opt = sweep and (self.dp is None or inl) and self.n_params > 0
-        if overlap_opt:
+        sweep = sweep and (self.dp is None or inl) and self.n_params > 0
+        if sweep:
             if self.opt_chunks is None:
                 self._plan_opt_chunks()
             self._opt_swept = set()
             self._opt_done = [set() for _ in self.opt_chunks]
-        pending: list = []            # (layer, dx, ld, M, side) whose weight gradients wait for the group's edge
-
-        def flush():
-            if not pending:
-                return
-            side_g = pending[0][4]
-            mark = L.lane_mark(0) if side_g else None         # ONE record on the main lane for the whole group
-            waited = False
-            for (pl, pdx, pld, pM, pside) in pending:
-                if pside:
-                    if not waited:
-                        L.lane_wait(mark, 1)
-                        waited = True
-                    L.set_lane(1)
-                # scratch of the lane the gradient runs on: the side lane's weight gradients own ws_aux; one kept on the main lane
-                # (tail_on_main) must not share it -- the side lane may still be inside an earlier layer's slabs (found in round 6:
-                # with tail_on_main > 0 the loss differed from run to run)
-                wsl = self.ws_aux if pside else self.ws
-                if pl.kind == "lin":
-                    L.colsum(pl.dx, pl.dbias, pM, pl.cout_pad, pl.cout, wsl)   # bias gradient
-                if pl.idx == 1:
-                    # the first layer's own kernel: taps as the M axis of the MFMA, the f32 image rounded to bf16 on
-                    # its way into LDS (csrc/conv_wgrad.hip, conv_first_wgrad_mfma_kernel)
-                    L.conv_first_wgrad(self.images, pl.dx, pl.dw, wsl)
-                else:
-                    L.conv2d_wgrad(pl.wgrad_desc, pdx, pld, pl.dw, wsl)
-                if pside:
-                    L.set_lane(0)
-                if self._overlap_rec:
-                    for src, reader in self._xstep_reader.items():
-                        if reader == pl.idx and self._xstep_slot[src] in self._xstep_waits.values():     # (only slots somebody waits on)
-                            L.lane_mark_slot(1 if pside else 0, self._xstep_slot[src])
-                if overlap_opt and pside:
-                    # the optimizer sweep of an arena slice (+ the re-pack of its layers) as soon as the slice's weight
-                    # gradients are final, on the side lane behind them -- not at the end of the critical chain.  It rewrites
-                    # the bf16 operands the data-gradient convs of these layers read: they are all behind the group's edge,
-                    # which the side lane has waited for
-                    ci = self._opt_chunk_of[pl.idx]
-                    self._opt_done[ci].add(pl.idx)
-                    if self._opt_done[ci] == self.opt_chunks[ci]["members"]:
-                        if inl:
-                            # data parallel: the slice's gradients are summed over the ranks first -- the collective goes to
-                            # the exchange lane (behind the side lane's weight gradients of the slice; the side lane itself
-                            # goes on with the next layers' weight gradients) ...
-                            L.lane_wait(L.lane_mark(1), L.COMM_LANE)
-                            L.set_lane(L.COMM_LANE)
-                            ch = self.opt_chunks[ci]
-                            self.dp.exchange_inlist(ci, ch["off"], ch["cnt"])
-                            # ... and the sweep right behind it on the exchange lane (lowest stream priority, like the side
-                            # lane the single-GPU step sweeps on): the side lane never waits for the links; its mark sits
-                            # behind the group's main-lane edge, so the re-pack is safe.  (A hop between lanes costs ~15 us,
-                            # profiles/r05_hw_queues.txt, and the side lane is nearly as busy as the main one.  One RCCL rank,
-                            # same box, ms per step: plain 4.16-4.18 | this 4.17-4.18 | exchange lane at normal priority 4.22 |
-                            # the sweep back on the side lane two layers later 4.20)
-                            self._sweep_chunk(ci, 1.0 / self.dp.world_size)
-                            L.set_lane(0)
-                        else:
-                            L.set_lane(1)
-                            self._sweep_chunk(ci, 1.0)
-                            L.set_lane(0)
-                if on_layer_done is not None:
-                    on_layer_done(pl)
-            pending.clear()
-
+        # the weight gradient is off the critical chain (dx -> dgrad -> next layer's BN backward): in a recorded step it runs
+        # on the side lane, overlapping the small latency-bound BN kernels of the following layers -- except for the last
+        # few layers of the pass: nothing is left on the main lane to overlap with, the step would only wait for the side
+        # lane's backlog to drain.  (Data parallelism with a CUT list: every weight gradient stays on the side lane -- the
+        # bucket all-reduce is ordered after that lane only.  With the exchange in the list the slices whose last weight
+        # gradient ran on the main lane are exchanged and swept in optimizer_step, whose exchange lane waits for the main
+        # lane, which has joined the side lane)
+        tail = self.tail_on_main if (self.dp is None or inl) else 0
+        pending: list = []            # (layer, dx, ld, side) whose weight gradients wait for the group's edge
         for l in visit:
-            pos = order.index(l) if not l.lock else -1
-            if l.idx == self.score_layer and getattr(self, "_mask_loss_pending", False):
+            if l.idx == self.score_layer and self._mask_loss_pending:
                 L.lane_wait(self._mask_mark, 0)          # dscore comes from the side lane
                 self._mask_loss_pending = False
-            if l.lock and not l.passthru:
+            if not l.on_path:
                 continue                  # nothing upstream trains: no gradient crosses this layer
-            M = B * l.Ho * l.Wo
-            if l.kind == "lin":
-                dx, ld = l.dx, l.cout_pad
-            elif l.lock:
-                # a locked layer on the gradient's way (yolo/yolo3_net_pos.py:76-81: moving statistics, nothing to train):
-                # d conv = g * leaky'(z) * scale with the raw / scale / shift its forward used; the shortcut's source gets g
-                if not l.grad_set:
-                    raise L.DisyoloError("layer %d received no gradient" % l.idx)
-                sc = self.by_idx[l.shortcut] if l.shortcut is not None else None
-                if sc is not None and sc.grad is None:
-                    sc = None
-                kw = dict(shortcut_grad=sc.grad, shortcut_accumulate=sc.grad_set) if sc is not None else {}
-                L.bn_frozen_bwd(l.grad, l.raw, l.scale, l.shift, l.dx, M, l.cout, cfg.ALPHA, **kw)
-                dx, ld = l.dx, l.cout
-                if sc is not None:
-                    sc.grad_set = True
-            else:
-                if not l.grad_set:
-                    raise L.DisyoloError("layer %d received no gradient" % l.idx)
-                # a residual layer hands its output gradient on to the shortcut's source (res_conv_bn, :148-151): that
-                # copy / add rides on the batch-norm backward's apply pass, which reads l.grad anyway
-                sc = self.by_idx[l.shortcut] if l.shortcut is not None else None
-                if sc is not None and sc.grad is None:
-                    sc = None
-                kw = dict(shortcut_grad=sc.grad, shortcut_accumulate=sc.grad_set) if sc is not None else {}
-                if l.fused_bwd:
-                    pass        # l.dx, l.dgamma, l.dbeta came out of the data-gradient conv that made l.grad final (_accumulate_into)
-                elif self.sync_bn:
-                    # (sum g, sum g*xhat) of this rank -> the same over all ranks -> dx; dgamma / dbeta stay local
-                    L.bn_bwd_reduce(l.grad, l.raw, l.scale, l.shift, l.mean, l.rstd, M, l.cout, l.bwd_local, self.ws, cfg.ALPHA)
-                    L.copy2d_f32(l.bwd_local.view(torch.float32), l.bwd_global.view(torch.float32), 1, 4 * l.cout,
-                                 4 * l.cout, 4 * l.cout)
-                    self._sync_sums(l.bwd_global)
-                    L.bn_bwd_apply_sums(l.grad, l.raw, l.scale, l.shift, l.mean, l.rstd, l.bwd_local, l.bwd_global,
-                                        M * self.dp.world_size, l.dx, l.dgamma, l.dbeta, M, l.cout, self.ws, cfg.ALPHA, **kw)
-                elif l.bwd_part_rows:
-                    # the patch conv that made l.grad final left the batch-norm backward sums, one row per patch
-                    ref = None
-                    if self.bn_fuse_check is not None and self._rec is None:
-                        # debug mode: the plain three-kernel backward on the same gradient first, into scratch
-                        ref = (torch.empty_like(l.dx), torch.empty_like(l.dgamma), torch.empty_like(l.dbeta))
-                        L.bn_act_bwd(l.grad, l.raw, l.scale, l.shift, l.mean, l.rstd, ref[0], ref[1], ref[2], M, l.cout,
-                                     self.ws, cfg.ALPHA)
-                    L.bn_act_bwd_partials(l.grad, l.raw, l.scale, l.shift, l.mean, l.rstd, l.dx, l.dgamma, l.dbeta, M,
-                                          l.cout, l.bwd_part, l.bwd_part_rows, self.ws, cfg.ALPHA, **kw)
-                    if ref is not None:
-                        torch.cuda.synchronize()
-
-                        def rel(a, b):
-                            a, b = a.double().flatten(), b.double().flatten()
-                            return float((a - b).norm() / (b.norm() + 1e-30))
-                        self.bn_fuse_check.append({"layer": l.idx, "rows": l.bwd_part_rows, "shape": (l.Ho, l.Wo, l.cout),
-                                                   "dx": rel(l.dx, ref[0]), "dgamma": rel(l.dgamma, ref[1]),
-                                                   "dbeta": rel(l.dbeta, ref[2]),
-                                                   "finite": bool(torch.isfinite(l.dx.float()).all())})
-                else:
-                    L.bn_act_bwd(l.grad, l.raw, l.scale, l.shift, l.mean, l.rstd, l.dx, l.dgamma, l.dbeta, M, l.cout,
-                                 self.ws, cfg.ALPHA, **kw)
-                dx, ld = l.dx, l.cout
-                if sc is not None:
-                    sc.grad_set = True
-            # the weight gradient is off the critical chain (dx -> dgrad -> next layer's BN
-            # backward): in a recorded step it runs on the side lane, overlapping the small
-            # latency-bound BN kernels of the following layers
-            # ... except for the last few layers of the pass: nothing is left on the main lane to
-            # overlap with, the step would only wait for the side lane's backlog to drain
-            # (data parallelism with a CUT list: every weight gradient stays on the side lane -- the bucket all-reduce is ordered
-            # after that lane only.  With the exchange in the list the slices whose last weight gradient ran on the main lane are
-            # exchanged and swept in optimizer_step, whose exchange lane waits for the main lane, which has joined the side lane)
-            tail = self.tail_on_main if (self.dp is None or inl) else 0
-            side = self.use_side_lane and (pos < len(order) - tail)
+            dx, ld = self._bn_backward(l)
             # enqueue order = host order: the data-gradient convs (critical chain, main lane) are issued before the
-            # weight gradient, which only needs dx.  The edge to the side lane is an event RECORDED ON THE MAIN LANE, and a
-            # record costs the recording stream ~3 us (tools/micro/event_cost.hip: a chain of 10-us kernels, 11.0 -> 13.8 us
-            # per kernel with a record behind each, 12.0 with one per three): one edge per layer was ~0.1 ms of a 4.1-ms
-            # step.  So the weight gradients of WGRAD_GROUP consecutive layers share ONE edge, recorded behind the
-            # group's data-gradient convs; the side lane lags a layer or two more, which nothing waits for.
-            for mode, tgt, kw in l.dgrad_descs:
-                if mode == "direct":
-                    final = (final_of.get(tgt.idx) == (l.idx, "direct") and not tgt.lock and tgt.kind != "lin"
-                             and tgt.cout % 8 == 0 and tgt.raw is not None)
-                    self._accumulate_into(tgt, kw, dx, l.cin, l.k, l.stride, final)
-                    tgt.grad_set = True
-                else:
-                    self._accumulate_into(tgt, kw, dx, l.cin, l.k, l.stride)
-                    up = tgt
-                    L.upsample2x_bwd(kw["tmp"], up.grad, B, l.H, l.W, up.cout, 0, up.cout, accumulate=up.grad_set)
-                    up.grad_set = True
-            if l.lock:
+            # weight gradient, which only needs dx
+            for entry in l.dgrad_descs:
+                self._dgrad(l, entry, dx, final_of)
+            if not l.trains:
                 continue                  # no weight gradient, no optimizer slice, no re-pack
-            if pending and pending[-1][4] != side:
-                flush()
-            pending.append((l, dx, ld, M, side))
+            side = self.use_side_lane and (pos_of[l.idx] < len(order) - tail)
+            if pending and pending[-1][3] != side:
+                self._flush_wgrads(pending, sweep, on_layer_done)
+            pending.append((l, dx, ld, side))
             if not side or len(pending) >= WGRAD_GROUP:
-                flush()
-        flush()
+                self._flush_wgrads(pending, sweep, on_layer_done)
+        self._flush_wgrads(pending, sweep, on_layer_done)
         if not self._overlap_rec:
             L.lane_sync(1, 0)
+
+    def _dx_of(self, l: Layer) -> Tuple[torch.Tensor, int]:
+        """(gradient wrt l's conv output, its row pitch): the linear layers' rows are the loss kernels', cout_pad wide"""
+        return l.dx, (l.cout_pad if l.kind == "lin" else l.cout)
+
+    def _bn_backward(self, l: Layer) -> Tuple[torch.Tensor, int]:
+        """l.grad -> l.dx (and dgamma / dbeta of a trainable layer) through the activation and the batch norm, in the form this
+        layer takes; a linear layer's dx is the loss kernels' own.  Returns (dx, its row pitch)."""
+        if l.kind == "lin":
+            return self._dx_of(l)
+        if not l.grad_set:
+            raise L.DisyoloError("layer %d received no gradient" % l.idx)
+        M = self.B * l.Ho * l.Wo
+        # a residual layer hands its output gradient on to the shortcut's source (res_conv_bn, :148-151): that copy / add
+        # rides on the batch-norm backward's apply pass, which reads l.grad anyway
+        sc = self.by_idx[l.shortcut] if l.shortcut is not None else None
+        if sc is not None and sc.grad is None:
+            sc = None
+        kw = dict(shortcut_grad=sc.grad, shortcut_accumulate=sc.grad_set) if sc is not None else {}
+        if l.lock:
+            # a locked layer on the gradient's way (yolo/yolo3_net_pos.py:76-81: moving statistics, nothing to train):
+            # d conv = g * leaky'(z) * scale with the raw / scale / shift its forward used; the shortcut's source gets g
+            L.bn_frozen_bwd(l.grad, l.raw, l.scale, l.shift, l.dx, M, l.cout, cfg.ALPHA, **kw)
+        elif l.fused_bwd:
+            pass        # l.dx, l.dgamma, l.dbeta came out of the data-gradient conv that made l.grad final (_accumulate_into)
+        elif self.sync_bn:
+            # (sum g, sum g*xhat) of this rank -> the same over all ranks -> dx; dgamma / dbeta stay local
+            L.bn_bwd_reduce(l.grad, l.raw, l.scale, l.shift, l.mean, l.rstd, M, l.cout, l.bwd_local, self.ws, cfg.ALPHA)
+            L.copy2d_f32(l.bwd_local.view(torch.float32), l.bwd_global.view(torch.float32), 1, 4 * l.cout,
+                         4 * l.cout, 4 * l.cout)
+            self._sync_sums(l.bwd_global)
+            L.bn_bwd_apply_sums(l.grad, l.raw, l.scale, l.shift, l.mean, l.rstd, l.bwd_local, l.bwd_global,
+                                M * self.dp.world_size, l.dx, l.dgamma, l.dbeta, M, l.cout, self.ws, cfg.ALPHA, **kw)
+        elif l.bwd_part_rows:
+            # the patch conv that made l.grad final left the batch-norm backward sums, one row per patch
+            ref = self._bn_plain_into_scratch(l, M) if (self.bn_fuse_check is not None and self._rec is None) else None
+            L.bn_act_bwd_partials(l.grad, l.raw, l.scale, l.shift, l.mean, l.rstd, l.dx, l.dgamma, l.dbeta, M,
+                                  l.cout, l.bwd_part, l.bwd_part_rows, self.ws, cfg.ALPHA, **kw)
+            if ref is not None:
+                self._file_bn_fuse_check(l, ref)
+        else:
+            L.bn_act_bwd(l.grad, l.raw, l.scale, l.shift, l.mean, l.rstd, l.dx, l.dgamma, l.dbeta, M, l.cout,
+                         self.ws, cfg.ALPHA, **kw)
+        if sc is not None:
+            sc.grad_set = True
+        return self._dx_of(l)
+
+    def _bn_plain_into_scratch(self, l: Layer, M: int):
+        """``bn_fuse_check`` (debug, eager steps): the plain three-kernel backward on l.grad, into scratch (dx, dgamma, dbeta)"""
+        ref = (torch.empty_like(l.dx), torch.empty_like(l.dgamma), torch.empty_like(l.dbeta))
+        L.bn_act_bwd(l.grad, l.raw, l.scale, l.shift, l.mean, l.rstd, ref[0], ref[1], ref[2], M, l.cout, self.ws, cfg.ALPHA)
+        return ref
+
+    def _file_bn_fuse_check(self, l: Layer, ref) -> None:
+        """... and the relative differences of what the partial-sum form then left in l.dx / l.dgamma / l.dbeta"""
+        torch.cuda.synchronize()
+        rel = lambda a, b: float((a.double() - b.double()).norm() / (b.double().norm() + 1e-30))
+        self.bn_fuse_check.append({"layer": l.idx, "rows": l.bwd_part_rows, "shape": (l.Ho, l.Wo, l.cout),
+                                   "dx": rel(l.dx, ref[0]), "dgamma": rel(l.dgamma, ref[1]), "dbeta": rel(l.dbeta, ref[2]),
+                                   "finite": bool(torch.isfinite(l.dx.float()).all())})
+
+    def _dgrad_final(self, l: Layer, tgt: Layer, final_of) -> bool:
+        """l's direct data gradient is the last contribution to tgt.grad, and tgt trains with batch norm: the conv may emit
+        tgt's batch-norm backward sums, or run that whole backward, in its epilogue (_accumulate_into)"""
+        return final_of.get(tgt.idx) == (l.idx, "direct") and tgt.train_bn and tgt.cout % 8 == 0
+
+    def _dgrad(self, l: Layer, entry, dx: torch.Tensor, final_of) -> None:
+        """one data gradient of layer l (an entry of l.dgrad_descs): into its source's gradient, or -- "up" -- into up_tmp
+        and through the 2x upsampling's backward into the gradient of the layer that was upsampled"""
+        mode, tgt, kw = entry
+        if mode == "direct":
+            self._accumulate_into(tgt, kw, dx, l.k, l.stride, self._dgrad_final(l, tgt, final_of))
+        else:
+            self._accumulate_into(tgt, kw, dx, l.k, l.stride)
+            L.upsample2x_bwd(kw["tmp"], tgt.grad, self.B, l.H, l.W, tgt.cout, 0, tgt.cout, accumulate=tgt.grad_set)
+        tgt.grad_set = True
+
+    def _wgrad(self, l: Layer, dx: torch.Tensor, ld: int, side: bool) -> None:
+        """weight gradient of one trainable layer (and the bias gradient of a linear one) on the current lane.  Scratch of
+        the lane it runs on: the side lane's weight gradients own ws_aux; one kept on the main lane (tail_on_main) must not
+        share it -- the side lane may still be inside an earlier layer's slabs (found in round 6: with tail_on_main > 0 the
+        loss differed from run to run)"""
+        wsl = self.ws_aux if side else self.ws
+        if l.kind == "lin":
+            L.colsum(l.dx, l.dbias, self.B * l.Ho * l.Wo, l.cout_pad, l.cout, wsl)   # bias gradient
+        if l.idx == 1:
+            # the first layer's own kernel: taps as the M axis of the MFMA, the f32 image rounded to bf16 on
+            # its way into LDS (csrc/conv_wgrad.hip, conv_first_wgrad_mfma_kernel)
+            L.conv_first_wgrad(self.images, l.dx, l.dw, wsl)
+        else:
+            L.conv2d_wgrad(l.wgrad_desc, dx, ld, l.dw, wsl)
+
+    def _flush_wgrads(self, pending: list, sweep: bool, on_layer_done) -> None:
+        """the weight gradients of a group of consecutive layers (all on the side lane, or all on the main one).  The edge to
+        the side lane is an event RECORDED ON THE MAIN LANE, and a record costs the recording stream ~3 us
+        (tools/micro/event_cost.hip: a chain of 10-us kernels, 11.0 -> 13.8 us per kernel with a record behind each, 12.0 with
+        one per three): one edge per layer was ~0.1 ms of a 4.1-ms step.  So WGRAD_GROUP layers share ONE edge, recorded behind
+        the group's data-gradient convs; the side lane lags a layer or two more, which nothing waits for."""
+        if not pending:
+            return
+        side = pending[0][3]
+        if side:
+            L.lane_wait(L.lane_mark(0), 1)
+        for l, dx, ld, _ in pending:
+            if side:
+                L.set_lane(1)
+            self._wgrad(l, dx, ld, side)
+            if side:
+                L.set_lane(0)
+            if self._overlap_rec:
+                for src, reader in self._xstep_reader.items():
+                    if reader == l.idx and self._xstep_slot[src] in self._xstep_waits.values():     # (only slots somebody waits on)
+                        L.lane_mark_slot(1 if side else 0, self._xstep_slot[src])
+            if sweep and side:
+                self._sweep_slice_when_final(l)
+            if on_layer_done is not None:
+                on_layer_done(l)
+        pending.clear()
+
+    def _sweep_slice_when_final(self, l: Layer) -> None:
+        """l's weight gradient is enqueued on the side lane: once that holds for every layer of its arena slice, the slice's
+        optimizer sweep (+ the re-pack of its layers) is issued behind them -- not at the end of the critical chain.  It
+        rewrites the bf16 operands the data-gradient convs of these layers read: they are all behind the group's edge, which
+        the side lane has waited for"""
+        ci = self._opt_chunk_of[l.idx]
+        self._opt_done[ci].add(l.idx)
+        if self._opt_done[ci] != self.opt_chunks[ci]["members"]:
+            return
+        if self.dp is None:
+            L.set_lane(1)
+            self._sweep_chunk(ci, 1.0)
+            L.set_lane(0)
+            return
+        # data parallel (exchange in the list): the slice's gradients are summed over the ranks first -- the collective goes
+        # to the exchange lane (behind the side lane's weight gradients of the slice; the side lane itself goes on with the
+        # next layers' weight gradients) and the sweep right behind it on the exchange lane (lowest stream priority, like the
+        # side lane the single-GPU step sweeps on): the side lane never waits for the links; its mark sits behind the group's
+        # main-lane edge, so the re-pack is safe.  (A hop between lanes costs ~15 us, profiles/r05_hw_queues.txt, and the
+        # side lane is nearly as busy as the main one.  One RCCL rank, same box, ms per step: plain 4.16-4.18 | this
+        # 4.17-4.18 | exchange lane at normal priority 4.22 | the sweep back on the side lane two layers later 4.20)
+        L.lane_wait(L.lane_mark(1), L.COMM_LANE)
+        L.set_lane(L.COMM_LANE)
+        ch = self.opt_chunks[ci]
+        self.dp.exchange_inlist(ci, ch["off"], ch["cnt"])
+        self._sweep_chunk(ci, 1.0 / self.dp.world_size)
+        L.set_lane(0)
 
     def _apply_tiles(self) -> None:
         """rebuild everything that depends on a tile choice: batch-norm partial-sum buffers
@@ -2072,7 +2072,7 @@ class YOLONet(object):
             # process-wide pool whose priority is fixed when a lane is first used: the setting only helps if lane 1 does not
             # exist yet -- say so when it is too late (a net that has recorded or tuned before enable_data_parallel)
             os.environ.setdefault("DISYOLO_LANE1_LOW", "0")
-            if not getattr(self, "plan_only", False):
+            if not self.plan_only:
                 for ln in L.lanes_report():
                     if ln.startswith("lane 1:") and "priority 0," not in ln and os.environ.get("DISYOLO_LANE1_LOW") == "0":
                         print("disyolo: the cut-list data-parallel step wants lane 1 at normal priority, but the lane already exists "

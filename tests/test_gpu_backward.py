@@ -21,7 +21,7 @@ Bounds (the constants below; "twin" = the same f64 computation on |operands|):
 The constants, and the worst ratios measured on an MI355X, are in backward_ref.
 
 Part B -- every weight-gradient, data-gradient, upsample-backward and colsum launch of the step, on integer operands,
-with the descriptors the step itself uses: f32 outputs bit-equal to the exact sum, bf16 outputs to the exact sum rounded
+issued by the methods backward() itself calls for them (net._dgrad, net._wgrad, net._dgrad_final): f32 outputs bit-equal to the exact sum, bf16 outputs to the exact sum rounded
 once to nearest-even.
 
 Per-layer reports go to test_reports/backward_<config>.json and test_reports/backward_exact_<config>.json at the repository
@@ -285,16 +285,16 @@ def test_backward_launches_are_exact_on_integers(dev, tag, tuned_tables):
         for l in visit:
             if l.lock:
                 continue
-            ws = net.ws
-            dy = l.dx[..., :l.cout]
-            M = B * l.Ho * l.Wo
+            dx, ld = net._dx_of(l)                           # (what backward() hands on from the layer's batch-norm step)
+            dy = dx[..., :l.cout]
             # ---- the residual layer's batch-norm backward hands its gradient to the shortcut's source first
             if l.kind == "res" and net.by_idx[l.shortcut].grad is not None:
                 sc = net.by_idx[l.shortcut]
                 _ints(sc.grad, -2, 2, gen)
                 sc.grad_set = True
-            # ---- data gradients, exactly as backward() issues them
-            for mode, tgt, kw in l.dgrad_descs:
+            # ---- data gradients: backward()'s own step for each entry (net._dgrad), the net's own ``final`` predicate
+            for entry in l.dgrad_descs:
+                mode, tgt, kw = entry
                 first = not tgt.grad_set
                 if first:
                     tgt.grad.fill_(float("nan"))             # a first write must not read what was there
@@ -304,11 +304,10 @@ def test_backward_launches_are_exact_on_integers(dev, tag, tuned_tables):
                     prev = R.f64(tgt.grad)
                 w = R.f64(l.w)
                 if mode == "direct":
-                    final = (final_of.get(tgt.idx) == (l.idx, "direct") and not tgt.lock and tgt.kind != "lin"
-                             and tgt.cout % 8 == 0 and tgt.raw is not None)
+                    final = net._dgrad_final(l, tgt, final_of)
                     lo = 0
                     tgt.bwd_part_rows = 0
-                    net._accumulate_into(tgt, kw, l.dx, l.cin, l.k, l.stride, final)
+                    net._dgrad(l, entry, dx, final_of)
                     exact = R.dgrad_ref(dy, w[:, :, lo:lo + tgt.cout, :], l.stride, l.H, l.W)
                     if prev is not None:
                         exact = exact + prev
@@ -327,11 +326,10 @@ def test_backward_launches_are_exact_on_integers(dev, tag, tuned_tables):
                     tmp = kw["tmp"]
                     tmp.fill_(float("nan"))
                     lo = net.by_idx[l.src].cout
-                    net._accumulate_into(tgt, kw, l.dx, l.cin, l.k, l.stride)
+                    net._dgrad(l, entry, dx, final_of)       # the conv into up_tmp, then upsample2x_bwd (which only reads it)
                     exact = R.dgrad_ref(dy, w[:, :, lo:lo + tgt.cout, :], 1, l.H, l.W)
                     what = "layer %d -> %d dgrad (concat, up_tmp)" % (l.idx, tgt.idx)
                     _collect(fails, R.check_exact_bf16, tmp, exact, what)
-                    L.upsample2x_bwd(tmp, tgt.grad, B, l.H, l.W, tgt.cout, 0, tgt.cout, accumulate=tgt.grad_set)
                     up = R.upsample2_bwd(R.f64(tmp))
                     if prev is not None:
                         up = up + prev
@@ -339,24 +337,21 @@ def test_backward_launches_are_exact_on_integers(dev, tag, tuned_tables):
                                                                                           ", accumulate" if prev is not None else ""))
                     launches.append({"layer": l.idx, "launch": "dgrad+upsample2x_bwd", "target": tgt.idx, "path": "up",
                                      "accumulate": prev is not None, "final": False})
-                tgt.grad_set = True
-            # ---- weight gradient (and the linear layers' bias gradient)
+            # ---- weight gradient (and the linear layers' bias gradient): backward()'s own step (net._wgrad), main lane
             l.dw.fill_(float("nan"))
+            if l.kind == "lin":
+                l.dbias.fill_(float("nan"))
+            net._wgrad(l, dx, ld, False)
             if l.idx == 1:
-                L.conv_first_wgrad(net.images, l.dx, l.dw, ws)
                 plan = "conv_first_wgrad"
                 x = R.f64(net.images)
             else:
-                ld = L.GRAD_LD if l.kind == "lin" else l.cout
-                L.conv2d_wgrad(l.wgrad_desc, l.dx, ld, l.dw, ws)
                 plan = list(L.conv2d_wgrad_plan(l.wgrad_desc))
                 x = R.layer_input(l, net.by_idx)
             _collect(fails, R.check_exact_f32, l.dw, R.wgrad_ref(x, dy, l.k, l.stride), "layer %d dW (plan %s)" % (l.idx, plan))
             del x
             launches.append({"layer": l.idx, "launch": "wgrad", "plan": plan})
             if l.kind == "lin":
-                l.dbias.fill_(float("nan"))
-                L.colsum(l.dx, l.dbias, M, L.GRAD_LD, l.cout, ws)
                 _collect(fails, R.check_exact_f32, l.dbias, R.f64(dy).sum((0, 1, 2)), "layer %d colsum" % l.idx)
                 launches.append({"layer": l.idx, "launch": "colsum"})
         torch.cuda.synchronize()

@@ -19,7 +19,7 @@ from backward_ref import C_G_REL, C_G_ACC, C_G_TWIN
 from disyolo_amd import config as cfg
 from disyolo_amd import lib as L
 from disyolo_amd.net import YOLONet
-from lock_maps import MAPS, lock_of, pass_through
+from lock_maps import MAPS, inputs_of, lock_of, pass_through
 from net_setup import perturb_variables
 
 pytestmark = pytest.mark.gpu
@@ -287,6 +287,37 @@ def test_pass_through_layers_one_by_one(dev, name):
             assert bool((err <= U_BF16 * want_act.abs() + 1e-6 * (z.abs() + 1)).all()), "layer %d forward" % l.idx
             print("%s layer %d: g %.3f dx %.3f of the bound" % (name, l.idx, worst, wdx))
     assert seen == len([i for i in pass_through(*lock_of(name)) if by[i].kind != "lin"])
+
+
+@pytest.mark.parametrize("name", ["hole_5_9", "stage1_hole"])
+def test_buffers_and_descriptors_follow_the_layer_roles(dev, name):
+    """what _plan and _build_descs give a layer, at B = 1, 64^2 (the smallest net the kernels take): the kept conv output
+    exactly where the layer keeps it, dx exactly for the linear layers and the layers the gradient crosses, and the output
+    gradient, the flipped weights and the weight-gradient descriptor where the spelled-out conditions put them (which layer
+    has a trainable layer at or above it comes from the test's own walk of the graph)"""
+    m, lock = lock_of(name)
+    net = YOLONet(training=True, device=dev, image_size=64, batch_size=1, lock=lock, mask_stride=m, seed=1)
+    ins = inputs_of(m)
+
+    def trainable_upto(i, seen=None):
+        seen = set() if seen is None else seen
+        if i == 0 or i in seen:
+            return False
+        seen.add(i)
+        return (not lock[i]) or any(trainable_upto(j, seen) for j in ins[i])
+
+    assert [l.idx for l in net.layers if l.passthru] == pass_through(m, lock)
+    for l in net.layers:
+        what = "%s, layer %d" % (name, l.idx)
+        crossed = (not l.lock) or l.passthru
+        assert l.on_path == crossed and l.keeps_raw == (crossed and l.kind != "lin"), what
+        assert (l.raw is not None) == l.keeps_raw, what
+        assert (l.dx is not None) == (l.kind == "lin" or l.on_path), what
+        assert (l.grad is not None) == (trainable_upto(l.idx) and l.kind != "lin"), what
+        srcs = [i for i in (l.src, l.src_up) if i is not None]
+        assert (l.wdg is not None) == (crossed and l.idx > 1 and any(trainable_upto(i) for i in srcs)), what
+        assert (l.wgrad_desc is not None) == (not l.lock and l.idx > 1), what
+        assert bool(l.dgrad_descs) == (l.wdg is not None), what
 
 
 # ------------------------------------------------------------------------------------------------ recorded forms

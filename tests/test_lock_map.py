@@ -9,8 +9,8 @@ import torch
 
 import disyolo_oracle as O
 import mask_stride_ref as R
-from disyolo_amd.net import YOLONet
-from lock_maps import MAPS, lock_of, pass_through
+from disyolo_amd.net import YOLONet, build_topology
+from lock_maps import MAPS, SCORE_LAYER, STRIDE_MAPS, inputs_of, lock_of, pass_through
 
 
 def _net(name, **kw):
@@ -91,6 +91,60 @@ def test_reference_stages_and_inference_nets_have_no_pass_through_layer():
         assert YOLONet(training=True, plan_only=True, stage=stage).pass_through_layers() == []
     m, lock = lock_of("hole_5_9")
     assert YOLONet(training=False, plan_only=True, lock=lock).pass_through_layers() == []
+
+
+def test_layer_roles_equal_the_spelled_out_predicates_and_the_gradients_way():
+    """the role slots (trains, train_bn, keeps_raw, on_path) against the predicates they replaced, and on_path against an
+    independent walk of the reference's graph: exactly the layers with a trainable layer at or upstream of them and a loss
+    downstream.  Every lock map of lock_maps.py and both stages at every mask stride, training and not.  On the layer table,
+    through the function the constructor itself calls (YOLONet._mark_pass_through): a plan-only net takes seconds to
+    initialise its variables, and its roles are a function of (table, lock map, training) alone"""
+    cases = [(lock_of(name)) for name in list(MAPS) + list(STRIDE_MAPS)]
+    cases += [(m, {i: (stage == 1 and i <= 52) for i in range(1, SCORE_LAYER[m] + 1)}) for stage in (1, 2) for m in (1, 2, 4)]
+    for m, lock in cases:
+        ins = inputs_of(m)
+        readers = {i: [j for j in ins if i in ins[j]] for i in ins}
+        losses = {59, 67, 75, SCORE_LAYER[m]}
+
+        def above(i, seen):          # i and everything upstream of it
+            if i and i not in seen:
+                seen.add(i)
+                for j in ins[i]:
+                    above(j, seen)
+            return seen
+
+        def reaches_loss(i):
+            return i in losses or any(reaches_loss(j) for j in readers[i])
+
+        for training in (True, False):
+            layers = build_topology(80, 3, m)
+            YOLONet._mark_pass_through(layers, lock, training)
+            assert [l.idx for l in layers] == sorted(ins)
+            for l in layers:
+                what = "m = %d, layer %d, training %s" % (m, l.idx, training)
+                assert l.lock == lock[l.idx], what
+                assert l.trains == (training and not l.lock), what
+                assert l.train_bn == (training and (not l.lock) and l.kind != "lin"), what
+                assert l.keeps_raw == (training and (not l.lock or l.passthru) and l.kind != "lin"), what
+                assert l.on_path == (training and (not l.lock or l.passthru)), what
+                assert (not l.on_path) == (not training or (l.lock and not l.passthru)), what
+                assert (l.on_path or (training and l.kind == "lin")) == \
+                    (training and (not l.lock or l.passthru or l.kind == "lin")), what
+                assert all(isinstance(v, bool) for v in (l.trains, l.train_bn, l.keeps_raw, l.on_path, l.passthru)), what
+                want = training and any(not lock[t] for t in above(l.idx, set())) and reaches_loss(l.idx)
+                assert l.on_path == want, what
+            assert [l.idx for l in layers if l.passthru] == (pass_through(m, lock) if training else [])
+
+
+def test_a_plan_only_net_carries_the_roles_of_its_table():
+    m, lock = lock_of("stage1_hole")
+    net = YOLONet(training=True, plan_only=True, mask_stride=m, lock=lock)
+    layers = build_topology(net.num_class, net.k, m)
+    assert YOLONet._mark_pass_through(layers, lock, True) == net._needs_grad_into
+    for a, b in zip(net.layers, layers):
+        assert (a.lock, a.passthru, a.trains, a.train_bn, a.keeps_raw, a.on_path) == \
+            (b.lock, b.passthru, b.trains, b.train_bn, b.keeps_raw, b.on_path)
+    assert [l.idx for l in net.layers if l.on_path] == list(range(53, 83))
 
 
 def test_fp8_refuses_a_lock_map_that_breaks_the_fp8_chain():
