@@ -6,6 +6,8 @@
 //   tile_paste_bits  every kept detection's mask pasted into its tile as a BIT plane (paste_bit, one wave ballot per 64 px)
 //   tile_seam_counts per candidate pair of instances of two overlapping tiles: |A n R|, |B n R|, |A n B| by popcount
 //   tile_compose     per merged group: the OR of its members cropped to its box, and the owner map (integer atomicMax)
+// and for tiled evaluation (evaluate.MAP.collect_tiled; defined by tests/tiles_eval_ref.py) one more per photograph:
+//   tile_group_counts per (group, ground-truth instance) pair: |mask n gt| over the groups' arena bytes and cropped bit planes
 // Every output is an integer or a bit and every sum an integer sum, so nothing depends on the order the lanes land in.
 #include <vector>
 #include "common.h"
@@ -165,6 +167,80 @@ __global__ __launch_bounds__(TC_T) void tile_compose_kernel(const int* groups, i
   }
 }
 
+// ---- group counts (tiled evaluation) --------------------------------------------------------------------------------------
+// pairs[p] = {g, j, block0}: |mask_g n gt_j|, or with j = -1 the group's own pixel count.  The pair's rectangle is the
+// group's box, cut to the ground-truth instance's box when there is one; a block takes GC_CHUNK consecutive pixels of the
+// rectangle (row-major), a thread GC_PX of them GC_T apart, so that a wave reads 64 neighbouring bytes of the arena.  The two
+// operands need no common alignment: a lane takes its pixel's byte of the group (origin x1_g) and its pixel's bit of the plane
+// (origin x1_j, word (x - x1_j) / 32), the wave ballots "both set", and the popcounts are summed: one integer atomic per block.
+// A pair gets one block per chunk up to GC_MAX_BLOCKS, which then stride over the chunks: a rectangle the size of the
+// photograph still covers the device, but no more than GC_MAX_BLOCKS atomics land on its one count (adds to ONE address run
+// at some 90 per microsecond: with a block per chunk a 12-Mpixel box spent its time there, not reading).
+constexpr int GC_T = 256;
+constexpr int GC_PX = 8;
+constexpr int GC_CHUNK = GC_T * GC_PX;
+constexpr int GC_MAX_BLOCKS = 1024;
+
+__host__ __device__ inline int group_counts_blocks(int64_t area) {
+  if (area <= 0) return 1;
+  const int64_t chunks = (area + GC_CHUNK - 1) / GC_CHUNK;
+  return chunks < GC_MAX_BLOCKS ? (int)chunks : GC_MAX_BLOCKS;
+}
+
+__global__ __launch_bounds__(GC_T) void tile_group_counts_kernel(const int* groups, const unsigned char* arena, const int* gt,
+                                                                 const unsigned int* gt_bits, const int* pairs, int P, int* counts) {
+  __shared__ int part[GC_T / 64];
+  int lo = 0, hi = P - 1;      // the last pair whose first block is <= this block
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (pairs[mid * 3 + 2] <= (int)blockIdx.x) lo = mid; else hi = mid - 1;
+  }
+  const int* pr = pairs + lo * 3;
+  const int* g = groups + (size_t)pr[0] * 8;
+  const int j = pr[1];
+  const int gy1 = g[2], gx1 = g[3], bw = g[5] - gx1;
+  int ry1 = gy1, rx1 = gx1, ry2 = g[4], rx2 = g[5];
+  int jy1 = 0, jx1 = 0, pitch = 0;
+  const unsigned int* plane = gt_bits;
+  if (j >= 0) {
+    const int* t = gt + (size_t)j * 8;
+    jy1 = t[0], jx1 = t[1], pitch = t[5];
+    ry1 = max(ry1, jy1), rx1 = max(rx1, jx1), ry2 = min(ry2, t[2]), rx2 = min(rx2, t[3]);
+    plane = gt_bits + (size_t)t[6];
+  }
+  const int rw = rx2 - rx1;
+  const unsigned int area = (ry2 > ry1 && rw > 0) ? (unsigned int)(ry2 - ry1) * (unsigned int)rw : 0u;     // < 2^31 (checked)
+  const unsigned int nb = (unsigned int)group_counts_blocks(area);
+  const unsigned char* mask = arena + (size_t)g[7] * 16;
+  int n = 0;                   // (wave-uniform: every lane holds its wave's count)
+  // (block-uniform trip count: every lane reaches every ballot.  chunk * GC_CHUNK < area + nb * GC_CHUNK < 2^31 + 2^21)
+  for (unsigned int chunk = (unsigned int)blockIdx.x - (unsigned int)pr[2]; chunk * GC_CHUNK < area; chunk += nb) {
+#pragma unroll
+    for (int k = 0; k < GC_PX; ++k) {
+      const unsigned int p = chunk * GC_CHUNK + k * GC_T + threadIdx.x;
+      bool on = false;
+      if (p < area) {
+        const unsigned int yr = p / (unsigned int)rw;
+        const int y = ry1 + (int)yr, x = rx1 + (int)(p - yr * (unsigned int)rw);
+        on = mask[(size_t)(y - gy1) * bw + (x - gx1)] != 0;
+        if (on && j >= 0) {
+          const int c = x - jx1;
+          on = (plane[(size_t)(y - jy1) * pitch + (c >> 5)] >> (c & 31)) & 1u;
+        }
+      }
+      n += __popcll(__ballot(on));
+    }
+  }
+  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = n;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int s = 0;
+#pragma unroll
+    for (int wv = 0; wv < GC_T / 64; ++wv) s += part[wv];
+    if (s) atomicAdd(&counts[lo], s);
+  }
+}
+
 bool net_ok(int H, int W) { return H > 0 && W > 0 && W % 32 == 0; }
 
 bool tiles_ok(const int32_t* origins_host, int T, int H, int W) {
@@ -298,4 +374,71 @@ extern "C" int disyolo_tile_compose(const int32_t* groups_host, const int32_t* g
   }
   return tile_compose_run(groups, G, (int)blocks, members, inst_tile, origins, planes, net_h, net_w, image_h, image_w, arena, owner,
                           stream);
+}
+
+extern "C" int disyolo_tile_group_counts_blocks(int64_t area) { return group_counts_blocks(area); }
+
+static int tile_group_counts_run(const int32_t* groups, const uint8_t* arena, const int32_t* gt, const uint32_t* gt_bits,
+                                 const int32_t* pairs, int P, int blocks, int32_t* counts, void* stream) {
+  DY_RECORD_OR_RUN([=](void* s) { return tile_group_counts_run(groups, arena, gt, gt_bits, pairs, P, blocks, counts, s); });
+  if (hipMemsetAsync(counts, 0, (size_t)P * sizeof(int32_t), (hipStream_t)stream) != hipSuccess) {
+    disyolo_set_error("tile_group_counts: hipMemsetAsync failed");
+    return DISYOLO_E_HIP;
+  }
+  hipLaunchKernelGGL(tile_group_counts_kernel, dim3(blocks), dim3(GC_T), 0, (hipStream_t)stream, (const int*)groups,
+                     (const unsigned char*)arena, (const int*)gt, (const unsigned int*)gt_bits, (const int*)pairs, P,
+                     (int*)counts);
+  DY_CHECK_LAUNCH();
+  return DISYOLO_OK;
+}
+
+extern "C" int disyolo_tile_group_counts(const int32_t* groups_host, const int32_t* groups, int G, const uint8_t* arena,
+                                         int64_t arena_bytes, const int32_t* gt_host, const int32_t* gt, int ng,
+                                         const uint32_t* gt_bits, int64_t gt_words, const int32_t* pairs_host,
+                                         const int32_t* pairs, int P, int image_h, int image_w, int32_t* counts, void* stream) {
+  DY_REQUIRE(G >= 0 && ng >= 0 && P >= 0 && image_h > 0 && image_w > 0 && arena_bytes >= 0 && gt_words >= 0,
+             "tile_group_counts: bad args");
+  DY_REQUIRE((int64_t)image_h * image_w < (1ll << 31), "tile_group_counts: image too large");
+  if (P == 0 || G == 0) return DISYOLO_OK;
+  DY_REQUIRE(groups_host && groups && arena && pairs_host && pairs && counts, "tile_group_counts: null pointer");
+  DY_REQUIRE(ng == 0 || (gt_host && gt && (gt_bits || gt_words == 0)), "tile_group_counts: null pointer");
+  // the host copies are what this call can check: every index and offset the kernel follows
+  for (int gi = 0; gi < G; ++gi) {
+    const int32_t* g = groups_host + (size_t)gi * 8;
+    DY_REQUIRE(g[2] >= 0 && g[2] <= g[4] && g[4] <= image_h && g[3] >= 0 && g[3] <= g[5] && g[5] <= image_w,
+               "tile_group_counts: group %d: box (%d, %d, %d, %d) leaves the %d x %d image", gi, g[2], g[3], g[4], g[5], image_h,
+               image_w);
+    const int64_t area = (int64_t)(g[4] - g[2]) * (g[5] - g[3]);
+    DY_REQUIRE(g[7] >= 0 && (int64_t)g[7] * 16 + area <= arena_bytes,
+               "tile_group_counts: group %d does not fit the arena of %lld bytes", gi, (long long)arena_bytes);
+  }
+  for (int j = 0; j < ng; ++j) {
+    const int32_t* t = gt_host + (size_t)j * 8;
+    DY_REQUIRE(t[0] >= 0 && t[0] <= t[2] && t[2] <= image_h && t[1] >= 0 && t[1] <= t[3] && t[3] <= image_w,
+               "tile_group_counts: ground truth %d: box (%d, %d, %d, %d) leaves the %d x %d image", j, t[0], t[1], t[2], t[3],
+               image_h, image_w);
+    const int64_t rows = t[2] - t[0], need = (t[3] - t[1] + 31) / 32;
+    DY_REQUIRE(t[5] >= need && t[6] >= 0 && (int64_t)t[6] + rows * t[5] <= gt_words,
+               "tile_group_counts: ground truth %d: pitch %d, offset %d do not hold its %lld x %d box in %lld words", j, t[5],
+               t[6], (long long)rows, t[3] - t[1], (long long)gt_words);
+  }
+  int64_t blocks = 0;
+  for (int p = 0; p < P; ++p) {
+    const int32_t* pr = pairs_host + (size_t)p * 3;
+    DY_REQUIRE(pr[0] >= 0 && pr[0] < G && pr[1] >= -1 && pr[1] < ng,
+               "tile_group_counts: pair %d = (%d, %d) is out of range (%d groups, %d ground-truth instances)", p, pr[0], pr[1], G,
+               ng);
+    const int32_t* g = groups_host + (size_t)pr[0] * 8;
+    int64_t rh = g[4] - g[2], rw = g[5] - g[3];
+    if (pr[1] >= 0) {
+      const int32_t* t = gt_host + (size_t)pr[1] * 8;
+      rh = (int64_t)(g[4] < t[2] ? g[4] : t[2]) - (g[2] > t[0] ? g[2] : t[0]);
+      rw = (int64_t)(g[5] < t[3] ? g[5] : t[3]) - (g[3] > t[1] ? g[3] : t[1]);
+    }
+    DY_REQUIRE(pr[2] == blocks, "tile_group_counts: pair %d: block0 is %d, the plan gives %lld (disyolo_tile_group_counts_blocks)",
+               p, pr[2], (long long)blocks);
+    blocks += disyolo_tile_group_counts_blocks(rh > 0 && rw > 0 ? rh * rw : 0);
+    DY_REQUIRE(blocks < (1ll << 31), "tile_group_counts: too many pixels for one launch");
+  }
+  return tile_group_counts_run(groups, arena, gt, gt_bits, pairs, P, (int)blocks, counts, stream);
 }

@@ -44,6 +44,31 @@ def load_image_rgb(path: str) -> np.ndarray:
         return np.asarray(im.convert("RGB"))
 
 
+def gt_bit_planes(masks) -> Tuple[np.ndarray, np.ndarray]:
+    """ground-truth masks [h,w] (> 0.5 is set) -> (gt int32 [ng,8] = y1, x1, y2, x2, 0, pitch, off, area; words uint32): each
+    instance as a bit plane cropped to its tight box, pitch = ceil((x2 - x1) / 32) words per row from word ``off``; bit i of
+    word k of row r is pixel (y1 + r, x1 + 32 k + i) and the bits past the box's last column are zero (disyolo_tile_group_counts'
+    layout).  An instance without pixels has an empty box and area 0.  Column 4 (the class id) is the caller's."""
+    gt = np.zeros((len(masks), 8), np.int32)
+    words, off = [], 0
+    for j, mask in enumerate(masks):
+        m = np.asarray(mask).astype(float) > 0.5
+        ys, xs = np.flatnonzero(m.any(1)), np.flatnonzero(m.any(0))
+        if ys.size == 0:
+            gt[j, 6] = off
+            continue
+        y1, x1, y2, x2 = int(ys[0]), int(xs[0]), int(ys[-1]) + 1, int(xs[-1]) + 1
+        pitch = -(-(x2 - x1) // 32)
+        rows = np.zeros((y2 - y1, pitch * 32), bool)
+        rows[:, :x2 - x1] = m[y1:y2, x1:x2]
+        words.append(np.packbits(rows, axis=1, bitorder="little").view("<u4").reshape(-1))
+        gt[j] = (y1, x1, y2, x2, 0, pitch, off, int(rows.sum()))
+        off += (y2 - y1) * pitch
+    if off >= 1 << 31:
+        raise ValueError("gt_bit_planes: the instances' boxes hold too many words for int32 offsets")
+    return gt, (np.concatenate(words) if words else np.zeros(0, "<u4")).astype(np.uint32)
+
+
 class MAP(object):
     """Ground truth + metric, like the reference's two ``MAP`` classes.  ``groundtruth`` =
     [recs_mask, recs_mergemask or recs_size, ..., index] is passed in (the reference builds it from its
@@ -284,6 +309,80 @@ class MAP(object):
                     detfile[str(c)].append({"imageid": imageid, "score": float(det[b][k, 5]), "ov": ov})
         return out
 
+    def _gt_planes(self, imageid: str, device):
+        """all ground-truth instances of one image for ``collect_tiled``, as bit planes cropped to their tight boxes
+        (``gt_bit_planes``): (gt int32 [ng,8] on the host, its CUDA copy, the words int32 CUDA, {classid: (instance indices of
+        that class in ``recs_mask`` order = voc_eval's ``objs`` order, their pixel counts f32 on the host)}).  Cached like
+        ``_gt_image``, whose uint8 [ng,H,W] stack is 8 x H x W / box area times larger."""
+        key = ("planes", imageid)
+        hit = self._gt_cache.get(key)
+        if hit is None:
+            objs = self.recs_mask[imageid]
+            gt, words = gt_bit_planes([o["mask"] for o in objs])
+            cls = np.array([o["classid"] for o in objs], np.int32).reshape(-1)
+            gt[:, 4] = cls
+            per_class = {int(c): (np.nonzero(cls == c)[0], gt[cls == c, 7].astype(np.float32)) for c in np.unique(cls)}
+            hit = (gt, torch.from_numpy(gt).to(device), torch.from_numpy(words.view(np.int32)).to(device), per_class)
+            self._gt_cache[key] = hit
+        return hit
+
+    def collect_tiled(self, imageid: str, res, detfile: Dict[str, List[Dict]], true_map=None,
+                      conf: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``collect`` for what ``tiles.detect_tiled`` / ``tiles.merge_tiles`` returned for one whole image (``res``, a
+        ``TiledDetections`` in image pixels: ``net_size`` plays no part).  Every merged group is a detection.  Its mask stays
+        cropped to its box in the merge's arena and the ground truth stays cropped bit planes (``_gt_planes``): one upload (the
+        pair table: per group its own pixel count, and one row per ground-truth instance of its class whose box meets the
+        group's), ONE launch (disyolo_tile_group_counts), one fetch of the counts.  Appends to ``detfile`` what ``collect`` would
+        append for the groups' full-size masks, in its order (classes ascending, groups in rank order within a class); with
+        ``true_map`` (uint8 [h,w]) and ``conf`` adds the image's confusion counts; returns ``res.merged``.
+
+        The ``ov`` rows are inter / (area_group + area_gt - inter) in f32 from integer counts converted to f32 --
+        ``collect_batch``'s arithmetic, equal to ``compute_overlaps_masks`` bit for bit while the image has fewer than 2^24
+        pixels.  Above that (3000 x 4000 is 1.2e7, 5000 x 4000 is past it) the counts here are still exact integers, where the
+        reference's f32 sums of ones stop counting at 2^24: the rows can then differ, and these are the right ones.
+        ``DISYOLO_EVAL_GPU_IOU=0`` takes the host path instead (full-size masks to ``voc_eval``), the built-in comparator."""
+        image_hw = tuple(int(v) for v in self.sizes[imageid])
+        if tuple(res.image_hw) != image_hw:
+            raise ValueError("collect_tiled: the result is of a %s image, %r is %s" % (tuple(res.image_hw), imageid, image_hw))
+        G = len(res)
+        classid = np.asarray(res.classid, np.int64).reshape(-1)
+        if G and os.environ.get("DISYOLO_EVAL_GPU_IOU", "1") == "0":
+            for c in sorted({int(v) for v in classid}):
+                for g in np.nonzero(classid == c)[0]:
+                    detfile[str(c)].append({"imageid": imageid, "score": float(res.score[g]),
+                                            "mask": res.full_mask(int(g)).cpu().numpy()})
+        elif G:
+            dev = res.arena.device
+            gt, gt_dev, gt_bits, per_class = self._gt_planes(imageid, dev)
+            boxes = np.asarray(res.boxes, np.int64).reshape(-1, 4)
+            # ---- the pair table in one pass: (g, -1) per group, (g, j) per instance of the group's class whose box meets its box
+            meet = ((classid[:, None] == gt[None, :, 4])
+                    & (np.minimum(boxes[:, None, 2], gt[None, :, 2]) > np.maximum(boxes[:, None, 0], gt[None, :, 0]))
+                    & (np.minimum(boxes[:, None, 3], gt[None, :, 3]) > np.maximum(boxes[:, None, 1], gt[None, :, 1])))
+            pg, pj = np.nonzero(meet)
+            pairs2 = np.concatenate([np.stack([np.arange(G), np.full(G, -1)], 1), np.stack([pg, pj], 1)])
+            pairs, _ = L.tile_group_counts_plan(res.groups, gt, pairs2)
+            cnt = L.tile_group_counts(res.groups, res.arena, gt, gt_bits, pairs, image_hw, groups_dev=res.groups_dev,
+                                      gt_dev=gt_dev, arena_bytes=res.arena_bytes).cpu().numpy()   # one upload, launch, fetch
+            area = cnt[:G].astype(np.float32)
+            inter_all = np.zeros((G, gt.shape[0]), np.float32)                                  # a missing pair is inter = 0
+            inter_all[pg, pj] = cnt[G:]
+            for c in sorted({int(v) for v in classid}):
+                rows = np.nonzero(classid == c)[0]
+                if c not in per_class:
+                    ovs = [np.zeros(0, np.float32)] * len(rows)
+                else:
+                    cols, gt_area = per_class[c]
+                    inter = inter_all[rows][:, cols]                                             # [nd, ng] exact counts
+                    union = area[rows][:, None] + gt_area[None, :] - inter
+                    with np.errstate(divide="ignore", invalid="ignore"):
+                        ovs = list((inter / union).astype(np.float32))
+                for g, ov in zip(rows, ovs):
+                    detfile[str(c)].append({"imageid": imageid, "score": float(res.score[g]), "ov": ov})
+        if true_map is not None and conf is not None:
+            self._add_confusion(self._true_map(imageid, true_map, res.merged.device), res.merged, conf)
+        return res.merged
+
     def do_python_eval(self, detdata: List[Dict]):
         """utils/validation_map.py:104-198: detdata = [{'boxes' [n,6], 'masks' [n,S,S] (CUDA tensor or numpy)
         or the scalar 0.0, 'imname'}] in ``index`` order -> [{'thresh', 'AP' [3], 'mAP' [recall, precision, mAP]}]"""
@@ -301,14 +400,26 @@ class MAP(object):
 
 
 def evaluate(net, images: Dict[str, np.ndarray], eval_map: MAP, det_thresh: float = cfg.OBJ_THRESHOLD,
-             weights_file: Optional[str] = None):
+             weights_file: Optional[str] = None, tiled: Optional[Dict] = None):
     """calculate_test_map.py:180-347.  ``images``: image id -> RGB uint8 array (or a path to decode);
     ``net``: a YOLONet built with batch size 1 like the reference's test graph (:354), or with a larger one: B images are then
     letter-boxed into one frame, run as one batch and collected by ``MAP.collect_batch`` (a short last batch runs with the
     stale frames of the one before left in place).  Returns
     (thresh_out, mask_acc, timing) = ([{'thresh', 'AP', 'mAP'}], [bg, crack, spall, rebar, mIoU] or None,
     {'prediction_s', 'crop_assemble_s', 'per_image_s'}).  The class list is ``eval_map``'s (``MAP(classes=...)``, the net's must
-    have as many): one AP per class, and mask_acc = background, one IoU per class, their mean."""
+    have as many): one AP per class, and mask_acc = background, one IoU per class, their mean.
+
+    ``tiled``: None (the letter-boxed loops above), or a dict {"overlap": 64, "merge_overlap": 0.5} (either key may be left
+    out): every image runs whole through ``tiles.detect_tiled`` -- any image size, any batch size and option set of an
+    inference net -- and its merged instances are scored in image pixels by ``MAP.collect_tiled``.  ``prediction_s`` is then
+    the time in ``detect_tiled``, ``crop_assemble_s`` the time in ``collect_tiled``."""
+    if tiled is not None:
+        unknown = sorted(set(tiled) - {"overlap", "merge_overlap"})
+        if unknown:
+            raise ValueError("evaluate: tiled takes the keys 'overlap' and 'merge_overlap' (got %s)" %
+                             ", ".join(repr(k) for k in unknown))
+        if net.training:
+            raise ValueError("evaluate: tiled evaluation takes an inference net (training=False)")
     if weights_file is not None:
         from .checkpoint import restore_net
         restore_net(net, weights_file)                       # saver.restore (:184-185)
@@ -322,6 +433,10 @@ def evaluate(net, images: Dict[str, np.ndarray], eval_map: MAP, det_thresh: floa
         raise ValueError("evaluate: the net has %d classes, the MAP %d" % (net.num_class, eval_map.num_class))
     seg = SegmentationAccuracy(net.device, eval_map.num_class) if eval_map.merged is not None else None
     t_pred = t_crop = 0.0
+    if tiled is not None:
+        t_pred, t_crop = _evaluate_tiled(net, images, eval_map, det_thresh, detfile, seg, tiled.get("overlap", 64),
+                                         tiled.get("merge_overlap", 0.5))
+        return _evaluate_result(eval_map, detfile, seg, t_pred, t_crop)
     if B > 1:
         t_pred, t_crop = _evaluate_batches(net, images, eval_map, det_thresh, detfile, seg)
         return _evaluate_result(eval_map, detfile, seg, t_pred, t_crop)
@@ -379,6 +494,29 @@ def _evaluate_batches(net, images, eval_map: MAP, det_thresh: float, detfile, se
         t = time.time()
         eval_map.collect_batch(ids, dets, keep, masks, detfile,
                                true_maps=[eval_map.merged[i] for i in ids] if seg is not None else None,
+                               conf=seg.conf if seg is not None else None)
+        torch.cuda.synchronize()
+        t_crop += time.time() - t
+    return t_pred, t_crop
+
+
+def _evaluate_tiled(net, images, eval_map: MAP, det_thresh: float, detfile, seg, overlap, merge_overlap) -> Tuple[float, float]:
+    """evaluate()'s loop over whole images: ``tiles.detect_tiled`` (the tiles run as batches of the net's size), then
+    ``MAP.collect_tiled``.  Returns (seconds in detect_tiled, seconds in collect_tiled)."""
+    from .tiles import detect_tiled
+    t_pred = t_crop = 0.0
+    for index in eval_map.index:
+        src = images[index]
+        rgb = load_image_rgb(src) if isinstance(src, str) else np.asarray(src)
+        assert list(rgb.shape[:2]) == list(eval_map.sizes[index])
+        rgb = torch.from_numpy(np.ascontiguousarray(rgb)).to(net.device)
+        torch.cuda.synchronize()
+        t = time.time()
+        res = detect_tiled(net, rgb, overlap, det_thresh, merge_overlap)
+        torch.cuda.synchronize()
+        t_pred += time.time() - t
+        t = time.time()
+        eval_map.collect_tiled(index, res, detfile, true_map=eval_map.merged[index] if seg is not None else None,
                                conf=seg.conf if seg is not None else None)
         torch.cuda.synchronize()
         t_crop += time.time() - t

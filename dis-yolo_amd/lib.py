@@ -193,6 +193,10 @@ _SIGS = {
     "disyolo_tile_compose": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                        C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                        C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "disyolo_tile_group_counts_blocks": (C.c_int, [C.c_int64]),
+    "disyolo_tile_group_counts": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                            C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                            C.c_void_p, C.c_void_p]),
     "disyolo_confusion16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "disyolo_confusion_n": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p]),
     "disyolo_paste_job_size": (C.c_size_t, []),
@@ -1108,12 +1112,13 @@ def tile_compose_plan(boxes, member_start):
 
 
 def tile_compose(groups, members, inst_tile, origins, planes, size, image_hw, arena, owner, inst_tile_dev=None,
-                 origins_dev=None) -> None:
+                 origins_dev=None, groups_dev=None) -> None:
     """groups [G,8] (tile_compose_plan), members [M], inst_tile [N], origins [T,2]: host int32 tables (checked before the
-    launch); planes int32 CUDA [N,net_h,net_w/32]; arena uint8 CUDA; owner int32 CUDA [h,w] (disyolo_tile_compose)"""
+    launch; device copies may be passed in); planes int32 CUDA [N,net_h,net_w/32]; arena uint8 CUDA; owner int32 CUDA [h,w]
+    (disyolo_tile_compose)"""
     nh, nw = hw_of(size)
     dev = owner.device
-    groups, groups_d = _table(np.asarray(groups, np.int32).reshape(-1, 8), 8, "groups", None, dev)
+    groups, groups_d = _table(np.asarray(groups, np.int32).reshape(-1, 8), 8, "groups", groups_dev, dev)
     members, members_d = _table(members, 1, "members", None, dev)
     inst_tile, inst_tile_dev = _table(inst_tile, 1, "inst_tile", inst_tile_dev, dev)
     origins, origins_dev = _table(origins, 2, "origins", origins_dev, dev)
@@ -1129,6 +1134,66 @@ def tile_compose(groups, members, inst_tile, origins, planes, size, image_hw, ar
                                        _p(origins_dev), int(origins.shape[0]), _p(planes) if G else None, nh, nw,
                                        int(image_hw[0]), int(image_hw[1]), _p(arena) if G else None,
                                        int(arena.numel()) if G else 0, _p(owner), _stream()), "tile_compose")
+
+
+GROUP_COUNTS_CHUNK = 2048      # pixels of a pair's rectangle per block of disyolo_tile_group_counts (..._group_counts_blocks)
+GROUP_COUNTS_MAX_BLOCKS = 1024  # ... and the most blocks one pair gets: they stride over the chunks of a larger rectangle
+
+
+def tile_group_counts_plan(groups, gt, pairs2):
+    """groups int32 [G,8] (tile_compose_plan), gt int32 [ng,8] = y1, x1, y2, x2, classid, pitch, off, area, pairs2 int [P,2] =
+    (g, j) with j = -1 for the group's own pixel count -> (pairs int32 [P,3] = g, j, block0 as disyolo_tile_group_counts takes
+    them, the launch's block count).  A pair's rectangle is the group's box, cut to the instance's box for j >= 0; an empty one
+    takes one block."""
+    groups = np.asarray(groups, np.int64).reshape(-1, 8)
+    gt = np.asarray(gt, np.int64).reshape(-1, 8)
+    p2 = np.asarray(pairs2, np.int64).reshape(-1, 2)
+    P = int(p2.shape[0])
+    lib = load()
+    if ([lib.disyolo_tile_group_counts_blocks(a) for a in (GROUP_COUNTS_CHUNK, GROUP_COUNTS_CHUNK + 1, 1 << 40)]
+            != [1, 2, GROUP_COUNTS_MAX_BLOCKS]):
+        raise DisyoloError("tile_group_counts_plan: the library's chunk is not %d pixels in at most %d blocks: rebuild it" %
+                           (GROUP_COUNTS_CHUNK, GROUP_COUNTS_MAX_BLOCKS))
+    pairs = np.zeros((P, 3), np.int32)
+    if P == 0:
+        return pairs, 0
+    g, j = p2[:, 0], p2[:, 1]
+    if g.min() < 0 or g.max() >= groups.shape[0] or j.min() < -1 or j.max() >= gt.shape[0]:
+        raise DisyoloError("tile_group_counts_plan: a pair is out of range (%d groups, %d ground-truth instances)" %
+                           (groups.shape[0], gt.shape[0]))
+    box = groups[g, 2:6]
+    if gt.shape[0]:
+        other = gt[np.maximum(j, 0), :4]
+        own = (j < 0)[:, None]
+        box = np.where(own, box, np.concatenate([np.maximum(box[:, :2], other[:, :2]), np.minimum(box[:, 2:], other[:, 2:])], 1))
+    area = np.maximum(box[:, 2] - box[:, 0], 0) * np.maximum(box[:, 3] - box[:, 1], 0)
+    blocks = np.concatenate([[0], np.cumsum(np.clip((area + GROUP_COUNTS_CHUNK - 1) // GROUP_COUNTS_CHUNK, 1, GROUP_COUNTS_MAX_BLOCKS))])
+    if blocks[-1] >= 1 << 31:
+        raise DisyoloError("tile_group_counts_plan: the pairs' rectangles hold too many pixels for one launch")
+    pairs[:, 0], pairs[:, 1], pairs[:, 2] = g, j, blocks[:-1]
+    return pairs, int(blocks[-1])
+
+
+def tile_group_counts(groups, arena, gt, gt_bits, pairs, image_hw, groups_dev=None, gt_dev=None, pairs_dev=None,
+                      arena_bytes: Optional[int] = None):
+    """groups [G,8], gt [ng,8], pairs [P,3] (tile_group_counts_plan): host int32 tables (checked before the launch; their device
+    copies may be passed in); arena uint8 CUDA (what tile_compose wrote; ``arena_bytes`` of it, all by default); gt_bits uint32
+    bits as int32 CUDA -> counts int32 CUDA [P] (disyolo_tile_group_counts).  P = 0 or G = 0 launches nothing."""
+    dev = arena.device
+    groups, groups_dev = _table(np.asarray(groups, np.int32).reshape(-1, 8), 8, "groups", groups_dev, dev)
+    gt, gt_dev = _table(np.asarray(gt, np.int32).reshape(-1, 8), 8, "gt", gt_dev, dev)
+    pairs, pairs_dev = _table(np.asarray(pairs, np.int32).reshape(-1, 3), 3, "pairs", pairs_dev, dev)
+    G, ng, P = int(groups.shape[0]), int(gt.shape[0]), int(pairs.shape[0])
+    _need(arena, torch.uint8, "arena")
+    _need(gt_bits, torch.int32, "gt_bits")
+    nbytes = int(arena.numel()) if arena_bytes is None else int(arena_bytes)
+    if not 0 <= nbytes <= int(arena.numel()):
+        raise DisyoloError("tile_group_counts: arena_bytes = %d, the arena holds %d" % (nbytes, int(arena.numel())))
+    counts = torch.zeros(P, dtype=torch.int32, device=dev)
+    _check(load().disyolo_tile_group_counts(groups.ctypes.data, _p(groups_dev), G, _p(arena), nbytes, gt.ctypes.data, _p(gt_dev),
+                                            ng, _p(gt_bits), int(gt_bits.numel()), pairs.ctypes.data, _p(pairs_dev), P,
+                                            int(image_hw[0]), int(image_hw[1]), _p(counts), _stream()), "tile_group_counts")
+    return counts
 
 
 def polygon_mask(px, py, poly_start, poly_is_out, image_h: int, image_w: int, mask) -> None:

@@ -88,14 +88,19 @@ class TiledDetections:
       members   per group the (tile, row) of its detections
       mask(g)   bool CUDA view [y2-y1, x2-x1] of the group's mask cropped to its box; full_mask(g) bool CUDA [h,w]
       owner     int32 CUDA [h,w]: 0, or 1 + the rank of the LAST covering group; merged uint8 CUDA [h,w]: its class + 1
-      tiles     int32 [T,2] the plan;  inputs, tile_outputs: the tiles' net inputs and outputs when detect_tiled was asked to keep them"""
+      tiles     int32 [T,2] the plan;  inputs, tile_outputs: the tiles' net inputs and outputs when detect_tiled was asked to keep them
+      groups, groups_dev, arena, arena_bytes   the [G,8] table ``lib.tile_compose`` took (numpy and its CUDA copy), the arena
+                it wrote the cropped masks into and the bytes of it in use: what ``lib.tile_group_counts`` reads"""
 
-    def __init__(self, tiles, image_hw, boxes, classid, score, members, arena, offsets, owner, merged):
+    def __init__(self, tiles, image_hw, boxes, classid, score, members, arena, offsets, owner, merged, groups=None,
+                 groups_dev=None, arena_bytes=None):
         self.tiles, self.image_hw = tiles, (int(image_hw[0]), int(image_hw[1]))
         self.boxes, self.classid, self.score, self.members = boxes, classid, score, members
         self._arena, self._offsets = arena, offsets
         self.owner, self.merged = owner, merged
         self.inputs = self.tile_outputs = None
+        self.groups, self.groups_dev, self.arena = groups, groups_dev, arena
+        self.arena_bytes = int(arena.numel()) if arena_bytes is None else int(arena_bytes)
 
     def __len__(self) -> int:
         return int(self.boxes.shape[0])
@@ -222,14 +227,16 @@ def merge_tiles(tiles, image_hw, net_size, detections, keep, masks, merge_overla
     groups, arena_bytes = L.tile_compose_plan(boxes, start)
     arena = torch.empty(max(arena_bytes, 16), dtype=torch.uint8, device=dev)
     owner = torch.empty(h, w, dtype=torch.int32, device=dev)
-    L.tile_compose(groups, mem_flat, kt, tiles, planes, (H, W), (h, w), arena, owner, tile_d, origins_d)
+    groups_d = torch.from_numpy(groups).to(dev)
+    L.tile_compose(groups, mem_flat, kt, tiles, planes, (H, W), (h, w), arena, owner, tile_d, origins_d, groups_d)
     lut = torch.from_numpy(np.concatenate([[0], gcls + 1]).astype(np.uint8)).to(dev)
     merged = lut[owner.long()]
     if probe is not None:           # what each launch took, for tools/tiles_rate.py
         probe.update(instances=N, pairs=pairs, inst_tile=kt, planes=planes, groups=groups, members=mem_flat,
                      arena=arena, owner=owner, inst_tile_dev=tile_d, origins_dev=origins_d)
     offsets = [int(v) * 16 for v in groups[:, 7]]
-    return TiledDetections(tiles, (h, w), boxes, gcls, gscore[order], members, arena, offsets, owner, merged)
+    return TiledDetections(tiles, (h, w), boxes, gcls, gscore[order], members, arena, offsets, owner, merged, groups, groups_d,
+                           arena_bytes)
 
 
 def detect_tiled(net, image_rgb, overlap=64, det_thresh=cfg.OBJ_THRESHOLD, merge_overlap: float = 0.5,

@@ -172,6 +172,26 @@ def main():
             y1, x1, y2, x2 = res.boxes[g]
             print("  %s %.2f box (%d, %d)-(%d, %d), %d pixels, from tiles %s" % (
                 classes[res.classid[g]], res.score[g], y1, x1, y2, x2, int(res.mask(g).sum()), sorted({t for t, _ in res.members[g]})))
+        # the metric of the whole image against the records it was drawn from: every repeat of an instance is an instance
+        from disyolo_amd.evaluate import MAP, evaluate
+        from disyolo_amd.train_data import rasterize_instance
+        recs, true_map = [], np.zeros((th, tw), np.uint8)
+        for name, polys in zip(rec["class_names"], rec["polygons"]):
+            one = rasterize_instance(polys, h, w, dev).cpu().numpy() > 0
+            for y0 in range(0, th, h):
+                for x0 in range(0, tw, w):
+                    m = np.zeros((th, tw), bool)
+                    m[y0:y0 + h, x0:x0 + w] = one[:th - y0, :tw - x0]
+                    if m.any():
+                        recs.append({"imageid": "big", "classid": classes.index(name), "difficult": 0, "mask": m})
+                        true_map[m] = classes.index(name) + 1
+        big_map = MAP({"big": recs}, {"big": [th, tw]}, ["big"], merged={"big": true_map}, classes=classes)
+        thresh_out, mask_acc, timing = evaluate(inf, {"big": big}, big_map, det_thresh=0.05,
+                                                tiled={"overlap": (nh // 8, nw // 8), "merge_overlap": 0.5})
+        print("tiled evaluation against %d ground-truth instances: AP %s, (recall, precision, mAP) %s, mIoU %.3f; "
+              "detect_tiled %.1f ms, collect_tiled %.1f ms" % (
+                  len(recs), np.round(thresh_out[0]["AP"], 3).tolist(), np.round(thresh_out[0]["mAP"], 3).tolist(), mask_acc[-1],
+                  timing["prediction_s"] * 1e3, timing["crop_assemble_s"] * 1e3))
 
 
 if __name__ == "__main__":

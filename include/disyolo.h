@@ -648,6 +648,22 @@ int disyolo_tile_compose(const int32_t* groups_host, const int32_t* groups, int 
                          const int32_t* members, int M, const int32_t* inst_tile_host, const int32_t* inst_tile, int N,
                          const int32_t* origins_host, const int32_t* origins, int T, const uint32_t* planes, int net_h, int net_w,
                          int image_h, int image_w, uint8_t* arena, int64_t arena_bytes, int32_t* owner, void* stream);
+/* tiled evaluation: pixel counts of merged groups against ground truth kept as cropped bit planes (evaluate.MAP.collect_tiled;
+ * defined by tests/tiles_eval_ref.py).  groups int32 [G, 8] and arena (arena_bytes) are what disyolo_tile_compose took and
+ * wrote: group g's mask is bytes 0 / 1, row-major over its box, at arena + 16 * off16 (only columns 2 .. 5 and 7 are read; the
+ * padding behind a group's area is never counted).  gt int32 [ng, 8] = {y1, x1, y2, x2, classid, pitch, off, area}: instance
+ * j's plane is cropped to its box, pitch >= ceil((x2 - x1) / 32) words per row from word `off` of gt_bits (gt_words words);
+ * bit i of word k of row r is pixel (y1 + r, x1 + 32 k + i), bits past the box's last column are zero; classid and area are
+ * the caller's.  pairs int32 [P, 3] = {g, j, block0}: j >= 0 asks for |mask_g n gt_j|, j = -1 for the group's own pixel count;
+ * block0 = the sum of disyolo_tile_group_counts_blocks(area of the pair's rectangle) over the pairs before it, the rectangle
+ * being the group's box (j = -1) or box n gt box; an empty rectangle takes one block, a large one at most 1024, which stride
+ * over its 2048-pixel chunks.  counts int32 [P] is zeroed here, then
+ * integer atomicAdd of per-block popcounts: order-independent.  P = 0 or G = 0 launches nothing. */
+int disyolo_tile_group_counts_blocks(int64_t area);
+int disyolo_tile_group_counts(const int32_t* groups_host, const int32_t* groups, int G, const uint8_t* arena, int64_t arena_bytes,
+                              const int32_t* gt_host, const int32_t* gt, int ng, const uint32_t* gt_bits, int64_t gt_words,
+                              const int32_t* pairs_host, const int32_t* pairs, int P, int image_h, int image_w, int32_t* counts,
+                              void* stream);
 /* semantic-segmentation accuracy of evaluate (calculate_test_map.py:303-346): adds the 4x4 pixel
  * confusion counts of two uint8 class maps (0 = background, 1..3 = classes; other values are
  * ignored) to conf int64 [16], conf[true*4 + pred]; the caller zeroes conf before the first image
