@@ -9,6 +9,8 @@
 // Host code (train_data.py) only draws the random decisions and transforms the handful of boxes.
 // scikit-image's rasteriser is pinned by golden vectors (tests/golden/polygon.json); cv2 and pyblur are not
 // installable here: their arithmetic is restated from the libraries' documented behaviour -- unpinned.
+#include <climits>
+
 #include "common.h"
 #include "runtime.h"
 
@@ -232,6 +234,212 @@ __global__ __launch_bounds__(256) void to_float_kernel(const unsigned char* src,
     dst[i] = __fdiv_rn((float)src[i], 255.f);           // image.astype(float32) / 255.0 stays float32 in numpy
 }
 
+// ---- window training: a batch image is a net-size window of its record at scale 1 ---------------------------
+// the visible part of a job's instance: crop n window n image, in image coordinates (empty when x2 <= x1 or y2 <= y1)
+struct WinRect {
+  int x1, y1, x2, y2;
+};
+__device__ __forceinline__ WinRect window_rect(const disyolo_window_job& j, int net_h, int net_w) {
+  WinRect r;
+  r.x1 = max(max(j.crop_x, j.x0), 0);
+  r.y1 = max(max(j.crop_y, j.y0), 0);
+  r.x2 = min(min(j.crop_x + j.crop_w, j.x0 + net_w), j.image_w);
+  r.y2 = min(min(j.crop_y + j.crop_h, j.y0 + net_h), j.image_h);
+  return r;
+}
+constexpr int WIN_ROWS = 16;       // rows of a job's visible rect per block: a crack's crop as tall as the window takes net_h / 16 blocks
+
+__global__ void window_vis_init_kernel(int* vis, int njobs) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= njobs) return;
+  vis[5 * i] = 0; vis[5 * i + 1] = INT_MAX; vis[5 * i + 2] = INT_MAX; vis[5 * i + 3] = 0; vis[5 * i + 4] = 0;
+}
+__global__ void window_vis_finish_kernel(int* vis, int njobs) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= njobs) return;
+  if (vis[5 * i] == 0) vis[5 * i + 1] = vis[5 * i + 2] = 0;      // nothing visible: the box is zeros
+}
+
+// blockIdx.y = job, blockIdx.x = a group of WIN_ROWS rows of its visible rect.  Only bytes inside the rect are read, as aligned
+// 4-byte words where a whole word lies inside the row's segment.  Integer wave reductions, then one set of integer atomics
+// per block: sums, minima and maxima of integers do not depend on the order.
+__global__ __launch_bounds__(256) void window_visible_kernel(const disyolo_window_job* jobs, int net_h, int net_w, int* vis) {
+  const disyolo_window_job j = jobs[blockIdx.y];
+  const WinRect r = window_rect(j, net_h, net_w);
+  const int ya = r.y1 + (int)blockIdx.x * WIN_ROWS, yb = min(ya + WIN_ROWS, r.y2);
+  if (r.x2 <= r.x1 || ya >= yb) return;                          // (the same for every thread of the block)
+  const int width = r.x2 - r.x1, nslot = (width + 3) / 4 + 1;
+  int cnt = 0, xmin = INT_MAX, xmax = -1, ymin = INT_MAX, ymax = -1;
+  for (int i = threadIdx.x; i < (yb - ya) * nslot; i += blockDim.x) {
+    const int y = ya + i / nslot, k = i % nslot;
+    const unsigned char* lo = j.src + (size_t)(y - j.crop_y) * j.crop_w + (r.x1 - j.crop_x);
+    const uintptr_t a_lo = (uintptr_t)lo, a_hi = a_lo + width, wa = (a_lo & ~(uintptr_t)3) + 4 * (uintptr_t)k;
+    if (wa >= a_hi) continue;
+    unsigned word = 0;                                           // the word's bytes inside [lo, hi), others 0
+    if (wa >= a_lo && wa + 4 <= a_hi) {
+      word = *reinterpret_cast<const unsigned*>(wa);
+    } else {
+#pragma unroll
+      for (int t = 0; t < 4; ++t)
+        if (wa + t >= a_lo && wa + t < a_hi) word |= (unsigned)*reinterpret_cast<const unsigned char*>(wa + t) << (8 * t);
+    }
+    if (word == 0) continue;
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+      if ((word >> (8 * t)) & 0xffu) {
+        const int x = r.x1 + (int)((int64_t)(wa + t) - (int64_t)a_lo) - j.x0;   // window coordinates
+        ++cnt;
+        xmin = min(xmin, x); xmax = max(xmax, x);
+        ymin = min(ymin, y - j.y0); ymax = max(ymax, y - j.y0);
+      }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    cnt += __shfl_xor(cnt, o, 64);
+    xmin = min(xmin, __shfl_xor(xmin, o, 64)); ymin = min(ymin, __shfl_xor(ymin, o, 64));
+    xmax = max(xmax, __shfl_xor(xmax, o, 64)); ymax = max(ymax, __shfl_xor(ymax, o, 64));
+  }
+  __shared__ int part[4][5];
+  const int wave = threadIdx.x / DY_WAVE;
+  if (threadIdx.x % DY_WAVE == 0) {
+    part[wave][0] = cnt; part[wave][1] = xmin; part[wave][2] = ymin; part[wave][3] = xmax; part[wave][4] = ymax;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int w = 1; w < 4; ++w) {
+      cnt += part[w][0];
+      xmin = min(xmin, part[w][1]); ymin = min(ymin, part[w][2]);
+      xmax = max(xmax, part[w][3]); ymax = max(ymax, part[w][4]);
+    }
+    if (cnt > 0) {
+      int* v = vis + 5 * (size_t)blockIdx.y;
+      atomicAdd(v, cnt);
+      atomicMin(v + 1, xmin); atomicMin(v + 2, ymin);
+      atomicMax(v + 3, xmax + 1); atomicMax(v + 4, ymax + 1);
+    }
+  }
+}
+
+// blockIdx.y = which array: the four target arrays <- 0, rows <- -1; 16-byte stores between the unaligned ends
+struct WinClear {
+  unsigned* p[5];
+  int64_t n[5];
+};
+__global__ __launch_bounds__(256) void window_clear_kernel(WinClear c) {
+  unsigned* p = c.p[blockIdx.y];
+  const int64_t n = c.n[blockIdx.y];
+  const unsigned v = blockIdx.y == 4 ? 0xffffffffu : 0u;
+  int64_t head = (int64_t)((16 - ((uintptr_t)p & 15)) & 15) / 4;
+  if (head > n) head = n;
+  const int64_t quads = (n - head) / 4, tail = head + 4 * quads;
+  const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, step = (int64_t)gridDim.x * blockDim.x;
+  uint4* q = reinterpret_cast<uint4*>(p + head);
+  for (int64_t i = tid; i < quads; i += step) q[i] = make_uint4(v, v, v, v);
+  if (tid < head) p[tid] = v;
+  if (tid < n - tail) p[tail + tid] = v;
+}
+
+// ONE lane per image walks the image's jobs in order: the order defines the rows of true_boxes and which box keeps a
+// (cell, anchor) that two boxes fall into.  f32 arithmetic operation by operation as synth.assign_target_entries and
+// defect_train._fill do it in numpy (this file is compiled without contraction).
+__global__ void window_targets_kernel(const disyolo_window_job* jobs, int njobs, const int* vis, const float* anchors, int B, int G,
+                                      int C, int net_h, int net_w, int min_visible, float* true_boxes, float* yolo3, float* yolo2,
+                                      float* yolo1, int* rows) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  float ahw[9][2], a_area[9];
+  for (int k = 0; k < 9; ++k) {
+    ahw[k][0] = __fmul_rn(anchors[2 * k], 0.5f);
+    ahw[k][1] = __fmul_rn(anchors[2 * k + 1], 0.5f);
+    a_area[k] = __fmul_rn(__fmul_rn(ahw[k][0], ahw[k][1]), 4.f);
+  }
+  const float fw = (float)net_w, fh = (float)net_h;
+  int r = 0;
+  for (int i = 0; i < njobs; ++i) {
+    if (jobs[i].b != b) continue;
+    const int flip = jobs[i].flip, cls = jobs[i].cls;
+    const int* v = vis + 5 * (size_t)i;
+    // the loader's clamp of each coordinate to [0, net - 1] (sx = sy = 1, dx = dy = 0)
+    const int x1 = max(min(v[1], net_w - 1), 0), y1 = max(min(v[2], net_h - 1), 0);
+    const int x2 = max(min(v[3], net_w - 1), 0), y2 = max(min(v[4], net_h - 1), 0);
+    if (v[0] < min_visible || x2 - x1 <= 0 || y2 - y1 <= 0 || r >= G) {
+      rows[i] = -1;
+      continue;
+    }
+    rows[i] = r;
+    const float xc = __fmul_rn((float)(x1 + x2), 0.5f), yc = __fmul_rn((float)(y1 + y2), 0.5f);    // integers or halves: exact
+    const float w = (float)(x2 - x1), h = (float)(y2 - y1);
+    const float xcf = flip == 2 ? __fsub_rn((float)(net_w - 1), xc) : xc, ycf = flip == 3 ? __fsub_rn((float)(net_h - 1), yc) : yc;
+    const float out[4] = {__fdiv_rn(xcf, fw), __fdiv_rn(ycf, fh), __fdiv_rn(w, fw), __fdiv_rn(h, fh)};
+    float* tb = true_boxes + ((size_t)b * G + r) * 5;
+    tb[0] = out[0]; tb[1] = out[1]; tb[2] = out[2]; tb[3] = out[3]; tb[4] = (float)cls;
+    ++r;
+    // best of the nine anchors, boxes centred at the origin
+    const float hw = __fmul_rn(w, 0.5f), hh = __fmul_rn(h, 0.5f);
+    const float area = __fmul_rn(__fmul_rn(hw, hh), 4.f);
+    float best = 0.f;
+    int idx = 0;
+    for (int k = 0; k < 9; ++k) {
+      const float iw = fmaxf(__fmul_rn(2.f, fminf(hw, ahw[k][0])), 0.f), ih = fmaxf(__fmul_rn(2.f, fminf(hh, ahw[k][1])), 0.f);
+      const float ia = __fmul_rn(iw, ih);
+      const float iou = __fdiv_rn(ia, __fsub_rn(__fadd_rn(area, a_area[k]), ia));
+      if (k == 0 || iou > best) { best = iou; idx = k; }         // the first maximum, like argmax
+    }
+    if (!(best > 0.f)) continue;                                 // the box row stays, no cell
+    const int s = idx / 3, a = idx - 3 * s, d = 8 << s;
+    const int gh = net_h / d, gw = net_w / d;
+    // int(xc * gw / net_w): gw / net_w = 1 / d and xc is a multiple of 1/2, so the quotient is exact in any precision
+    int xi = min((x1 + x2) / (2 * d), gw - 1), yi = min((y1 + y2) / (2 * d), gh - 1);
+    if (flip == 2) xi = gw - 1 - xi;
+    if (flip == 3) yi = gh - 1 - yi;
+    float* grid = s == 0 ? yolo3 : (s == 1 ? yolo2 : yolo1);
+    float* cell = grid + ((((size_t)b * gh + yi) * gw + xi) * 3 + a) * (size_t)(5 + C);
+    if (cell[4] != 0.f) continue;                                // an occupied (cell, anchor) keeps its first box
+    cell[0] = out[0]; cell[1] = out[1]; cell[2] = out[2]; cell[3] = out[3]; cell[4] = 1.f;
+    if (cls >= 0 && cls < C) cell[5 + cls] = 1.f;
+  }
+}
+
+// blockIdx.y = job, blockIdx.x = a group of WIN_ROWS rows of its visible rect; one thread per aligned 4-byte word of the
+// destination row: a word that lies inside the row's segment and whose four source bytes are aligned too moves as one word
+// (byte-swapped for the horizontal flip), everything else byte by byte
+__global__ __launch_bounds__(256) void window_place_masks_kernel(const disyolo_window_job* jobs, const int* rows,
+                                                                 unsigned char* true_masks, int G, int net_h, int net_w) {
+  const int row = rows[blockIdx.y];
+  if (row < 0 || row >= G) return;
+  const disyolo_window_job j = jobs[blockIdx.y];
+  const WinRect r = window_rect(j, net_h, net_w);
+  const int ya = r.y1 + (int)blockIdx.x * WIN_ROWS, yb = min(ya + WIN_ROWS, r.y2);
+  if (r.x2 <= r.x1 || ya >= yb || j.b < 0) return;
+  unsigned char* plane = true_masks + ((size_t)j.b * G + row) * net_h * net_w;
+  const int wx1 = r.x1 - j.x0, wx2 = r.x2 - j.x0;                // window columns [wx1, wx2)
+  const int dlo = j.flip == 2 ? net_w - wx2 : wx1, dhi = j.flip == 2 ? net_w - wx1 : wx2;
+  const int nslot = (dhi - dlo + 3) / 4 + 1;
+  for (int i = threadIdx.x; i < (yb - ya) * nslot; i += blockDim.x) {
+    const int y = ya + i / nslot, k = i % nslot;
+    const int wy = y - j.y0;
+    unsigned char* drow = plane + (size_t)(j.flip == 3 ? net_h - 1 - wy : wy) * net_w;
+    // source byte of window column wx: srow[wx - wx1]
+    const unsigned char* srow = j.src + (size_t)(y - j.crop_y) * j.crop_w + (r.x1 - j.crop_x);
+    const uintptr_t d_lo = (uintptr_t)(drow + dlo), d_hi = (uintptr_t)(drow + dhi), wa = (d_lo & ~(uintptr_t)3) + 4 * (uintptr_t)k;
+    if (wa >= d_hi) continue;
+    const int c0 = dlo + (int)((int64_t)wa - (int64_t)d_lo);     // destination column of the word's first byte
+    if (wa >= d_lo && wa + 4 <= d_hi) {
+      const unsigned char* s4 = j.flip == 2 ? srow + (net_w - 1 - (c0 + 3) - wx1) : srow + (c0 - wx1);
+      if (((uintptr_t)s4 & 3) == 0) {
+        const unsigned word = *reinterpret_cast<const unsigned*>(s4);
+        *reinterpret_cast<unsigned*>(wa) = j.flip == 2 ? __builtin_bswap32(word) : word;
+        continue;
+      }
+    }
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      const int c = c0 + t;
+      if (c >= dlo && c < dhi) drow[c] = srow[(j.flip == 2 ? net_w - 1 - c : c) - wx1];
+    }
+  }
+}
+
 int grid_for(int64_t n) {
   int64_t g = (n + 255) / 256;
   if (g > 256 * 16) g = 256 * 16;
@@ -336,6 +544,68 @@ extern "C" int disyolo_aug_motion_blur3_hw(const uint8_t* src, uint8_t* dst, int
   // a convolution flips the kernel: the tap at kernel offset (+dy,+dx) reads the pixel at (-dy,-dx)
   hipLaunchKernelGGL(motion_blur3_kernel, dim3(grid_for((int64_t)net_h * net_w)), dim3(256), 0, (hipStream_t)stream, src, dst, net_h,
                      net_w, -dyA, -dxA, use_a, use_b);
+  DY_CHECK_LAUNCH();
+  return DISYOLO_OK;
+}
+
+extern "C" size_t disyolo_window_job_size(void) { return sizeof(disyolo_window_job); }
+
+extern "C" int disyolo_window_visible(const disyolo_window_job* jobs, int njobs, int net_h, int net_w, int32_t* vis, void* stream) {
+  DY_REQUIRE(njobs >= 0 && njobs <= 65535 && net_h > 0 && net_w > 0, "window_visible: bad args (0 <= njobs <= 65535, net_h, net_w > 0)");
+  DY_REQUIRE(njobs == 0 || (jobs && vis), "window_visible: null jobs / vis");
+  DY_RECORD_OR_RUN([=](void* s) { return disyolo_window_visible(jobs, njobs, net_h, net_w, vis, s); });
+  if (njobs == 0) return DISYOLO_OK;
+  const int gj = (njobs + 255) / 256;
+  hipLaunchKernelGGL(window_vis_init_kernel, dim3(gj), dim3(256), 0, (hipStream_t)stream, vis, njobs);
+  hipLaunchKernelGGL(window_visible_kernel, dim3((net_h + WIN_ROWS - 1) / WIN_ROWS, njobs), dim3(256), 0, (hipStream_t)stream, jobs,
+                     net_h, net_w, vis);
+  hipLaunchKernelGGL(window_vis_finish_kernel, dim3(gj), dim3(256), 0, (hipStream_t)stream, vis, njobs);
+  DY_CHECK_LAUNCH();
+  return DISYOLO_OK;
+}
+
+extern "C" int disyolo_window_targets(const disyolo_window_job* jobs, int njobs, const int32_t* vis, const float* anchors, int B, int G,
+                                      int C, int net_h, int net_w, int min_visible, float* true_boxes, float* yolo3, float* yolo2,
+                                      float* yolo1, int32_t* rows, void* stream) {
+  DY_REQUIRE(njobs >= 0 && njobs <= 65535 && B > 0, "window_targets: bad args (0 <= njobs <= 65535, B > 0)");
+  DY_REQUIRE(G >= 1 && G <= DISYOLO_MAX_BOXES, "window_targets: G = %d, need 1 .. %d", G, DISYOLO_MAX_BOXES);
+  DY_REQUIRE(C >= 1 && C <= 80, "window_targets: C = %d, need 1 .. 80", C);
+  DY_REQUIRE(net_h > 0 && net_w > 0 && net_h % 32 == 0 && net_w % 32 == 0,
+             "window_targets: the net's sides must be positive multiples of 32 (got %d x %d)", net_h, net_w);
+  DY_REQUIRE(min_visible >= 1, "window_targets: min_visible = %d, need >= 1", min_visible);
+  DY_REQUIRE(anchors && true_boxes && yolo3 && yolo2 && yolo1, "window_targets: null anchors / outputs");
+  DY_REQUIRE(njobs == 0 || (jobs && vis && rows), "window_targets: null jobs / vis / rows");
+  DY_RECORD_OR_RUN([=](void* s) {
+    return disyolo_window_targets(jobs, njobs, vis, anchors, B, G, C, net_h, net_w, min_visible, true_boxes, yolo3, yolo2, yolo1, rows, s);
+  });
+  WinClear c;
+  float* out[4] = {true_boxes, yolo3, yolo2, yolo1};
+  int64_t biggest = 0;
+  for (int k = 0; k < 4; ++k) {
+    const int d = 4 << k;                                        // (k = 1, 2, 3: the grids at net / 8, 16, 32)
+    c.p[k] = reinterpret_cast<unsigned*>(out[k]);
+    c.n[k] = k == 0 ? (int64_t)B * G * 5 : (int64_t)B * (net_h / d) * (net_w / d) * 3 * (5 + C);
+    if (c.n[k] > biggest) biggest = c.n[k];
+  }
+  c.p[4] = reinterpret_cast<unsigned*>(rows);
+  c.n[4] = njobs;
+  hipLaunchKernelGGL(window_clear_kernel, dim3(grid_for(biggest / 4 + 8), 5), dim3(256), 0, (hipStream_t)stream, c);
+  if (njobs > 0)
+    hipLaunchKernelGGL(window_targets_kernel, dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)stream, jobs, njobs, (const int*)vis,
+                       anchors, B, G, C, net_h, net_w, min_visible, true_boxes, yolo3, yolo2, yolo1, (int*)rows);
+  DY_CHECK_LAUNCH();
+  return DISYOLO_OK;
+}
+
+extern "C" int disyolo_window_place_masks(const disyolo_window_job* jobs, int njobs, const int32_t* rows, uint8_t* true_masks, int G,
+                                          int net_h, int net_w, void* stream) {
+  DY_REQUIRE(njobs >= 0 && njobs <= 65535 && net_h > 0 && net_w > 0, "window_place_masks: bad args (0 <= njobs <= 65535, net_h, net_w > 0)");
+  DY_REQUIRE(G >= 1 && G <= DISYOLO_MAX_BOXES, "window_place_masks: G = %d, need 1 .. %d", G, DISYOLO_MAX_BOXES);
+  DY_REQUIRE(njobs == 0 || (jobs && rows && true_masks), "window_place_masks: null jobs / rows / true_masks");
+  DY_RECORD_OR_RUN([=](void* s) { return disyolo_window_place_masks(jobs, njobs, rows, true_masks, G, net_h, net_w, s); });
+  if (njobs == 0) return DISYOLO_OK;
+  hipLaunchKernelGGL(window_place_masks_kernel, dim3((net_h + WIN_ROWS - 1) / WIN_ROWS, njobs), dim3(256), 0, (hipStream_t)stream, jobs,
+                     (const int*)rows, true_masks, G, net_h, net_w);
   DY_CHECK_LAUNCH();
   return DISYOLO_OK;
 }

@@ -257,6 +257,10 @@ _SIGS = {
     "disyolo_aug_change_light_hw": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_void_p]),
     "disyolo_aug_motion_blur3_hw": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "disyolo_aug_to_float": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "disyolo_window_job_size": (C.c_size_t, []),
+    "disyolo_window_visible": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "disyolo_window_targets": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p] * 6),
+    "disyolo_window_place_masks": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "disyolo_crc32c": (C.c_uint32, [C.c_void_p, C.c_size_t, C.c_uint32]),
     "disyolo_l2_workspace": (C.c_size_t, [C.c_int64]),
     "disyolo_l2_loss": (C.c_int, [C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
@@ -285,6 +289,9 @@ def load() -> C.CDLL:
         if lib.disyolo_paste_job_size() != PASTE_JOB.itemsize:
             raise DisyoloError("%s was built from a different include/disyolo.h (paste job %d bytes, this binding %d): "
                                "rebuild it" % (LIB_PATH, lib.disyolo_paste_job_size(), PASTE_JOB.itemsize))
+        if lib.disyolo_window_job_size() != WINDOW_JOB.itemsize:
+            raise DisyoloError("%s was built from a different include/disyolo.h (window job %d bytes, this binding %d): "
+                               "rebuild it" % (LIB_PATH, lib.disyolo_window_job_size(), WINDOW_JOB.itemsize))
         _lib = lib
     return _lib
 
@@ -1230,6 +1237,71 @@ def aug_place_batch(jobs_dev, njobs: int, size) -> None:
         raise DisyoloError("aug_place_batch: %d jobs do not fit %d bytes" % (njobs, jobs_dev.numel()))
     nh, nw = hw_of(size)
     _check(load().disyolo_aug_place_batch_hw(_p(jobs_dev), njobs, nh, nw, _stream()), "aug_place_batch")
+
+
+WINDOW_JOB = np.dtype([("src", np.uint64), ("crop_h", np.int32), ("crop_w", np.int32), ("crop_x", np.int32), ("crop_y", np.int32),
+                       ("x0", np.int32), ("y0", np.int32), ("image_h", np.int32), ("image_w", np.int32), ("b", np.int32),
+                       ("cls", np.int32), ("flip", np.int32), ("reserved", np.int32)])
+assert WINDOW_JOB.itemsize == 56     # (disyolo_window_job, include/disyolo.h)
+
+
+def _window_jobs(jobs_dev, njobs: int, what: str) -> int:
+    _need(jobs_dev, torch.uint8, "jobs")
+    njobs = int(njobs)
+    if njobs < 0 or jobs_dev.numel() < njobs * WINDOW_JOB.itemsize:
+        raise DisyoloError("%s: %d jobs do not fit %d bytes" % (what, njobs, jobs_dev.numel()))
+    return njobs
+
+
+def window_visible(jobs_dev, njobs: int, size, vis) -> None:
+    """jobs_dev: uint8 CUDA tensor holding njobs WINDOW_JOB records; vis int32 CUDA [>= njobs, 5] <- (count, x1, y1, x2, y2) of
+    every job's visible part, in window coordinates (disyolo_window_visible)"""
+    njobs = _window_jobs(jobs_dev, njobs, "window_visible")
+    _need(vis, torch.int32, "vis")
+    if vis.dim() != 2 or vis.shape[1] != 5 or vis.shape[0] < njobs:
+        raise DisyoloError("window_visible: vis must be int32 [>= %d, 5] (got %s)" % (njobs, tuple(vis.shape)))
+    nh, nw = hw_of(size)
+    _check(load().disyolo_window_visible(_p(jobs_dev), njobs, nh, nw, _p(vis), _stream()), "window_visible")
+
+
+def window_targets(jobs_dev, njobs: int, vis, anchors, size, min_visible: int, true_boxes, yolo3, yolo2, yolo1, rows) -> None:
+    """the target arrays of a window batch from ``window_visible``'s table (disyolo_window_targets): true_boxes f32 CUDA
+    [B,1,1,1,G,5] (or [B,G,5]), yolo3 / yolo2 / yolo1 f32 CUDA [B, net_h/d, net_w/d, 3, 5+C], all zeroed and filled; rows int32
+    CUDA [>= njobs] <- each job's row of true_boxes, or -1; anchors f32 CUDA [9,2]"""
+    njobs = _window_jobs(jobs_dev, njobs, "window_targets")
+    nh, nw = hw_of(size)
+    _need(vis, torch.int32, "vis")
+    _need(rows, torch.int32, "rows")
+    _need(anchors, torch.float32, "anchors")
+    _need_shape(anchors, (9, 2), "anchors")
+    for t, name in ((true_boxes, "true_boxes"), (yolo3, "yolo3"), (yolo2, "yolo2"), (yolo1, "yolo1")):
+        _need(t, torch.float32, name)
+    if vis.dim() != 2 or vis.shape[1] != 5 or vis.shape[0] < njobs or rows.numel() < njobs:
+        raise DisyoloError("window_targets: vis must be int32 [>= %d, 5] and rows hold %d entries" % (njobs, njobs))
+    if true_boxes.dim() not in (3, 6) or true_boxes.shape[-1] != 5 or true_boxes.numel() != true_boxes.shape[0] * true_boxes.shape[-2] * 5:
+        raise DisyoloError("window_targets: true_boxes must be [B,1,1,1,G,5] or [B,G,5] (got %s)" % (tuple(true_boxes.shape),))
+    B, G = int(true_boxes.shape[0]), int(true_boxes.shape[-2])
+    if yolo3.dim() != 5:
+        raise DisyoloError("window_targets: yolo3 must be [B, net_h/8, net_w/8, 3, 5+C] (got %s)" % (tuple(yolo3.shape),))
+    nc = int(yolo3.shape[-1]) - 5
+    for t, d, name in ((yolo3, 8, "yolo3"), (yolo2, 16, "yolo2"), (yolo1, 32, "yolo1")):
+        _need_shape(t, (B, nh // d, nw // d, 3, 5 + nc), name)
+    _check(load().disyolo_window_targets(_p(jobs_dev), njobs, _p(vis), _p(anchors), B, G, nc, nh, nw, int(min_visible),
+                                         _p(true_boxes), _p(yolo3), _p(yolo2), _p(yolo1), _p(rows), _stream()), "window_targets")
+
+
+def window_place_masks(jobs_dev, njobs: int, rows, true_masks, size) -> None:
+    """true_masks uint8 CUDA [B,G,net_h,net_w] (zeroed by the caller): the visible bytes of every job with rows[job] >= 0 into
+    plane [b, rows[job]], flipped (disyolo_window_place_masks)"""
+    njobs = _window_jobs(jobs_dev, njobs, "window_place_masks")
+    nh, nw = hw_of(size)
+    _need(rows, torch.int32, "rows")
+    _need(true_masks, torch.uint8, "true_masks")
+    if true_masks.dim() != 4 or tuple(true_masks.shape[2:]) != (nh, nw) or rows.numel() < njobs:
+        raise DisyoloError("window_place_masks: true_masks must be [B,G,%d,%d] and rows hold %d entries (got %s)"
+                           % (nh, nw, njobs, tuple(true_masks.shape)))
+    _check(load().disyolo_window_place_masks(_p(jobs_dev), njobs, _p(rows), _p(true_masks), int(true_masks.shape[1]), nh, nw,
+                                             _stream()), "window_place_masks")
 
 
 def aug_salt_pepper(image, size, rows, cols, nsalt: int, npepper: int) -> None:

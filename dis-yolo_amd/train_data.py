@@ -21,6 +21,13 @@ it, records beyond the budget are recomputed per visit as before.  With it ``get
 target grids kept sparse on the host (a dozen rows in 5 MB of zeros) and uploaded from pinned staging, and all placements of a batch (images and instance masks) in one launch: 7.5 -> 1.4 ms per batch of 8
 at 576^2; ``Solver.train`` end to end 630 -> 2100 images/s in stage 1 (the step's own rate), 806 in stage 2 (the step: 833)
 (``tools/solver_rate.py``).
+
+``placement="window"`` (the reference has nothing like it): every batch image is a net-size window of its record at
+scale 1, the training counterpart of ``tiles.detect_tiled``.  The host draws the window's origin; which instances the window keeps,
+their boxes and the three target grids come from the visible pixels and are computed on the GPU (window_visible, window_targets,
+window_place_masks of ``csrc/augment.hip``), so ``get_device()`` still has no host synchronisation and ``get()`` downloads the
+four small arrays with one.  The record cache keeps each instance's mask cropped to its static box.  tests/window_ref.py is the
+definition.
 """
 from __future__ import annotations
 
@@ -36,11 +43,17 @@ from . import lib as L
 from .synth import assign_target_entries
 
 
-def rasterize_instance(polys: Sequence[Dict], image_h: int, image_w: int, device, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+def rasterize_instance(polys: Sequence[Dict], image_h: int, image_w: int, device, out: Optional[torch.Tensor] = None,
+                       origin=(0, 0)) -> torch.Tensor:
     """``load_mask`` for one instance (utils/train_data.py:325-336) on the GPU: polys = [{'type': 'out'|'in',
-    'all_points_x': [...], 'all_points_y': [...]}] -> uint8 CUDA [image_h, image_w]"""
+    'all_points_x': [...], 'all_points_y': [...]}] -> uint8 CUDA [image_h, image_w].  ``origin`` = (x, y), integers: the
+    raster's pixel (0, 0) is the image's pixel (x, y) -- with ``image_h`` / ``image_w`` the crop's size this rasterises a crop
+    of the instance without the full-size mask (the kernel works on vertex - pixel, so an integer shift changes no pixel)."""
     xs = np.concatenate([np.asarray(p["all_points_x"], np.float32) for p in polys]) if polys else np.zeros(0, np.float32)
     ys = np.concatenate([np.asarray(p["all_points_y"], np.float32) for p in polys]) if polys else np.zeros(0, np.float32)
+    if tuple(origin) != (0, 0):
+        xs = (xs.astype(np.float64) - int(origin[0])).astype(np.float32)
+        ys = (ys.astype(np.float64) - int(origin[1])).astype(np.float32)
     start = np.cumsum([0] + [len(p["all_points_x"]) for p in polys]).astype(np.int32)
     is_out = np.asarray([1 if p["type"] == "out" else 0 for p in polys], np.int32)
     if out is None:
@@ -51,6 +64,50 @@ def rasterize_instance(polys: Sequence[Dict], image_h: int, image_w: int, device
     L.polygon_mask(torch.from_numpy(xs).to(device), torch.from_numpy(ys).to(device), torch.from_numpy(start).to(device),
                    torch.from_numpy(is_out).to(device), image_h, image_w, out)
     return out
+
+
+def static_box(polys: Sequence[Dict], image_h: int, image_w: int):
+    """(x1, y1, x2, y2) of an instance from its annotation alone: the min and the max + 1 of its polygons' vertices, clipped to
+    the image (every pixel ``rasterize_instance`` sets lies inside it); x2 <= x1 or y2 <= y1 when nothing of it is in the
+    image.  Host arithmetic: no raster, no synchronisation."""
+    if not polys or not any(len(p["all_points_x"]) for p in polys):
+        return 0, 0, 0, 0
+    xs = np.concatenate([np.asarray(p["all_points_x"], np.float64) for p in polys])
+    ys = np.concatenate([np.asarray(p["all_points_y"], np.float64) for p in polys])
+    return (max(int(math.floor(xs.min())), 0), max(int(math.floor(ys.min())), 0),
+            min(int(math.ceil(xs.max())) + 1, int(image_w)), min(int(math.ceil(ys.max())) + 1, int(image_h)))
+
+
+WINDOW_CANDIDATES = 256      # instances of a record a window looks at: the first 256 whose static box meets it
+
+
+def window_candidates(boxes, x0: int, y0: int, net_h: int, net_w: int) -> List[int]:
+    """the indices of the static boxes (x1, y1, x2, y2) that meet the window [x0, x0 + net_w) x [y0, y0 + net_h), in order,
+    the first WINDOW_CANDIDATES of them"""
+    out = []
+    for i, (x1, y1, x2, y2) in enumerate(boxes):
+        if x1 < x0 + net_w and x2 > x0 and y1 < y0 + net_h and y2 > y0:
+            out.append(i)
+            if len(out) == WINDOW_CANDIDATES:
+                break
+    return out
+
+
+def draw_window(rng, boxes, image_h: int, image_w: int, net_h: int, net_w: int, positive_fraction: float) -> Dict:
+    """the window draws of one image, in this order: u = uniform(); with instances and u < positive_fraction an
+    instance j, a point (px, py) of its static box and where in the window that point falls (ox, oy); otherwise the origin
+    itself, x then y.  ``boxes``: the record's static boxes (the non-empty ones).  Returns x0, y0 (and what was drawn)."""
+    max_x, max_y = max(image_w - net_w, 0), max(image_h - net_h, 0)
+    u = rng.uniform()
+    if len(boxes) and u < positive_fraction:
+        j = int(rng.randint(0, len(boxes)))
+        bx1, by1, bx2, by2 = boxes[j]
+        px, py = int(rng.randint(bx1, bx2)), int(rng.randint(by1, by2))
+        ox, oy = int(rng.randint(0, net_w)), int(rng.randint(0, net_h))
+        return {"x0": min(max(px - ox, 0), max_x), "y0": min(max(py - oy, 0), max_y), "instance": j, "point": (px, py)}
+    x0 = int(rng.randint(0, max_x + 1))
+    y0 = int(rng.randint(0, max_y + 1))
+    return {"x0": x0, "y0": y0, "instance": None, "point": None}
 
 
 def extract_bboxes(mask: torch.Tensor):
@@ -136,7 +193,19 @@ class defect_train(object):
     def __init__(self, labels: List[Dict], batch_size: Optional[int] = None, image_size=None, device=None,
                  rng: Optional[np.random.RandomState] = None, flipped: Optional[bool] = None,
                  blur_noise_light: Optional[bool] = None, cache_bytes: int = 16 << 30,
-                 classes: Optional[Sequence[str]] = None, anchors=None, max_box_per_image: Optional[int] = None):
+                 classes: Optional[Sequence[str]] = None, anchors=None, max_box_per_image: Optional[int] = None,
+                 placement: str = "letterbox", min_visible: int = 8, positive_fraction: float = 1.0):
+        # placement: "letterbox" = the reference's loader (the whole record fitted into the net); "window" = each batch image
+        # a net-size window of its record at scale 1: min_visible = the visible pixels an instance needs to be
+        # kept, positive_fraction = the share of windows drawn around a point of an instance (the rest anywhere in the image)
+        if placement not in ("letterbox", "window"):
+            raise ValueError("placement must be 'letterbox' or 'window' (got %r)" % (placement,))
+        if isinstance(min_visible, bool) or not isinstance(min_visible, (int, np.integer)) or min_visible < 1:
+            raise ValueError("min_visible must be an int >= 1 (got %r)" % (min_visible,))
+        if isinstance(positive_fraction, bool) or not isinstance(positive_fraction, (int, float, np.integer, np.floating)) \
+                or not 0.0 <= float(positive_fraction) <= 1.0:
+            raise ValueError("positive_fraction must be a number in [0, 1] (got %r)" % (positive_fraction,))
+        self.placement, self.min_visible, self.positive_fraction = placement, int(min_visible), float(positive_fraction)
         self.batch_size = cfg.BATCH_SIZE if batch_size is None else batch_size
         # image_size: an int S or a pair (net_h, net_w), like YOLONet's; the attribute keeps the caller's form
         from .net import check_image_size
@@ -187,8 +256,25 @@ class defect_train(object):
         self._frames = torch.zeros(B, NH, NW, 3, dtype=torch.uint8, device=dev)
         self._blur = torch.zeros(NH, NW, 3, dtype=torch.uint8, device=dev)
         njob = B * (1 + G)
-        self._jobs_host = [torch.zeros(njob * L.PLACE_JOB.itemsize, dtype=torch.uint8, pin_memory=dev.type == "cuda") for _ in range(2)]
-        self._jobs_dev = [torch.zeros(njob * L.PLACE_JOB.itemsize, dtype=torch.uint8, device=dev) for _ in range(2)]
+        job_bytes = njob * L.PLACE_JOB.itemsize
+        if placement == "window":
+            # the B image placements, then the window jobs (one per image and candidate instance) in the same staging: one
+            # upload; the visible-part table and the jobs' rows stay on the device, and so do the four target arrays (the
+            # clip windows never change: uploaded here, once)
+            job_bytes = B * L.PLACE_JOB.itemsize + B * WINDOW_CANDIDATES * L.WINDOW_JOB.itemsize
+            self._vis = torch.zeros(B * WINDOW_CANDIDATES, 5, dtype=torch.int32, device=dev)
+            self._rows = torch.zeros(B * WINDOW_CANDIDATES, dtype=torch.int32, device=dev)
+            self._anchors_dev = torch.from_numpy(self.anchors).to(dev)
+            for st, d in zip(self._host, self._dev):
+                d[4].copy_(st[4])
+        # the salt-and-pepper coordinates of a batch (rows, cols per image) go through pinned staging too: an upload from
+        # pageable memory waits for the stream, and get_device() must only enqueue
+        n_el = NH * NW * 3
+        n_sp = int(math.ceil(0.004 * n_el * 0.2)) + int(math.ceil(0.004 * n_el * 0.8))
+        self._sp_host = [torch.zeros(B, 2, n_sp, dtype=torch.int32, pin_memory=cuda) for _ in range(2)]
+        self._sp_dev = [torch.zeros(B, 2, n_sp, dtype=torch.int32, device=dev) for _ in range(2)]
+        self._jobs_host = [torch.zeros(job_bytes, dtype=torch.uint8, pin_memory=dev.type == "cuda") for _ in range(2)]
+        self._jobs_dev = [torch.zeros(job_bytes, dtype=torch.uint8, device=dev) for _ in range(2)]
         self.last_decisions: List[Dict] = []                   # the random draws of the last get(), for tests / logging
         # per-record static part (image on the GPU, instance masks, boxes, classes), keyed by the record object
         self.cache_bytes = int(cache_bytes)
@@ -225,9 +311,16 @@ class defect_train(object):
         return entry
 
     def get(self):
-        """the reference's tuple: (images, true_masks) on the GPU, (true_boxes, yolo_3, yolo_2, yolo_1, window) numpy"""
+        """the reference's tuple: (images, true_masks) on the GPU, (true_boxes, yolo_3, yolo_2, yolo_1, window) numpy.  In
+        window mode the host never has the boxes and grids (they come from the visible pixels): this call downloads the four
+        arrays, with ONE synchronisation; a training loop takes ``get_device()``, which has none."""
         self._fill()
         h = self._host[self._last]
+        if self.placement == "window":
+            small = [t.numpy() for t in torch.cat([d.reshape(-1) for d in self._dev[self._last][:4]]).cpu().split(
+                [d.numel() for d in self._dev[self._last][:4]])]
+            small = [a.reshape(d.shape) for a, d in zip(small, self._dev[self._last][:4])]
+            return (self.images, self.true_masks.view(torch.bool), small[0], small[1], small[2], small[3], h[4].numpy())
         return (self.images, self.true_masks.view(torch.bool), h[0].numpy(), h[1].numpy(), h[2].numpy(), h[3].numpy(), h[4].numpy())
 
     def get_device(self) -> Dict[str, torch.Tensor]:
@@ -239,7 +332,143 @@ class defect_train(object):
         return {"images": self.images, "true_masks": self.true_masks.view(torch.bool), "true_boxes": d[0], "yolo3": d[1],
                 "yolo2": d[2], "yolo1": d[3], "clip_window": d[4]}
 
+    def _record_window(self, label):
+        """the static part of a record in window mode: (image_h, image_w, image uint8 on the GPU, per instance with a
+        non-empty static box its byte mask CROPPED to that box (rasterised once, with the vertices shifted by the crop's
+        origin), the static boxes [(x1, y1, x2, y2)], the class indices).  Nothing full-size per instance is kept, no box is
+        fetched from the device, and the record is not cut to its first max_box_per_image instances."""
+        hit = self._cache.get(id(label))
+        if hit is not None:
+            return hit[1]
+        dev = self.device
+        image = self._image(label)
+        image_h, image_w = image.shape[:2]
+        crops, boxes, cls = [], [], []
+        for polys, name in zip(label["polygons"], label["class_names"]):
+            x1, y1, x2, y2 = static_box(polys, image_h, image_w)
+            if x2 <= x1 or y2 <= y1:
+                continue
+            crops.append(rasterize_instance(polys, y2 - y1, x2 - x1, dev, origin=(x1, y1)))
+            boxes.append((x1, y1, x2, y2))
+            cls.append(self.class_to_ind[name])
+        src = torch.from_numpy(np.ascontiguousarray(image)).to(dev)
+        entry = (image_h, image_w, src, crops, boxes, cls)
+        nbytes = src.numel() + sum(m.numel() for m in crops)
+        if self._cached + nbytes <= self.cache_bytes:
+            self._cache[id(label)] = (label, entry)
+            self._cached += nbytes
+        return entry
+
+    def _draw_photo(self, count: int, bnl: int, dec: Dict, photo: List) -> None:
+        """the draws of the photometric step of image ``count`` (:228-241, 466-535) in the reference's order; the step itself is
+        noted in ``photo`` for after the placement launch"""
+        rng = self.rng
+        net_h, net_w = self.net_h, self.net_w
+        if bnl == 2:                                                                    # salt & pepper (:511-525)
+            n_el = net_h * net_w * 3
+            ns, npp = int(math.ceil(0.004 * n_el * 0.2)), int(math.ceil(0.004 * n_el * 0.8))
+            cs = [rng.randint(0, i - 1, ns) for i in (net_h, net_w, 3)]
+            cp = [rng.randint(0, i - 1, npp) for i in (net_h, net_w, 3)]
+            photo.append((count, "salt_pepper", (np.concatenate([cs[0], cp[0]]).astype(np.int32),
+                                                 np.concatenate([cs[1], cp[1]]).astype(np.int32), ns, npp)))
+            dec.update(salt=(cs[0], cs[1]), pepper=(cp[0], cp[1]))
+        elif bnl == 3:                                                                  # light (:527-535)
+            coeff = rng.uniform() + 0.5
+            photo.append((count, "light", (coeff,)))
+            dec["coeff"] = coeff
+        elif bnl == 4:                                                                  # motion blur (:466-494)
+            length_idx = rng.randint(0, 1)                                              # lineLengths = [3]
+            type_idx = int(rng.randint(0, 3))                                           # right, left, full
+            angles = np.linspace(0, 180, 4, endpoint=False)                             # kernel centre 1 -> 4 lines
+            angle = int(angles[rng.randint(0, len(angles))])
+            photo.append((count, "blur", (angle, {0: 1, 1: 2, 2: 0}[type_idx])))
+            dec.update(angle=angle, line_type=("right", "left", "full")[type_idx], _len=int(length_idx))
+
+    def _next_record(self) -> None:
+        self.cursor += 1
+        if self.cursor >= len(self.gt_labels):                                          # :266-271
+            self.rng.shuffle(self.gt_labels)
+            self.random_labels = copy.copy(self.gt_labels)
+            self.cursor = 0
+            self.epoch += 1
+
+    def _photo_and_float(self, photo: List, turn: int) -> None:
+        """the photometric steps noted by ``_draw_photo`` on the placed frames, then the batch's one /255 (the caller records
+        the set's upload event after this: the salt-and-pepper staging of ``turn`` is read by copies enqueued here)"""
+        S = (self.net_h, self.net_w)
+        for count, what, a in photo:
+            f = self._frames[count]
+            if what == "salt_pepper":
+                h, d = self._sp_host[turn][count], self._sp_dev[turn][count]
+                h.numpy()[0], h.numpy()[1] = a[0], a[1]
+                d.copy_(h, non_blocking=True)
+                L.aug_salt_pepper(f, S, d[0], d[1], a[2], a[3])
+            elif what == "light":
+                L.aug_change_light(f, S, a[0])
+            else:
+                L.aug_motion_blur3(f, self._blur, S, a[0], a[1])
+                f.copy_(self._blur)
+        L.aug_to_float(self._frames, self.images)
+
+    def _fill_window(self) -> None:
+        """a batch of windows (DESIGN.md 4k): the host draws the origins and builds one job per image and candidate instance;
+        image placement, visible parts, target assignment and mask placement are launches on the current stream, and nothing
+        comes back to the host"""
+        B, rng = self.batch_size, self.rng
+        S = NH, NW = self.net_h, self.net_w
+        turn = self._turn
+        self._turn ^= 1
+        self._last = turn
+        self.images, self.true_masks = self._sets[turn]
+        if self._uploaded[turn] is not None:
+            self._uploaded[turn].synchronize()                 # (the upload of two batches ago: long done)
+        self.true_masks.zero_()
+        self.last_decisions = []
+        place_bytes = B * L.PLACE_JOB.itemsize
+        raw = self._jobs_host[turn].numpy()
+        jobs, wjobs = raw[:place_bytes].view(L.PLACE_JOB), raw[place_bytes:].view(L.WINDOW_JOB)
+        nwin = 0
+        photo, alive = [], []
+        for count in range(B):
+            label = self.random_labels[self.cursor]
+            image_h, image_w, src, crops, boxes, cls = self._record_window(label)
+            dec = {"placement": "window"}
+            dec.update(draw_window(rng, boxes, image_h, image_w, NH, NW, self.positive_fraction))
+            x0, y0 = dec["x0"], dec["y0"]
+            flip = 1
+            if self.flipped:
+                flip = int(rng.randint(low=1, high=4))
+            bnl = 1
+            if self.blur_noise_light:
+                bnl = int(rng.randint(low=1, high=5))
+            dec.update(flip=flip, bnl=bnl)
+            # the image: the existing placement at scale 1 (taps a = 0: a copy) with the 127 pad
+            alive.append((src, crops))
+            jobs[count] = (src.data_ptr(), self._frames[count].data_ptr(), 0, image_h, image_w, image_w, image_h, -x0, -y0, flip)
+            for i in window_candidates(boxes, x0, y0, NH, NW):
+                x1, y1, x2, y2 = boxes[i]
+                wjobs[nwin] = (crops[i].data_ptr(), y2 - y1, x2 - x1, x1, y1, x0, y0, image_h, image_w, count, cls[i], flip, 0)
+                nwin += 1
+            self._draw_photo(count, bnl, dec, photo)
+            self.last_decisions.append(dec)
+            self._next_record()
+        nbytes = place_bytes + nwin * L.WINDOW_JOB.itemsize
+        jd = self._jobs_dev[turn]
+        jd[:nbytes].copy_(self._jobs_host[turn][:nbytes], non_blocking=True)
+        L.aug_place_batch(jd, B, S)
+        d, wj = self._dev[turn], jd[place_bytes:]
+        self._last_window = (wj, nwin)                         # (what the three launches below were given: tools/window_rate.py)
+        L.window_visible(wj, nwin, S, self._vis)
+        L.window_targets(wj, nwin, self._vis, self._anchors_dev, S, self.min_visible, d[0], d[1], d[2], d[3], self._rows)
+        L.window_place_masks(wj, nwin, self._rows, self.true_masks, S)
+        self._photo_and_float(photo, turn)
+        if self.device.type == "cuda":
+            self._uploaded[turn] = torch.cuda.current_stream().record_event()      # (behind the set's last upload)
+        del alive
+
     def _fill(self) -> None:
+        if self.placement == "window":
+            return self._fill_window()
         B, G, rng = self.batch_size, self.max_box_per_image, self.rng
         S = (self.net_h, self.net_w)
         norm = np.asarray([self.net_w, self.net_h, self.net_w, self.net_h], np.float32)      # x, w by net_w; y, h by net_h
@@ -338,25 +567,7 @@ class defect_train(object):
             for j, m in enumerate(masks):
                 jobs[njobs] = (m.data_ptr(), self.true_masks[count, j].data_ptr(), 1, image_h, image_w, new_w, new_h, dx, dy, flip)
                 njobs += 1
-            if bnl == 2:                                                                    # salt & pepper (:511-525)
-                n_el = net_h * net_w * 3
-                ns, npp = int(math.ceil(0.004 * n_el * 0.2)), int(math.ceil(0.004 * n_el * 0.8))
-                cs = [rng.randint(0, i - 1, ns) for i in (net_h, net_w, 3)]
-                cp = [rng.randint(0, i - 1, npp) for i in (net_h, net_w, 3)]
-                photo.append((count, "salt_pepper", (np.concatenate([cs[0], cp[0]]).astype(np.int32),
-                                                     np.concatenate([cs[1], cp[1]]).astype(np.int32), ns, npp)))
-                dec.update(salt=(cs[0], cs[1]), pepper=(cp[0], cp[1]))
-            elif bnl == 3:                                                                  # light (:527-535)
-                coeff = rng.uniform() + 0.5
-                photo.append((count, "light", (coeff,)))
-                dec["coeff"] = coeff
-            elif bnl == 4:                                                                  # motion blur (:466-494)
-                length_idx = rng.randint(0, 1)                                              # lineLengths = [3]
-                type_idx = int(rng.randint(0, 3))                                           # right, left, full
-                angles = np.linspace(0, 180, 4, endpoint=False)                             # kernel centre 1 -> 4 lines
-                angle = int(angles[rng.randint(0, len(angles))])
-                photo.append((count, "blur", (angle, {0: 1, 1: 2, 2: 0}[type_idx])))
-                dec.update(angle=angle, line_type=("right", "left", "full")[type_idx], _len=int(length_idx))
+            self._draw_photo(count, bnl, dec, photo)
             # ---- normalise (:250-257)
             true_boxes[count, 0, 0, 0, :len(bx), :4] = bx / norm
             true_boxes[count, 0, 0, 0, :len(bx), 4] = cls
@@ -366,26 +577,12 @@ class defect_train(object):
                     ys[k][count, yi, xi, a] = row
                     written.append((k, count, yi, xi, a))
             self.last_decisions.append(dec)
-            self.cursor += 1
-            if self.cursor >= len(self.gt_labels):                                          # :266-271
-                self.rng.shuffle(self.gt_labels)
-                self.random_labels = copy.copy(self.gt_labels)
-                self.cursor = 0
-                self.epoch += 1
+            self._next_record()
         # ---- the batch's pixel work: one placement launch, the photometric steps, one /255
         jd = self._jobs_dev[turn]
         jd[:njobs * L.PLACE_JOB.itemsize].copy_(self._jobs_host[turn][:njobs * L.PLACE_JOB.itemsize], non_blocking=True)
         L.aug_place_batch(jd, njobs, S)
-        for count, what, a in photo:
-            f = self._frames[count]
-            if what == "salt_pepper":
-                L.aug_salt_pepper(f, S, torch.from_numpy(a[0]).to(dev), torch.from_numpy(a[1]).to(dev), a[2], a[3])
-            elif what == "light":
-                L.aug_change_light(f, S, a[0])
-            else:
-                L.aug_motion_blur3(f, self._blur, S, a[0], a[1])
-                f.copy_(self._blur)
-        L.aug_to_float(self._frames, self.images)
+        self._photo_and_float(photo, turn)
         del alive
         if dev.type == "cuda":
             for h, d in zip(host, self._dev[turn]):

@@ -5,7 +5,7 @@ inference net -> detections + instance masks for one image.
     python examples/train_synthetic.py [--steps 40] [--size 192 | --size 128x192] [--batch 4] [--out /tmp/disyolo_example] [--lock 62-64]
                                        [--classes crack,spall,rebar,stain,joint,void]
                                        [--max-boxes 100] [--max-det 100] [--anchors auto | --anchors w,h,w,h,... (9 pairs)]
-                                       [--tiled 500x700]
+                                       [--tiled 500x700] [--windows 600x800]
 
 It mirrors what the reference's ``train_yolo3_mask.py:237-248`` (train) and ``calculate_test_map.py`` (test) do
 with a real dataset; swap ``synthetic_labels`` for ``disyolo_amd.pre_process.load_verify_contour(path, 'train')``
@@ -38,6 +38,27 @@ def synthetic_labels(rng, n, classes=None):
         for _j in range(rng.randint(1, 4)):
             cy, cx = rng.uniform(0.3, 0.7) * h, rng.uniform(0.3, 0.7) * w
             ry, rx = rng.uniform(0.1, 0.25) * h, rng.uniform(0.1, 0.25) * w
+            t = np.sort(rng.uniform(0, 2 * np.pi, rng.randint(6, 10)))
+            polys.append([{"type": "out", "all_points_x": np.clip(cx + rx * np.cos(t), 0, w - 1).astype(int).tolist(),
+                           "all_points_y": np.clip(cy + ry * np.sin(t), 0, h - 1).astype(int).tolist()}])
+            names.append(classes[rng.randint(0, len(classes))])
+        out.append({"image": image, "class_names": names, "polygons": polys})
+    return out
+
+
+def large_labels(rng, n, size, classes=None, instances=12):
+    """n records of ``size`` = (h, w) -- inspection photographs far larger than the net -- each with ``instances`` small
+    defects (radii of 6 .. 60 pixels, whatever the image's size); the image is one noise patch repeated"""
+    classes = cfg.CLASSES if classes is None else classes
+    h, w = (size, size) if isinstance(size, int) else size
+    out = []
+    for _ in range(n):
+        patch = rng.randint(0, 256, (min(h, 256), min(w, 256), 3)).astype(np.uint8)
+        image = np.ascontiguousarray(np.tile(patch, (-(-h // patch.shape[0]), -(-w // patch.shape[1]), 1))[:h, :w])
+        polys, names = [], []
+        for _j in range(instances):
+            ry, rx = rng.uniform(6, min(60, h / 4)), rng.uniform(6, min(60, w / 4))
+            cy, cx = rng.uniform(ry, h - 1 - ry), rng.uniform(rx, w - 1 - rx)
             t = np.sort(rng.uniform(0, 2 * np.pi, rng.randint(6, 10)))
             polys.append([{"type": "out", "all_points_x": np.clip(cx + rx * np.cos(t), 0, w - 1).astype(int).tolist(),
                            "all_points_y": np.clip(cy + ry * np.sin(t), 0, h - 1).astype(int).tolist()}])
@@ -118,11 +139,16 @@ def main():
     ap.add_argument("--tiled", type=parse_size, default=None, metavar="HxW",
                     help="also run the trained net over one synthetic image of this size, larger than the net, cut into "
                          "overlapping tiles whose instances are merged over the seams (disyolo_amd.tiles.detect_tiled)")
+    ap.add_argument("--windows", type=parse_size, default=None, metavar="HxW",
+                    help="window training: the records are synthetic images of this size, larger than the net, and every "
+                         "batch image is a net-size window of one of them at scale 1 (defect_train(placement='window')); at "
+                         "the end the trained net runs over one whole record with detect_tiled")
     args = ap.parse_args()
     classes = [c.strip() for c in args.classes.split(",")]
     dev = torch.device("cuda:0")
     rng = np.random.RandomState(0)
-    labels = synthetic_labels(rng, 16, classes)
+    labels = synthetic_labels(rng, 16, classes) if args.windows is None else large_labels(rng, 8, args.windows, classes)
+    placement = {} if args.windows is None else {"placement": "window"}
     anchors = args.anchors
     if isinstance(anchors, str):
         anchors = cluster_anchors(labels, args.size)
@@ -131,7 +157,7 @@ def main():
 
     # --- train: stage 1 (conv1-52 locked), batches built on the GPU from the polygon records
     data = defect_train(labels, batch_size=args.batch, image_size=args.size, device=dev, rng=np.random.RandomState(1),
-                        classes=classes, **limits)
+                        classes=classes, **limits, **placement)
     net = YOLONet(training=True, device=dev, image_size=args.size, batch_size=args.batch, stage=1, seed=0, k_map=args.k_map,
                   mask_stride=args.mask_stride, lock=parse_lock(args.lock), classes=classes, nms=args.nms, max_detection=args.max_det,
                   mask_roi_det=args.mask_rois[0], mask_roi_gt=args.mask_rois[1], **limits)
@@ -157,6 +183,14 @@ def main():
     h, w = rec["image"].shape[:2]
     entries, merged = postprocess.paste_detections(det_boxes[0], det_masks[0], h, w, args.size)
     print("%d detections on a %dx%d image; class map has %d labelled pixels" % (len(entries), h, w, int((merged > 0).sum())))
+
+    # --- window training: the net saw its records at scale 1, so it is run over a whole record the same way, as tiles
+    if args.windows is not None:
+        from disyolo_amd import tiles
+        res = tiles.detect_tiled(inf, rec["image"], overlap=(inf.H // 8, inf.W // 8), det_thresh=0.05)
+        print("windows: trained on %dx%d windows of %dx%d records; detect_tiled on the first record: %d tiles -> %d instances "
+              "(%d annotated), class map has %d labelled pixels" % (inf.H, inf.W, h, w, len(res.tiles), len(res), len(rec["polygons"]),
+                                                                   int((res.merged > 0).sum())))
 
     # --- an image larger than the net: tiles of the net's size, an instance that runs through several tiles becomes one
     if args.tiled is not None:

@@ -769,6 +769,39 @@ int disyolo_aug_motion_blur3_hw(const uint8_t* src, uint8_t* dst, int net_h, int
 /* image.astype(float32) / 255.0 (:411-413) */
 int disyolo_aug_to_float(const uint8_t* image, float* out, int64_t n, void* stream);
 
+/* ---- window training (defect_train(placement="window"); nothing in the reference: its loader always
+ * fits the whole record into the net) ----
+ * A batch image is a net_h x net_w window of its record at scale 1 with its origin (x0, y0) in image pixels.  A window cuts
+ * instances, so boxes and target grids come from the VISIBLE pixels, on the device.  One job per (batch image, candidate
+ * instance), the jobs of an image adjacent and in record order.  src: the instance's 0 / 1 byte mask cropped to
+ * [crop_y, crop_y + crop_h) x [crop_x, crop_x + crop_w) of the image (row stride crop_w); the visible part of the instance is
+ * crop n window n image.  b: batch index, cls: class index, flip: 1 none / 2 horizontal / 3 vertical.
+ * jobs is a DEVICE array in the three calls below; njobs = 0 is allowed (window_targets then only zeroes its outputs). */
+typedef struct disyolo_window_job {
+  const uint8_t* src;
+  int32_t crop_h, crop_w, crop_x, crop_y, x0, y0, image_h, image_w, b, cls, flip, reserved;
+} disyolo_window_job;
+size_t disyolo_window_job_size(void);
+/* vis int32 [njobs, 5] <- per job (count, x1, y1, x2, y2): the number of set pixels of the visible part and their tight box
+ * in window coordinates, unflipped, x2 / y2 one past the last; all zeros when nothing is visible.  vis is initialised by the
+ * call; integer reductions only, so the result does not depend on the order the blocks run in. */
+int disyolo_window_visible(const disyolo_window_job* jobs, int njobs, int net_h, int net_w, int32_t* vis, void* stream);
+/* Target assignment of utils/train_data.py:136-178, 187-226, 250-257 on the device.  Zeroes true_boxes f32 [B, G, 5] and the
+ * grids yolo3 / yolo2 / yolo1 f32 [B, net_h / d, net_w / d, 3, 5 + C] (d = 8, 16, 32), then walks each image's jobs in order:
+ * a job is kept when its count >= min_visible, its box clamped to [0, net - 1] has w > 0 and h > 0, and fewer than G jobs of
+ * its image were kept before it.  A kept job takes the next row r of true_boxes ((xc, yc, w, h) / (net_w, net_h, net_w,
+ * net_h), class), its best-IoU anchor of the nine (f32, the first maximum; a maximum <= 0 writes no cell) and the cell its
+ * centre falls in unless an earlier job holds that (cell, anchor); centres and cells are reflected for flip 2 / 3.
+ * rows int32 [njobs] <- r, or -1 for a dropped job.  anchors f32 [9, 2] (device).  1 <= G <= DISYOLO_MAX_BOXES, 1 <= C <= 80,
+ * net_h and net_w multiples of 32, min_visible >= 1. */
+int disyolo_window_targets(const disyolo_window_job* jobs, int njobs, const int32_t* vis, const float* anchors, int B, int G,
+                           int C, int net_h, int net_w, int min_visible, float* true_boxes, float* yolo3, float* yolo2,
+                           float* yolo1, int32_t* rows, void* stream);
+/* true_masks uint8 [B, G, net_h, net_w]: every job with rows[job] >= 0 copies its visible bytes into plane [b, rows[job]],
+ * flipped; the caller zeroes true_masks first. */
+int disyolo_window_place_masks(const disyolo_window_job* jobs, int njobs, const int32_t* rows, uint8_t* true_masks, int G,
+                               int net_h, int net_w, void* stream);
+
 /* ---- host helper of the checkpoint reader / writer (dis-yolo_amd/checkpoint.py; train_yolo3_mask.py:58,
  * 221-226 Saver.save / calculate_test_map.py:184-185 Saver.restore): CRC-32C (Castagnoli) of n bytes,
  * continuing from `crc` (0 to start) -- TensorFlow tensor bundles store it masked per tensor and per
