@@ -197,6 +197,11 @@ _SIGS = {
     "disyolo_tile_group_counts": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                             C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                             C.c_void_p, C.c_void_p]),
+    "disyolo_measure_d2": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "disyolo_measure_thin": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "disyolo_measure_counts": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "disyolo_confusion16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "disyolo_confusion_n": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p]),
     "disyolo_paste_job_size": (C.c_size_t, []),
@@ -1201,6 +1206,77 @@ def tile_group_counts(groups, arena, gt, gt_bits, pairs, image_hw, groups_dev=No
                                             ng, _p(gt_bits), int(gt_bits.numel()), pairs.ctypes.data, _p(pairs_dev), P,
                                             int(image_hw[0]), int(image_hw[1]), _p(counts), _stream()), "tile_group_counts")
     return counts
+
+
+def _measure_tables(groups, arena, groups_dev, arena_bytes, what: str):
+    """the groups table (host copy checked by the library before any launch, device copy uploaded when not given), the arena
+    and the bytes of it in use, as every measure_* call takes them"""
+    _need(arena, torch.uint8, "arena")
+    groups, groups_dev = _table(np.asarray(groups, np.int32).reshape(-1, 8), 8, "groups", groups_dev, arena.device)
+    nbytes = int(arena.numel()) if arena_bytes is None else int(arena_bytes)
+    if not 0 <= nbytes <= int(arena.numel()):
+        raise DisyoloError("%s: arena_bytes = %d, the arena holds %d" % (what, nbytes, int(arena.numel())))
+    return groups, groups_dev, nbytes
+
+
+def _need_elems(t: torch.Tensor, dtype, n: int, name: str) -> None:
+    _need(t, dtype, name)
+    if int(t.numel()) < n:
+        raise DisyoloError("%s must hold at least %d elements (got %d)" % (name, n, int(t.numel())))
+
+
+def measure_blocks(groups) -> int:
+    """the block count of the plan in groups [G,8] (tile_compose_plan): what measure_counts' partials must hold"""
+    groups = np.asarray(groups, np.int64).reshape(-1, 8)
+    if groups.shape[0] == 0:
+        return 0
+    last = groups[-1]
+    area = max(int(last[4] - last[2]), 0) * max(int(last[5] - last[3]), 0)
+    return int(last[6]) + (area + COMPOSE_CHUNK - 1) // COMPOSE_CHUNK
+
+
+def measure_d2(groups, arena, colg, d2, groups_dev=None, arena_bytes: Optional[int] = None) -> None:
+    """groups [G,8] (tile_compose_plan; host int32, checked before the launch, its device copy may be passed in); arena uint8
+    CUDA (what tile_compose wrote; ``arena_bytes`` of it, all by default); colg int16 CUDA scratch and d2 int32 CUDA out, each
+    of at least arena_bytes elements in the arena's layout (disyolo_measure_d2).  Elements between crops are left untouched."""
+    groups, groups_dev, nbytes = _measure_tables(groups, arena, groups_dev, arena_bytes, "measure_d2")
+    _need_elems(colg, torch.int16, nbytes, "colg")
+    _need_elems(d2, torch.int32, nbytes, "d2")
+    _check(load().disyolo_measure_d2(groups.ctypes.data, _p(groups_dev), int(groups.shape[0]), _p(arena), nbytes, _p(colg), _p(d2),
+                                     _stream()), "measure_d2")
+
+
+def measure_thin(groups, arena, skel, tmp, flags, iters, it0: int, chunk: int, groups_dev=None,
+                 arena_bytes: Optional[int] = None) -> None:
+    """``chunk`` iterations of Zhang-Suen thinning, numbered from ``it0``, for all groups (disyolo_measure_thin): skel, tmp
+    uint8 CUDA of at least arena_bytes elements, flags int32 CUDA [chunk+1,G] (a non-zero word of the last row: that group
+    still changed), iters int32 CUDA [G].  No synchronisation here: the caller reads the last flags row."""
+    groups, groups_dev, nbytes = _measure_tables(groups, arena, groups_dev, arena_bytes, "measure_thin")
+    G = int(groups.shape[0])
+    _need_elems(skel, torch.uint8, nbytes, "skel")
+    _need_elems(tmp, torch.uint8, nbytes, "tmp")
+    _need(flags, torch.int32, "flags")
+    _need_shape(flags, (int(chunk) + 1, G), "flags")
+    _need(iters, torch.int32, "iters")
+    _need_shape(iters, (G,), "iters")
+    _check(load().disyolo_measure_thin(groups.ctypes.data, _p(groups_dev), G, _p(arena), nbytes, _p(skel), _p(tmp), _p(flags),
+                                       _p(iters), int(it0), int(chunk), _stream()), "measure_thin")
+
+
+def measure_counts(groups, arena, skel, d2, groups_dev=None, arena_bytes: Optional[int] = None):
+    """-> (counts int64 CUDA [G,8] = area, skel_px, n_orth, n_diag, n_end, max_d2, max_d2_skel, 0; sum_sqrt f64 CUDA [G]) of the
+    masks in arena, their skeletons in skel and their squared distances in d2 (disyolo_measure_counts)"""
+    groups, groups_dev, nbytes = _measure_tables(groups, arena, groups_dev, arena_bytes, "measure_counts")
+    G = int(groups.shape[0])
+    _need_elems(skel, torch.uint8, nbytes, "skel")
+    _need_elems(d2, torch.int32, nbytes, "d2")
+    dev = arena.device
+    counts = torch.zeros(G, 8, dtype=torch.int64, device=dev)
+    sum_sqrt = torch.zeros(G, dtype=torch.float64, device=dev)
+    partials = torch.empty(max(measure_blocks(groups), 1), dtype=torch.float64, device=dev)
+    _check(load().disyolo_measure_counts(groups.ctypes.data, _p(groups_dev), G, _p(arena), nbytes, _p(skel), _p(d2), _p(counts),
+                                         _p(partials), int(partials.numel()), _p(sum_sqrt), _stream()), "measure_counts")
+    return counts, sum_sqrt
 
 
 def polygon_mask(px, py, poly_start, poly_is_out, image_h: int, image_w: int, mask) -> None:

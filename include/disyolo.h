@@ -664,6 +664,35 @@ int disyolo_tile_group_counts(const int32_t* groups_host, const int32_t* groups,
                               const int32_t* gt_host, const int32_t* gt, int ng, const uint32_t* gt_bits, int64_t gt_words,
                               const int32_t* pairs_host, const int32_t* pairs, int P, int image_h, int image_w, int32_t* counts,
                               void* stream);
+/* ---- instance measurement: length, width and area of merged instances (csrc/measure.hip, dis-yolo_amd/measure.py; defined by
+ * tests/measure_ref.py) ----
+ * groups int32 [G, 8] and arena (arena_bytes) are what disyolo_tile_compose took and wrote: group g's mask is its crop, bh x bw
+ * bytes, row-major, at arena + 16 * off16; a non-zero byte is foreground (columns 2 .. 7 are read).  Every entry point checks
+ * the host copy before any launch: box sides in 0 .. 32767, block0 = the sum of disyolo_tile_compose_blocks(box area) over the
+ * groups before, crops inside arena_bytes in table order without overlap; otherwise DISYOLO_E_ARG.  Outputs lie in the arena's
+ * layout, one element per pixel (buffers of arena_bytes elements); the elements between two crops are never read and never
+ * written.  None allocates or synchronises.  G = 0 launches nothing.
+ *
+ * measure_d2: d2 int32 = the exact squared Euclidean distance of a foreground pixel to the nearest background pixel, a
+ * one-pixel ring around the crop counting as background; 0 on background.  colg uint16 is scratch (column distances). */
+int disyolo_measure_d2(const int32_t* groups_host, const int32_t* groups, int G, const uint8_t* arena, int64_t arena_bytes,
+                       uint16_t* colg, int32_t* d2, void* stream);
+/* `chunk` iterations of Zhang-Suen thinning (two launches each) for all groups, numbered it0 .. it0 + chunk - 1; the caller
+ * starts with it0 = 0 and continues with it0 += chunk while a word of the last flags row is non-zero.  skel and tmp are byte
+ * buffers; after every call skel holds each group's state (bytes 0 / 1), and once a group's iteration deleted nothing its blocks
+ * return at once and skel keeps its skeleton, whatever iteration it stopped at.  flags int32 [(chunk + 1) G]: row 1 + i, word g
+ * is non-zero when iteration it0 + i deleted a pixel of group g (vector atomic or); row 0 is the last row of the call before
+ * (it0 = 0: all live).  iters int32 [G]: the iterations each group ran, counting the one that deleted nothing (zeroed at
+ * it0 = 0).  The arena is only read.  The result does not depend on `chunk`. */
+int disyolo_measure_thin(const int32_t* groups_host, const int32_t* groups, int G, const uint8_t* arena, int64_t arena_bytes,
+                         uint8_t* skel, uint8_t* tmp, int32_t* flags, int32_t* iters, int it0, int chunk, void* stream);
+/* counts int64 [G, 8] = {area, skel_px, n_orth, n_diag, n_end, max_d2, max_d2_skel, 0} (zeroed here, then integer atomics: exact
+ * and order-independent); sum_sqrt f64 [G] = the sum over the skeleton of sqrt(d2), through partials f64 [partials_len >= the
+ * plan's block count]: per-block sums in a fixed order, added per group in block order -- no float atomic, the same bits on
+ * every run. */
+int disyolo_measure_counts(const int32_t* groups_host, const int32_t* groups, int G, const uint8_t* arena, int64_t arena_bytes,
+                           const uint8_t* skel, const int32_t* d2, int64_t* counts, double* partials, int64_t partials_len,
+                           double* sum_sqrt, void* stream);
 /* semantic-segmentation accuracy of evaluate (calculate_test_map.py:303-346): adds the 4x4 pixel
  * confusion counts of two uint8 class maps (0 = background, 1..3 = classes; other values are
  * ignored) to conf int64 [16], conf[true*4 + pred]; the caller zeroes conf before the first image
