@@ -202,6 +202,14 @@ _SIGS = {
                                        C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "disyolo_measure_counts": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "disyolo_skeleton_classify": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_void_p]),
+    "disyolo_skeleton_label": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p]),
+    "disyolo_skeleton_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "disyolo_skeleton_prune": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_int64, C.c_void_p, C.c_void_p]),
     "disyolo_confusion16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "disyolo_confusion_n": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p]),
     "disyolo_paste_job_size": (C.c_size_t, []),
@@ -1277,6 +1285,77 @@ def measure_counts(groups, arena, skel, d2, groups_dev=None, arena_bytes: Option
     _check(load().disyolo_measure_counts(groups.ctypes.data, _p(groups_dev), G, _p(arena), nbytes, _p(skel), _p(d2), _p(counts),
                                          _p(partials), int(partials.numel()), _p(sum_sqrt), _stream()), "measure_counts")
     return counts, sum_sqrt
+
+
+def _skeleton_tables(groups, like, groups_dev, arena_bytes, what: str):
+    """the groups table and the elements in use of the per-pixel buffers, as every skeleton_* call takes them"""
+    groups, groups_dev = _table(np.asarray(groups, np.int32).reshape(-1, 8), 8, "groups", groups_dev, like.device)
+    nbytes = int(like.numel()) if arena_bytes is None else int(arena_bytes)
+    if not 0 <= nbytes <= int(like.numel()):
+        raise DisyoloError("%s: arena_bytes = %d, the buffer holds %d" % (what, nbytes, int(like.numel())))
+    return groups, groups_dev, nbytes
+
+
+SKELETON_ROW = 12      # int64 words of a branch row (disyolo_skeleton_rows)
+
+
+def _need_rows(rows: torch.Tensor) -> None:
+    _need(rows, torch.int64, "rows")
+    if rows.dim() != 2 or int(rows.shape[1]) != SKELETON_ROW:
+        raise DisyoloError("rows must be [capacity, %d] (got %s)" % (SKELETON_ROW, tuple(rows.shape)))
+
+
+def skeleton_classify(groups, src, skel, links, groups_dev=None, arena_bytes: Optional[int] = None) -> None:
+    """src uint8 CUDA (a non-zero byte is a skeleton pixel) -> links uint8 CUDA, the link bits of every pixel; skel uint8 CUDA
+    gets the 0 / 1 state of src unless it IS src (disyolo_skeleton_classify).  All in the arena's layout."""
+    groups, groups_dev, nbytes = _skeleton_tables(groups, src, groups_dev, arena_bytes, "skeleton_classify")
+    _need(src, torch.uint8, "src")
+    _need_elems(skel, torch.uint8, nbytes, "skel")
+    _need_elems(links, torch.uint8, nbytes, "links")
+    _check(load().disyolo_skeleton_classify(groups.ctypes.data, _p(groups_dev), int(groups.shape[0]), nbytes, _p(src), _p(skel),
+                                            _p(links), _stream()), "skeleton_classify")
+
+
+def skeleton_label(groups, skel, links, labels, groups_dev=None, arena_bytes: Optional[int] = None) -> None:
+    """labels int32 CUDA: the branch label (its smallest pixel index) on pixels of degree <= 2, -1 on the crop's other pixels
+    (disyolo_skeleton_label: init, merge, flatten)"""
+    groups, groups_dev, nbytes = _skeleton_tables(groups, skel, groups_dev, arena_bytes, "skeleton_label")
+    _need(skel, torch.uint8, "skel")
+    _need_elems(links, torch.uint8, nbytes, "links")
+    _need_elems(labels, torch.int32, nbytes, "labels")
+    _check(load().disyolo_skeleton_label(groups.ctypes.data, _p(groups_dev), int(groups.shape[0]), nbytes, _p(skel), _p(links),
+                                         _p(labels), _stream()), "skeleton_label")
+
+
+def skeleton_rows(groups, links, labels, d2, rowid, rows, M2: int, ctrl, junctions, groups_dev=None,
+                  arena_bytes: Optional[int] = None) -> None:
+    """the branch rows int64 CUDA [capacity, SKELETON_ROW] in any order, ctrl int32 CUDA [1 + G] (the branch count, which may
+    exceed the capacity, and one spur flag per group) and junctions int64 CUDA [G,4] (disyolo_skeleton_rows); rowid int32 CUDA
+    per pixel is scratch.  No synchronisation here: the caller reads ctrl."""
+    groups, groups_dev, nbytes = _skeleton_tables(groups, links, groups_dev, arena_bytes, "skeleton_rows")
+    G = int(groups.shape[0])
+    _need(links, torch.uint8, "links")
+    _need_elems(labels, torch.int32, nbytes, "labels")
+    _need_elems(d2, torch.int32, nbytes, "d2")
+    _need_elems(rowid, torch.int32, nbytes, "rowid")
+    _need_rows(rows)
+    _need_elems(ctrl, torch.int32, G + 1, "ctrl")
+    _need(junctions, torch.int64, "junctions")
+    _need_shape(junctions, (G, 4), "junctions")
+    _check(load().disyolo_skeleton_rows(groups.ctypes.data, _p(groups_dev), G, nbytes, _p(links), _p(labels), _p(d2), _p(rowid),
+                                        _p(rows), int(rows.shape[0]), int(M2), _p(ctrl), _p(junctions), _stream()),
+           "skeleton_rows")
+
+
+def skeleton_prune(groups, labels, rowid, rows, skel, groups_dev=None, arena_bytes: Optional[int] = None) -> None:
+    """zeroes the bytes of skel whose branch is a spur by its row (disyolo_skeleton_prune)"""
+    groups, groups_dev, nbytes = _skeleton_tables(groups, skel, groups_dev, arena_bytes, "skeleton_prune")
+    _need(skel, torch.uint8, "skel")
+    _need_elems(labels, torch.int32, nbytes, "labels")
+    _need_elems(rowid, torch.int32, nbytes, "rowid")
+    _need_rows(rows)
+    _check(load().disyolo_skeleton_prune(groups.ctypes.data, _p(groups_dev), int(groups.shape[0]), nbytes, _p(labels), _p(rowid),
+                                         _p(rows), int(rows.shape[0]), _p(skel), _stream()), "skeleton_prune")
 
 
 def polygon_mask(px, py, poly_start, poly_is_out, image_h: int, image_w: int, mask) -> None:

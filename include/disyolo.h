@@ -693,6 +693,34 @@ int disyolo_measure_thin(const int32_t* groups_host, const int32_t* groups, int 
 int disyolo_measure_counts(const int32_t* groups_host, const int32_t* groups, int G, const uint8_t* arena, int64_t arena_bytes,
                            const uint8_t* skel, const int32_t* d2, int64_t* counts, double* partials, int64_t partials_len,
                            double* sum_sqrt, void* stream);
+/* ---- the graph of a skeleton: links, branches, rows per branch, spur pruning (csrc/skeleton.hip, measure.skeleton_graph;
+ * defined by tests/skeleton_ref.py; integers only) ----
+ * The groups table, its check on the host copy before any launch, the layout of every per-pixel buffer (arena_bytes elements,
+ * the elements between two crops never read and never written) and G = 0 are as for disyolo_measure_*.  Neighbours are numbered
+ * N, NE, E, SE, S, SW, W, NW = bits 0 .. 7.  None allocates or synchronises; no block waits for another.
+ *
+ * classify: links uint8 = the link bits of every pixel of src (a non-zero byte is a skeleton pixel): adjacent in a row or a
+ * column, or diagonal with neither pixel completing the 2x2 square set; 0 off the skeleton.  When skel != src, skel gets the
+ * 0 / 1 state of src as well (the copy a pruning starts from); skel == src writes links only. */
+int disyolo_skeleton_classify(const int32_t* groups_host, const int32_t* groups, int G, int64_t arena_bytes, const uint8_t* src,
+                              uint8_t* skel, uint8_t* links, void* stream);
+/* labels int32: on a pixel of degree <= 2 the smallest index y bw + x of its branch (the component under links between two
+ * such pixels), -1 on every other pixel of the crop.  Three launches: init, merge (union-find, the larger root hung under the
+ * smaller by an atomic min: the result does not depend on the order of arrival), flatten. */
+int disyolo_skeleton_label(const int32_t* groups_host, const int32_t* groups, int G, int64_t arena_bytes, const uint8_t* skel,
+                           const uint8_t* links, int32_t* labels, void* stream);
+/* rows int64 [capacity, 12], in any order: {group, root, px, n_orth, n_diag, n_end, n_attach, sum_q8, max_d2, min_d2, spur, 0}
+ * of every branch, spur from M2 = twice min_branch_px (0 .. 65534).  ctrl int32 [1 + G]: word 0 = the number of branches, which
+ * counts beyond `capacity` while nothing is written there (the caller repeats the call with more rows); word 1 + g is non-zero
+ * when group g has a spur.  junctions int64 [G, 4] = {junction_px, jj_orth, jj_diag, n_branches}.  rowid int32 per pixel is
+ * scratch (a root's row number).  ctrl and junctions are zeroed here; integer atomics only: exact and order-independent. */
+int disyolo_skeleton_rows(const int32_t* groups_host, const int32_t* groups, int G, int64_t arena_bytes, const uint8_t* links,
+                          const int32_t* labels, const int32_t* d2, int32_t* rowid, int64_t* rows, int64_t capacity, int M2,
+                          int32_t* ctrl, int64_t* junctions, void* stream);
+/* zeroes the bytes of skel whose branch's row has its spur bit set (labels, rowid, rows as disyolo_skeleton_rows left them, with
+ * a capacity that held every row) */
+int disyolo_skeleton_prune(const int32_t* groups_host, const int32_t* groups, int G, int64_t arena_bytes, const int32_t* labels,
+                           const int32_t* rowid, const int64_t* rows, int64_t capacity, uint8_t* skel, void* stream);
 /* semantic-segmentation accuracy of evaluate (calculate_test_map.py:303-346): adds the 4x4 pixel
  * confusion counts of two uint8 class maps (0 = background, 1..3 = classes; other values are
  * ignored) to conf int64 [16], conf[true*4 + pred]; the caller zeroes conf before the first image
