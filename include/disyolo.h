@@ -238,6 +238,15 @@ enum {
   DISYOLO_WGRAD_REDUCE_ONLY = 4,  /* launch only the slab reduction (workspace must hold the slabs)      */
   DISYOLO_WGRAD_STAGES_MASK = 0x30 /* im2col kernel pipeline depth: (n << 4), n = 1..3 -> 2..4 stages    */
 };
+/* ---- Workspaces.  Every entry point with a `workspace` / `workspace_bytes` pair keeps one contract; `need` is the answer
+ * of its size query (disyolo_*_workspace*), or the size its comment states where it has no query:
+ *   1. with workspace_bytes == need the call succeeds;
+ *   2. it writes nothing outside [workspace, workspace + need);
+ *   3. its outputs do not depend on what the workspace held before the call;
+ *   4. with need - 1 bytes it returns DISYOLO_E_WORKSPACE before any launch.
+ * Workspace contents are undefined on entry and on return: a caller may hand the same buffer to the next call on the same
+ * stream, and must not read it.  tests/test_gpu_workspace.py holds every entry point to rules 1-3 (exact size between guard
+ * bands, poisoned contents), tests/test_workspace.py to rule 4. */
 size_t disyolo_conv2d_wgrad_workspace(const disyolo_conv_desc* d, int opts);
 int disyolo_conv2d_wgrad(const disyolo_conv_desc* d, const void* dy, int dy_ld, float* dw,
                          void* workspace, size_t workspace_bytes, int opts, void* stream);
@@ -321,6 +330,7 @@ int disyolo_bn_bwd_reduce_rows(int64_t rows, int C);   /* workspace of bn_bwd_re
 int disyolo_bn_bwd_reduce(const void* dy, const void* x, const float* scale, const float* shift,
                           const float* mean, const float* rstd, int64_t rows, int C, float alpha, double* sums,
                           void* workspace, size_t workspace_bytes, void* stream);
+/* workspace of bn_bwd_apply_sums: 2 x C floats */
 int disyolo_bn_bwd_apply_sums(const void* dy, const void* x, const float* scale, const float* shift,
                               const float* mean, const float* rstd, const double* local_sums,
                               const double* global_sums, int64_t count, void* dx, float* dgamma, float* dbeta,
