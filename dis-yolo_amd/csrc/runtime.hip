@@ -423,6 +423,20 @@ extern "C" int disyolo_cmdlist_count(void* l, int what, int lane) {
   }
   return n;
 }
+// kind, lane, from, to of command `index`, as struct Cmd holds them (kinds: 0 launch, 1 sync, 2 mark, 3 wait, 4 mark_slot,
+// 5 wait_slot; kind 3: from = the mark's index; kinds 4 / 5: the slot is in to / from).  Read-only, no HIP call: what a test
+// needs to rebuild the partial order that a replay's event edges define.
+extern "C" int disyolo_cmdlist_describe(void* l, int index, int32_t out[4]) {
+  DY_REQUIRE(l && out, "cmdlist_describe: null list or output");
+  const CmdList* c = (const CmdList*)l;
+  DY_REQUIRE(index >= 0 && index < (int)c->cmds.size(), "cmdlist_describe: index %d outside [0,%d)", index, (int)c->cmds.size());
+  const Cmd& k = c->cmds[index];
+  out[0] = k.kind;
+  out[1] = k.lane;
+  out[2] = k.from;
+  out[3] = k.to;
+  return DISYOLO_OK;
+}
 extern "C" void* disyolo_cmdlist_lane_stream(void* l, int lane) {
   if (!l || lane < 1 || lane >= NLANES || !ensure_lane((CmdList*)l, lane)) return nullptr;
   return (void*)((CmdList*)l)->side[lane];

@@ -237,6 +237,7 @@ _SIGS = {
     "disyolo_cmdlist_end": (C.c_int, []),
     "disyolo_cmdlist_size": (C.c_int, [C.c_void_p]),
     "disyolo_cmdlist_count": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "disyolo_cmdlist_describe": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int32)]),
     "disyolo_cmdlist_set_lane": (C.c_int, [C.c_int]),
     "disyolo_cmdlist_sync": (C.c_int, [C.c_int, C.c_int]),
     "disyolo_cmdlist_mark": (C.c_int, [C.c_int]),
@@ -393,6 +394,15 @@ class CmdList:
     def count(self, what: str, lane: int) -> int:
         """packets a replay puts on ``lane``: what = "launches" | "records" | "waits" """
         return load().disyolo_cmdlist_count(self.h, {"launches": 0, "records": 1, "waits": 2}[what], lane)
+
+    def describe(self) -> list:
+        """(kind, lane, from, to) of every command, as the list holds them (include/disyolo.h: disyolo_cmdlist_describe)"""
+        out = (C.c_int32 * 4)()
+        cmds = []
+        for i in range(self.size()):
+            _check(load().disyolo_cmdlist_describe(self.h, i, out), "cmdlist_describe")
+            cmds.append(tuple(out))
+        return cmds
 
     def run(self, first: int = 0, last: Optional[int] = None, fork: bool = True, join: bool = True) -> None:
         last = self.size() if last is None else last

@@ -888,6 +888,16 @@ int disyolo_cmdlist_end(void);
 int disyolo_cmdlist_size(void* list);
 /* packets a replay puts on `lane`: what = 0 launches, 1 event records, 2 event waits (an event packet costs its stream ~3 us) */
 int disyolo_cmdlist_count(void* list, int what, int lane);
+/* out = { kind, lane, from, to } of command `index` (0 <= index < cmdlist_size), as the list holds them.  Read-only, no
+ * device work: a caller can rebuild the partial order a replay's edges define (tests/lane_order.py does).
+ *   kind 0 launch      on `lane`
+ *   kind 1 sync        lane `to` waits for everything lane `from` has recorded so far
+ *   kind 2 mark        a point of lane `from`
+ *   kind 3 wait        lane `to` waits for the mark at list index `from`
+ *   kind 4 mark_slot   a point of lane `from`, under slot `to`
+ *   kind 5 wait_slot   lane `to` waits for the last mark of slot `from`
+ * (`lane` is 0 for every kind but 0.)  A null list, null out or an index out of range: DISYOLO_E_ARG. */
+int disyolo_cmdlist_describe(void* list, int index, int32_t out[4]);
 /* four lanes: 0 = the stream passed to cmdlist_run, 1..3 = side streams owned by the list (3 = the gradient exchange).
  * set_lane selects the lane of the launches recorded next; sync(from,to) makes lane `to` wait
  * for what lane `from` has recorded so far.  Both are no-ops outside a recording.  Every

@@ -67,6 +67,28 @@ def test_exchange_entry_points_validate_and_resolve_rccl_without_a_gpu():
     assert lib.disyolo_cmdlist_lane_stream(None, 1) is None
 
 
+def test_cmdlist_describe_reports_argument_errors():
+    """disyolo_cmdlist_describe reads a recorded list and nothing else: a null list, a null output and an index outside
+    [0, size) come back as DISYOLO_E_ARG with a message; a recorded launch reads back as (0, lane, 0, 0)"""
+    lib = L.load()
+    out = (ctypes.c_int32 * 4)(7, 7, 7, 7)
+    assert lib.disyolo_cmdlist_describe(None, 0, out) == -1 and b"cmdlist_describe" in lib.disyolo_last_error()
+    prog = L.CmdList()
+    assert lib.disyolo_cmdlist_describe(prog.h, 0, out) == -1 and b"outside [0,0)" in lib.disyolo_last_error()     # an empty list
+    buf = ctypes.create_string_buffer(64)
+    p = ctypes.cast(buf, ctypes.c_void_p)
+    with prog:
+        L.set_lane(2)
+        assert lib.disyolo_add_bf16(p, p, 16, 1, None) == 0          # (records itself: nothing is launched)
+    assert prog.size() == 1
+    assert lib.disyolo_cmdlist_describe(prog.h, 0, None) == -1 and b"null" in lib.disyolo_last_error()
+    for bad in (-1, 1, 2 ** 31 - 1):
+        assert lib.disyolo_cmdlist_describe(prog.h, bad, out) == -1 and b"cmdlist_describe: index" in lib.disyolo_last_error()
+    assert list(out) == [7, 7, 7, 7]                                 # (a refused call writes nothing)
+    assert lib.disyolo_cmdlist_describe(prog.h, 0, out) == 0 and list(out) == [0, 2, 0, 0]
+    assert prog.describe() == [(0, 2, 0, 0)]
+
+
 def test_loss_entry_points_reject_unsupported_arguments_before_any_launch():
     """csrc/loss.hip: each unsupported argument of the three loss kernels comes back as an error code with
     disyolo_last_error set, before anything touches a device (the pointers below are host buffers that a launch

@@ -94,11 +94,13 @@ int main() {
     const int n = 1 + rng() % 60;
     static uint8_t a[64], b[64];
     for (int i = 0; i < n; ++i) {
-      switch (rng() % 6) {
+      switch (rng() % 8) {
         case 0: CHECK(disyolo_cmdlist_set_lane((int)(rng() % 3)) == DISYOLO_OK); break;
         case 1: CHECK(disyolo_cmdlist_sync((int)(rng() % 3), (int)(rng() % 3)) >= DISYOLO_E_HIP || true); break;
         case 2: { const int m = disyolo_cmdlist_mark((int)(rng() % 3)); if (m >= 0) marks.push_back(m); break; }
         case 3: if (!marks.empty()) (void)disyolo_cmdlist_wait(marks[rng() % marks.size()], (int)(rng() % 3)); break;
+        case 4: CHECK(disyolo_cmdlist_mark_slot((int)(rng() % 3), (int)(rng() % 16)) == DISYOLO_OK); break;
+        case 5: CHECK(disyolo_cmdlist_wait_slot((int)(rng() % 16), (int)(rng() % 3)) == DISYOLO_OK); break;
         default: CHECK(disyolo_add_bf16(a, b, 8 * (1 + rng() % 4), (int)(rng() & 1), nullptr) == DISYOLO_OK);   // records itself
       }
     }
@@ -108,6 +110,26 @@ int main() {
     CHECK(disyolo_cmdlist_end() == DISYOLO_OK);
     const int sz = disyolo_cmdlist_size(l);
     CHECK(sz >= 0);
+    // describe: every command reads back, its counts are cmdlist_count's, and the ends of the range are refused
+    int packets[3][3] = {};
+    for (int i = 0; i < sz; ++i) {
+      int32_t d[4] = {-1, -1, -1, -1};
+      CHECK(disyolo_cmdlist_describe(l, i, d) == DISYOLO_OK);
+      CHECK(d[0] >= 0 && d[0] <= 5 && d[1] >= 0 && d[1] < 3);
+      if (d[0] == 0) ++packets[0][d[1]];
+      if (d[0] == 1 || d[0] == 2 || d[0] == 4) { CHECK(d[2] >= 0 && d[2] < 3); ++packets[1][d[2]]; }
+      if (d[0] == 1 || d[0] == 3 || d[0] == 5) { CHECK(d[3] >= 0 && d[3] < 3); ++packets[2][d[3]]; }
+      if (d[0] == 4 || d[0] == 5) CHECK(d[d[0] == 4 ? 3 : 2] >= 0 && d[d[0] == 4 ? 3 : 2] < 16);      // the slot
+      if (d[0] == 3) {
+        int32_t m[4];
+        CHECK(d[2] >= 0 && d[2] < i && disyolo_cmdlist_describe(l, d[2], m) == DISYOLO_OK && m[0] == 2);
+      }
+    }
+    for (int what = 0; what < 3; ++what)
+      for (int lane = 0; lane < 3; ++lane) CHECK(disyolo_cmdlist_count(l, what, lane) == packets[what][lane]);
+    int32_t d[4];
+    CHECK(disyolo_cmdlist_describe(l, -1, d) == DISYOLO_E_ARG && disyolo_cmdlist_describe(l, sz, d) == DISYOLO_E_ARG);
+    CHECK(disyolo_cmdlist_describe(nullptr, 0, d) == DISYOLO_E_ARG && (sz == 0 || disyolo_cmdlist_describe(l, 0, nullptr) == DISYOLO_E_ARG));
     CHECK(disyolo_cmdlist_run(l, 0, sz, nullptr) == DISYOLO_OK);
     const int cut = sz ? (int)(rng() % (sz + 1)) : 0;
     CHECK(disyolo_cmdlist_run_ex(l, 0, cut, nullptr, 1) == DISYOLO_OK);
