@@ -210,6 +210,15 @@ _SIGS = {
                                         C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "disyolo_skeleton_prune": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_int64, C.c_void_p, C.c_void_p]),
+    "disyolo_trace_nodes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64] + [C.c_void_p] * 5 + [C.c_int64, C.c_void_p,
+                                      C.c_void_p]),
+    "disyolo_trace_rank": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64] + [C.c_void_p] * 5 + [C.c_int64, C.c_void_p,
+                                     C.c_int64, C.c_int] + [C.c_void_p] * 6),
+    "disyolo_trace_edges": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64] +
+                            [C.c_void_p] * 4 + [C.c_int64, C.c_void_p]),
+    "disyolo_trace_gather": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64] +
+                             [C.c_void_p] * 4 + [C.c_int64] + [C.c_void_p] * 4 + [C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
+                                                                                 C.c_void_p, C.c_void_p]),
     "disyolo_confusion16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "disyolo_confusion_n": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p]),
     "disyolo_paste_job_size": (C.c_size_t, []),
@@ -1366,6 +1375,101 @@ def skeleton_prune(groups, labels, rowid, rows, skel, groups_dev=None, arena_byt
     _need_rows(rows)
     _check(load().disyolo_skeleton_prune(groups.ctypes.data, _p(groups_dev), int(groups.shape[0]), nbytes, _p(labels), _p(rowid),
                                          _p(rows), int(rows.shape[0]), _p(skel), _stream()), "skeleton_prune")
+
+
+# the traced skeleton graph (csrc/trace.hip): int64 words of a node row and of an edge row, int32 words of a list entry, of a
+# branch profile entry, of a trunk profile entry, of the trunk plan's row per branch and per attach pixel; int64 of a trunk row
+TRACE_NODE, TRACE_EDGE, TRACE_ENT, TRACE_PROFILE, TRACE_TRUNK_PROFILE, TRACE_SEG, TRACE_ATTACH, TRACE_TRUNK = 8, 12, 12, 4, 5, 4, 6, 8
+
+
+def _need_table(t: torch.Tensor, dtype, width: int, name: str) -> None:
+    _need(t, dtype, name)
+    if t.dim() != 2 or int(t.shape[1]) != width:
+        raise DisyoloError("%s must be [n, %d] (got %s)" % (name, width, tuple(t.shape)))
+
+
+def trace_nodes(groups, links, d2, node_labels, noderow, nodes, ctrl, groups_dev=None, arena_bytes: Optional[int] = None) -> None:
+    """node_labels int32 CUDA: the node (its smallest pixel index) on pixels of degree >= 3, -1 on the crop's other pixels; nodes
+    int64 CUDA [capacity, TRACE_NODE] in any order and ctrl int32 CUDA [1], their number (disyolo_trace_nodes); noderow int32
+    CUDA per pixel is scratch.  No synchronisation here."""
+    groups, groups_dev, nbytes = _skeleton_tables(groups, links, groups_dev, arena_bytes, "trace_nodes")
+    _need(links, torch.uint8, "links")
+    _need_elems(d2, torch.int32, nbytes, "d2")
+    _need_elems(node_labels, torch.int32, nbytes, "node_labels")
+    _need_elems(noderow, torch.int32, nbytes, "noderow")
+    _need_table(nodes, torch.int64, TRACE_NODE, "nodes")
+    _need_elems(ctrl, torch.int32, 1, "ctrl")
+    _check(load().disyolo_trace_nodes(groups.ctypes.data, _p(groups_dev), int(groups.shape[0]), nbytes, _p(links), _p(d2),
+                                      _p(node_labels), _p(noderow), _p(nodes), int(nodes.shape[0]), _p(ctrl), _stream()), "trace_nodes")
+
+
+def trace_rank(groups, links, labels, d2, rowid, rows, ents, rounds: int, nxt, val, count, rank, rank_diag, groups_dev=None,
+               arena_bytes: Optional[int] = None) -> None:
+    """rank, rank_diag int32 CUDA per pixel: the steps of every branch pixel from its branch's start and the diagonal ones among
+    them, -1 elsewhere in the crops; ents int32 CUDA [capacity, TRACE_ENT], the list of the branch pixels in any order, and count
+    int32 CUDA [1], its length (disyolo_trace_rank).  nxt int32 and val int64 CUDA [4 capacity] are the two state buffers of the
+    ``rounds`` pointer-jumping rounds (2^rounds >= the longest branch's pixels - 1).  labels, rowid, rows: as skeleton_rows left
+    them.  No synchronisation here."""
+    groups, groups_dev, nbytes = _skeleton_tables(groups, links, groups_dev, arena_bytes, "trace_rank")
+    _need(links, torch.uint8, "links")
+    for t, name in ((labels, "labels"), (d2, "d2"), (rowid, "rowid"), (rank, "rank"), (rank_diag, "rank_diag")):
+        _need_elems(t, torch.int32, nbytes, name)
+    _need_rows(rows)
+    _need_table(ents, torch.int32, TRACE_ENT, "ents")
+    cap = int(ents.shape[0])
+    _need_elems(nxt, torch.int32, 4 * cap, "nxt")
+    _need_elems(val, torch.int64, 4 * cap, "val")
+    _need_elems(count, torch.int32, 1, "count")
+    _check(load().disyolo_trace_rank(groups.ctypes.data, _p(groups_dev), int(groups.shape[0]), nbytes, _p(links), _p(labels), _p(d2),
+                                     _p(rowid), _p(rows), int(rows.shape[0]), _p(ents), cap, int(rounds), _p(nxt), _p(val),
+                                     _p(count), _p(rank), _p(rank_diag), _stream()), "trace_rank")
+
+
+def trace_edges(groups, ents, count, rank, rank_diag, node_labels, edges, groups_dev=None, arena_bytes: Optional[int] = None) -> None:
+    """edges int64 CUDA [rows, TRACE_EDGE]: what the two ends of every branch are, row r for the branch of row r of skeleton_rows
+    (disyolo_trace_edges)"""
+    groups, groups_dev, nbytes = _skeleton_tables(groups, rank, groups_dev, arena_bytes, "trace_edges")
+    _need_table(ents, torch.int32, TRACE_ENT, "ents")
+    _need_elems(count, torch.int32, 1, "count")
+    _need(rank, torch.int32, "rank")
+    _need_elems(rank_diag, torch.int32, nbytes, "rank_diag")
+    _need_elems(node_labels, torch.int32, nbytes, "node_labels")
+    _need_table(edges, torch.int64, TRACE_EDGE, "edges")
+    _check(load().disyolo_trace_edges(groups.ctypes.data, _p(groups_dev), int(groups.shape[0]), nbytes, _p(ents), _p(count),
+                                      int(ents.shape[0]), _p(rank), _p(rank_diag), _p(node_labels), _p(edges), int(edges.shape[0]),
+                                      _stream()), "trace_edges")
+
+
+def trace_gather(groups, ents, count, rank, rank_diag, d2, offsets, profile, seg, edges, attach, tprofile, tstart, trunkrows,
+                 groups_dev=None, arena_bytes: Optional[int] = None) -> None:
+    """profile int32 CUDA [capacity, TRACE_PROFILE]: the ordered pixels of every branch, a branch at offsets[row] (int32 CUDA
+    [rows]); tprofile int32 CUDA [n, TRACE_TRUNK_PROFILE]: the trunk profiles by the plan seg int32 CUDA [rows, TRACE_SEG] and
+    attach int32 CUDA [m, TRACE_ATTACH]; trunkrows int64 CUDA [G, TRACE_TRUNK] over the entries tstart int32 CUDA [G + 1] bounds
+    (disyolo_trace_gather).  No synchronisation here."""
+    groups, groups_dev, nbytes = _skeleton_tables(groups, rank, groups_dev, arena_bytes, "trace_gather")
+    G = int(groups.shape[0])
+    _need_table(ents, torch.int32, TRACE_ENT, "ents")
+    _need_elems(count, torch.int32, 1, "count")
+    _need(rank, torch.int32, "rank")
+    _need_elems(rank_diag, torch.int32, nbytes, "rank_diag")
+    _need_elems(d2, torch.int32, nbytes, "d2")
+    _need_table(profile, torch.int32, TRACE_PROFILE, "profile")
+    _need_shape(profile, (int(ents.shape[0]), TRACE_PROFILE), "profile")
+    _need_table(seg, torch.int32, TRACE_SEG, "seg")
+    n_rows = int(seg.shape[0])
+    _need_elems(offsets, torch.int32, n_rows, "offsets")
+    _need_table(edges, torch.int64, TRACE_EDGE, "edges")
+    if int(edges.shape[0]) < n_rows:
+        raise DisyoloError("edges must hold the %d rows of seg (got %d)" % (n_rows, int(edges.shape[0])))
+    _need_table(attach, torch.int32, TRACE_ATTACH, "attach")
+    _need_table(tprofile, torch.int32, TRACE_TRUNK_PROFILE, "tprofile")
+    _need_elems(tstart, torch.int32, G + 1, "tstart")
+    _need(trunkrows, torch.int64, "trunkrows")
+    _need_shape(trunkrows, (G, TRACE_TRUNK), "trunkrows")
+    _check(load().disyolo_trace_gather(groups.ctypes.data, _p(groups_dev), G, nbytes, _p(ents), _p(count), int(ents.shape[0]), _p(rank),
+                                       _p(rank_diag), _p(d2), _p(offsets), n_rows, _p(profile), _p(seg), _p(edges), _p(attach),
+                                       int(attach.shape[0]), _p(tprofile), int(tprofile.shape[0]), _p(tstart), _p(trunkrows),
+                                       _stream()), "trace_gather")
 
 
 def polygon_mask(px, py, poly_start, poly_is_out, image_h: int, image_w: int, mask) -> None:

@@ -38,6 +38,26 @@ What the pruning rule does to the numbers: the short end piece of a crack beyond
 it, so up to min_branch_px is lost per end; a star whose arms are all short is pruned to its junction pixel; a plain T with
 arms 10.5 / 10.5 / 9.5 loses the 9.5 arm at min_branch_px = 10.
 
+The traced graph (csrc/trace.hip, defined by tests/trace_ref.py) orders what the graph left loose:
+
+    t = skeleton_trace(g)
+    t.nodes, t.nodes_of(i), t.edges, t.edges_of(i), t.rank(i), t.rank_diag(i), t.node_labels(i), t.branch_profile(i, root)
+    t.trunk, t.trunk_branches(i), t.trunk_profile(i), t.table(class_names)
+
+  node      a cluster of junction pixels joined by links, named by its smallest pixel, with its pixel count, centroid, largest
+            d2 and attachments;
+  rank      the steps of a branch pixel from its branch's start (a path's end pixel with the smaller index; a loop's root, walked
+            first to the neighbour with the smaller index), rank_diag the diagonal ones among them; an edge row says what the two
+            ends of a branch are: a node, a free end or a loop;
+  trunk     the main path of an instance: between the two vertices (nodes and free ends) whose shortest-path distance over the
+            branches is largest, with its ordered profile (y, x, d2, cum_orth, cum_diag), its length, mean and maximum width
+            and where it is widest.  The pixel work is integers on the GPU; the path is chosen on the host from the tables.
+
+What the trunk rule does to the numbers: a ring with a tail has the tail as its trunk (a branch from a node back to itself is
+never on a shortest path); of two arms between the same two nodes the shorter is taken; a crossing through a thick junction is
+measured straight from attach pixel to attach pixel; an instance of closed loops only has its heaviest loop as trunk.  Host
+synchronisations of skeleton_trace: one read of the edge and node tables, one of the trunk rows.
+
 Working memory of skeleton_graph beside what measure_arena holds: two int32 arenas (labels, row numbers), two byte arenas
 (links, the pruned skeleton) and the row buffer.  Its host synchronisations: one read per analysis (the row counter and the
 per-group spur flags in one copy; once more if the row buffer was too small) and the final copy.
@@ -237,7 +257,9 @@ class SkeletonGraphs:
       branches  one structured array over all instances, sorted by (instance, root): the integer columns of ROW_COLUMNS, root_y,
                 root_x, length_px, mean_width_px, max_width_px, min_width_px (and _mm with a scale), kind; branches_of(g)
       links(g) uint8, labels(g) int32, pruned_skeleton(g) bool: CUDA views [bh,bw]
-      table(class_names) measures.table extended with pruned_length_px, n_branches, junction_px"""
+      table(class_names) measures.table extended with pruned_length_px, n_branches, junction_px
+      rows_dev int64 CUDA [capacity, 12], rowid_arena int32 CUDA, row_order int64 [len(branches)]: the per-branch integer tables
+                on the device, for ``skeleton_trace`` to go on from"""
 
     def __init__(self, measures, pruned, links_arena, labels_arena, rows, junctions, group_analyses, converged, min_branch_px,
                  mm_per_px=None):
@@ -252,6 +274,9 @@ class SkeletonGraphs:
         b = measures.boxes
         self.branches = _branch_table(rows, b[:, 3] - b[:, 1], mm_per_px)
         self._first = np.searchsorted(self.branches["instance"], np.arange(len(measures) + 1))
+        # what ``skeleton_trace`` goes on from (set by skeleton_graph): the row buffer on the device as disyolo_skeleton_rows
+        # left it, the row numbers per root pixel, and row_order[k] = the device row of branches[k]
+        self.rows_dev, self.rowid_arena, self.row_order = None, None, np.zeros(0, np.int64)
 
     def __len__(self) -> int:
         return len(self.measures)
@@ -355,13 +380,300 @@ def skeleton_graph(m: InstanceMeasures, min_branch_px: float = 0.0, max_rounds: 
     flat = _read(torch.cat([rows[:count].reshape(-1), junctions.reshape(-1), counts.reshape(-1), sum_sqrt.view(torch.int64)]))
     nr = count * L.SKELETON_ROW
     table = flat[:nr].reshape(count, L.SKELETON_ROW)
-    table = table[np.lexsort((table[:, 1], table[:, 0]))]
+    row_order = np.lexsort((table[:, 1], table[:, 0]))
+    table = table[row_order]
     ssq = np.ascontiguousarray(flat[nr + 12 * G:]).view(np.float64)
     pm = InstanceMeasures(m.boxes, m._offsets, m.d2_arena, pruned, flat[nr + 4 * G:nr + 12 * G].reshape(G, 8), ssq,
                           m.group_iterations, mm_per_px, m.classid, m.score)
     pm.groups, pm.groups_dev, pm.arena, pm.arena_bytes = groups, groups_dev, m.arena, nbytes
-    return SkeletonGraphs(m, pm, links, labels, table, flat[nr:nr + 4 * G].reshape(G, 4), group_analyses, ~spur, min_branch_px,
-                          mm_per_px)
+    g = SkeletonGraphs(m, pm, links, labels, table, flat[nr:nr + 4 * G].reshape(G, 4), group_analyses, ~spur, min_branch_px, mm_per_px)
+    g.rows_dev, g.rowid_arena, g.row_order = rows, rowid, row_order.astype(np.int64)
+    return g
+
+
+# ---- the traced graph: nodes, ordered branches, the trunk ------------------------------------------------------------------
+NODE_COLUMNS = ("instance", "root", "px", "sum_y", "sum_x", "max_d2", "n_attach")
+EDGE_COLUMNS = ("instance", "root", "end0_kind", "end0_id", "end1_kind", "end1_id", "attach0_px", "attach1_px", "end0_px", "end1_px",
+                "inner_diag", "last_rank")
+TRUNK_COLUMNS = ("n_branches", "px", "n_orth", "n_diag", "n_end", "sum_q8", "max_d2", "max_pos", "max_y", "max_x", "weight")
+END_FREE, END_NODE, END_LOOP = 0, 1, 2
+W_ORTH, W_DIAG, W_END = 1024, 1448, 512       # the integer weights of the trunk selection: a fixed-point sqrt(2)
+
+
+def _trace_read(t: torch.Tensor) -> np.ndarray:
+    """a copy to the host: every host synchronisation of skeleton_trace goes through here"""
+    return t.cpu().numpy()
+
+
+def _octile(a: int, b: int, bw: int):
+    """(orthogonal, diagonal) steps between two pixels of a crop of width bw"""
+    dy, dx = abs(a // bw - b // bw), abs(a % bw - b % bw)
+    return max(dy, dx) - min(dy, dx), min(dy, dx)
+
+
+def select_trunk(weights, edges):
+    """The trunk of one instance.  weights int [n]: 1024 n_orth + 1448 n_diag + 512 n_end of its branches; edges int [n, >= 8]
+    (EDGE_COLUMNS), both sorted by root.  -> (path [(k, reversed)] of indices into them, distance).  Vertices are the nodes and
+    the free ends, ordered by (pixel id, kind, end); a loop or a branch that attaches to one node at both ends is no edge.
+    Dijkstra from every vertex in order, the heap popped by (distance, vertex order), edges relaxed in ascending root, a
+    predecessor replaced only on a strictly smaller distance, the best pair only on a strictly larger one; without any edge the
+    heaviest loop (the smallest root on a tie), without a loop nothing."""
+    import heapq
+    verts, ge = set(), []
+    for k, e in enumerate(edges):
+        k0, i0, k1, i1 = int(e[2]), int(e[3]), int(e[4]), int(e[5])
+        if k0 == END_LOOP or (k0 == END_NODE and k1 == END_NODE and i0 == i1):
+            continue
+        a, b = (i0, k0, 0), (i1, k1, 1 if (k0 == END_FREE and k1 == END_FREE and i0 == i1) else 0)
+        ge.append((k, int(weights[k]), a, b))
+        verts.update((a, b))
+    verts = sorted(verts)
+    at = {v: i for i, v in enumerate(verts)}
+    adj = [[] for _ in verts]
+    for k, w, a, b in ge:
+        adj[at[a]].append((k, w, at[b], False))
+        adj[at[b]].append((k, w, at[a], True))
+    best = (0, None, None, None)
+    for u in range(len(verts)):
+        dist, pred, done, heap = {u: 0}, {}, set(), [(0, u)]
+        while heap:
+            d, a = heapq.heappop(heap)
+            if a in done:
+                continue
+            done.add(a)
+            for k, w, b, rev in adj[a]:
+                if b not in dist or d + w < dist[b]:
+                    dist[b], pred[b] = d + w, (a, k, rev)
+                    heapq.heappush(heap, (d + w, b))
+        for v in sorted(dist):
+            if dist[v] > best[0]:
+                best = (dist[v], u, v, pred)
+    if best[1] is not None:
+        d, u, a, pred = best
+        path = []
+        while a != u:
+            a, k, rev = pred[a]
+            path.append((k, rev))
+        return path[::-1], d
+    loops = [(-int(weights[k]), k) for k, e in enumerate(edges) if int(e[2]) == END_LOOP]
+    if loops:
+        w, k = min(loops)
+        return [(k, False)], -w
+    return [], 0
+
+
+class SkeletonTraces:
+    """What ``skeleton_trace`` returns, for the G instances of its SkeletonGraphs ``graphs``:
+      nodes     one structured array over all instances, sorted by (instance, root): NODE_COLUMNS (int64) and centroid_y,
+                centroid_x (float64, crop coordinates); nodes_of(i)
+      edges     one row per branch, in the order of graphs.branches: EDGE_COLUMNS (int64).  End 0 is at rank 0, end 1 at the last
+                rank; kind 1 = a node (id its root, attach the junction pixel linked to), 0 = a free end (id the end pixel,
+                attach -1), 2 = a loop (id the root); end0_px, end1_px the branch's first and last pixel; edges_of(i)
+      rank(i), rank_diag(i), node_labels(i)  int32 CUDA views [bh,bw], -1 off the branch pixels / off the junction pixels
+      branch_profile(i, root)  int32 CUDA view [px,4]: y, x, d2, rank_diag of the branch's pixels in rank order (all of them lie
+                in profile_buffer in the order of graphs.branches).  A pixel's arc position is
+                (rank - rank_diag) + sqrt(2) rank_diag
+      trunk     structured array [G]: TRUNK_COLUMNS (int64), trunk_length_px, mean_width_px, max_width_px, widest_y, widest_x (the
+                first widest point in image coordinates) and, with a scale, trunk_length_mm, mean_width_mm, max_width_mm
+      trunk_branches(i)  [(root, reversed)] along the trunk; trunk_profile(i) int32 CUDA view [px,5]: y, x, d2, cum_orth, cum_diag
+      table(class_names) graphs.table extended with the trunk columns"""
+
+    def __init__(self, graphs, node_labels_arena, rank_arena, rank_diag_arena, nodes, edges, profile_buffer, trunk_ints, paths,
+                 trunk_buffer, trunk_start, mm_per_px=None):
+        self.graphs, self.mm_per_px = graphs, mm_per_px
+        self.node_labels_arena, self.rank_arena, self.rank_diag_arena = node_labels_arena, rank_arena, rank_diag_arena
+        self.profile_buffer, self.trunk_buffer = profile_buffer, trunk_buffer
+        G = len(graphs)
+        nodes = np.asarray(nodes, np.int64).reshape(-1, L.TRACE_NODE)
+        self.nodes = np.zeros(nodes.shape[0], dtype=[(c, np.int64) for c in NODE_COLUMNS] + [("centroid_y", np.float64), ("centroid_x", np.float64)])
+        for i, c in enumerate(NODE_COLUMNS):
+            self.nodes[c] = nodes[:, i]
+        self.nodes["centroid_y"] = nodes[:, 3] / np.maximum(nodes[:, 2], 1)
+        self.nodes["centroid_x"] = nodes[:, 4] / np.maximum(nodes[:, 2], 1)
+        self._node_first = np.searchsorted(self.nodes["instance"], np.arange(G + 1))
+        edges = np.asarray(edges, np.int64).reshape(-1, L.TRACE_EDGE)
+        self.edges = np.zeros(edges.shape[0], dtype=[(c, np.int64) for c in EDGE_COLUMNS])
+        for i, c in enumerate(EDGE_COLUMNS):
+            self.edges[c] = edges[:, i]
+        self._profile_start = np.concatenate([[0], np.cumsum(graphs.branches["px"])]).astype(np.int64)
+        self._paths, self._trunk_start = list(paths), np.asarray(trunk_start, np.int64)
+        ti = np.asarray(trunk_ints, np.int64).reshape(-1, len(TRUNK_COLUMNS))
+        floats = ["trunk_length_px", "mean_width_px", "max_width_px", "widest_y", "widest_x"]
+        if mm_per_px is not None:
+            floats += ["trunk_length_mm", "mean_width_mm", "max_width_mm"]
+        self.trunk = np.zeros(G, dtype=[(c, np.int64) for c in TRUNK_COLUMNS] + [(f, np.float64) for f in floats])
+        for i, c in enumerate(TRUNK_COLUMNS):
+            self.trunk[c] = ti[:, i]
+        t, some = self.trunk, ti[:, 1] > 0
+        t["trunk_length_px"] = np.where(some, t["n_orth"] + np.sqrt(2.0) * t["n_diag"] + t["n_end"] / 2.0, 0.0)
+        t["mean_width_px"] = np.where(some, 2.0 * (t["sum_q8"] / 256.0) / np.maximum(t["px"], 1) - 1.0, 0.0)
+        t["max_width_px"] = np.where(some, 2.0 * np.sqrt(t["max_d2"].astype(np.float64)) - 1.0, 0.0)
+        b = graphs.measures.boxes.astype(np.int64).reshape(-1, 4)
+        t["widest_y"], t["widest_x"] = np.where(some, b[:, 0] + t["max_y"], 0), np.where(some, b[:, 1] + t["max_x"], 0)
+        if mm_per_px is not None:
+            for f in ("trunk_length", "mean_width", "max_width"):
+                t[f + "_mm"] = t[f + "_px"] * float(mm_per_px)
+
+    def __len__(self) -> int:
+        return len(self.graphs)
+
+    def nodes_of(self, g: int) -> np.ndarray:
+        return self.nodes[self._node_first[g]:self._node_first[g + 1]]
+
+    def edges_of(self, g: int) -> np.ndarray:
+        return self.edges[self.graphs._first[g]:self.graphs._first[g + 1]]
+
+    def rank(self, g: int) -> torch.Tensor:
+        return self.graphs.measures._view(self.rank_arena, g)
+
+    def rank_diag(self, g: int) -> torch.Tensor:
+        return self.graphs.measures._view(self.rank_diag_arena, g)
+
+    def node_labels(self, g: int) -> torch.Tensor:
+        return self.graphs.measures._view(self.node_labels_arena, g)
+
+    def branch_profile(self, g: int, root: int) -> torch.Tensor:
+        b = self.graphs.branches_of(g)
+        k = int(np.searchsorted(b["root"], int(root)))
+        if k >= len(b) or int(b["root"][k]) != int(root):
+            raise KeyError("instance %d has no branch with root %r" % (g, root))
+        k += int(self.graphs._first[g])
+        return self.profile_buffer[int(self._profile_start[k]):int(self._profile_start[k + 1])]
+
+    def trunk_branches(self, g: int) -> List[tuple]:
+        return list(self._paths[g])
+
+    def trunk_profile(self, g: int) -> torch.Tensor:
+        return self.trunk_buffer[int(self._trunk_start[g]):int(self._trunk_start[g + 1])]
+
+    def table(self, class_names: Optional[Sequence[str]] = None) -> List[dict]:
+        rows = self.graphs.table(class_names)
+        t = self.trunk
+        for g, row in enumerate(rows):
+            row.update(trunk_length_px=float(t["trunk_length_px"][g]), trunk_branches=int(t["n_branches"][g]),
+                       trunk_mean_width_px=float(t["mean_width_px"][g]), trunk_max_width_px=float(t["max_width_px"][g]),
+                       trunk_widest_yx=(int(t["widest_y"][g]), int(t["widest_x"][g])))
+            if self.mm_per_px is not None:
+                row.update(trunk_length_mm=float(t["trunk_length_mm"][g]), trunk_mean_width_mm=float(t["mean_width_mm"][g]),
+                           trunk_max_width_mm=float(t["max_width_mm"][g]))
+        return rows
+
+
+def skeleton_trace(g: SkeletonGraphs, mm_per_px=None, node_labels_out=None, rank_out=None, rank_diag_out=None) -> SkeletonTraces:
+    """Trace the graphs of ``g`` (what skeleton_graph returned): the junction clusters as nodes, every branch ordered from one
+    end to the other with what its ends are, and per instance the trunk -- the path between the two vertices that lie farthest
+    apart -- with its profile.  ``mm_per_px`` defaults to the scale of ``g``.  ``node_labels_out``, ``rank_out``,
+    ``rank_diag_out`` (int32 CUDA of at least arena_bytes elements) are used for the result arenas when given; their elements
+    between two crops are left untouched.  ``g`` is not changed.  G = 0 launches nothing and reads nothing; without any skeleton
+    pixel only the two maps are written."""
+    if not isinstance(g, SkeletonGraphs):
+        raise ValueError("skeleton_trace needs the SkeletonGraphs of skeleton_graph (got %s)" % type(g).__name__)
+    if mm_per_px is None:
+        mm_per_px = g.mm_per_px
+    if mm_per_px is not None and not (np.isfinite(float(mm_per_px)) and float(mm_per_px) > 0.0):
+        raise ValueError("mm_per_px must be a positive number (got %r)" % (mm_per_px,))
+    m, G = g.measures, len(g)
+    nb = len(g.branches)
+    no_ints = np.zeros((G, len(TRUNK_COLUMNS)), np.int64)
+    if G == 0:
+        e32 = m.d2_arena.new_empty(0)
+        return SkeletonTraces(g, e32, e32, e32, np.zeros((0, L.TRACE_NODE)), np.zeros((0, L.TRACE_EDGE)), e32.view(0, L.TRACE_PROFILE), no_ints,
+                              [], e32.view(0, L.TRACE_TRUNK_PROFILE), np.zeros(1, np.int64), mm_per_px)
+    if m.groups is None or g.rows_dev is None or g.rowid_arena is None or len(g.row_order) != nb:
+        raise ValueError("skeleton_trace needs the SkeletonGraphs of skeleton_graph, with its row tables (rows_dev, rowid_arena, row_order)")
+    groups, groups_dev, nbytes, dev = m.groups, m.groups_dev, m.arena_bytes, g.links_arena.device
+    if nbytes >= 1 << 31:
+        raise ValueError("skeleton_trace takes arenas below 2^31 elements (got %d)" % nbytes)
+    n = max(nbytes, 1)
+    i32 = dict(dtype=torch.int32, device=dev)
+    node_labels = torch.empty(n, **i32) if node_labels_out is None else node_labels_out
+    rank = torch.empty(n, **i32) if rank_out is None else rank_out
+    rank_diag = torch.empty(n, **i32) if rank_diag_out is None else rank_diag_out
+    noderow = torch.empty(n, **i32)
+    px = g.branches["px"].astype(np.int64)
+    n_list, n_junction = int(px.sum()), int(g.junction_px.sum())
+    rounds = (int(px.max()) - 1).bit_length() if nb else 0           # 2^rounds >= the longest branch's pixels - 1
+    nodes = torch.empty(n_junction, L.TRACE_NODE, dtype=torch.int64, device=dev)
+    ents = torch.empty(n_list, L.TRACE_ENT, **i32)
+    nxt = torch.empty(4 * n_list, **i32)
+    val = torch.empty(4 * n_list, dtype=torch.int64, device=dev)
+    ctrl, count = torch.zeros(1, **i32), torch.zeros(1, **i32)
+    d2, links = m.d2_arena, g.links_arena
+    L.trace_nodes(groups, links, d2, node_labels, noderow, nodes, ctrl, groups_dev, nbytes)
+    L.trace_rank(groups, links, g.labels_arena, d2, g.rowid_arena, g.rows_dev, ents, rounds, nxt, val, count, rank, rank_diag, groups_dev,
+                 nbytes)
+    profile = torch.empty(n_list, L.TRACE_PROFILE, **i32)
+    if n_list == 0 and n_junction == 0:
+        return SkeletonTraces(g, node_labels, rank, rank_diag, np.zeros((0, L.TRACE_NODE)), np.zeros((0, L.TRACE_EDGE)), profile, no_ints,
+                              [[] for _ in range(G)], profile.new_empty(0, L.TRACE_TRUNK_PROFILE), np.zeros(G + 1, np.int64), mm_per_px)
+    n_rows = int(g.row_order.max()) + 1 if nb else 0
+    edges_dev = torch.empty(n_rows, L.TRACE_EDGE, dtype=torch.int64, device=dev)
+    L.trace_edges(groups, ents, count, rank, rank_diag, node_labels, edges_dev, groups_dev, nbytes)
+    # the first read: the edge and node tables, which the trunk selection needs
+    flat = _trace_read(torch.cat([edges_dev.reshape(-1), nodes.reshape(-1), ctrl.to(torch.int64)]))
+    ne = n_rows * L.TRACE_EDGE
+    edges = flat[:ne].reshape(n_rows, L.TRACE_EDGE)[g.row_order]
+    n_nodes = int(flat[-1])
+    if n_nodes > n_junction:
+        raise L.DisyoloError("skeleton_trace: %d nodes from %d junction pixels" % (n_nodes, n_junction))
+    ntab = flat[ne:ne + n_nodes * L.TRACE_NODE].reshape(n_nodes, L.TRACE_NODE)
+    ntab = ntab[np.lexsort((ntab[:, 1], ntab[:, 0]))]
+    b = g.branches
+    if not (np.array_equal(edges[:, 0], b["instance"]) and np.array_equal(edges[:, 1], b["root"]) and np.array_equal(edges[:, 11], px - 1)):
+        raise L.DisyoloError("skeleton_trace: the edge table does not describe the branches of the graph")
+    weights = W_ORTH * b["n_orth"] + W_DIAG * b["n_diag"] + W_END * b["n_end"]
+    widths = (m.boxes[:, 3] - m.boxes[:, 1]).astype(np.int64)
+    offsets = np.zeros(n_rows, np.int32)
+    offsets[g.row_order] = np.concatenate([[0], np.cumsum(px)[:-1]]) if nb else []
+    seg = np.zeros((n_rows, L.TRACE_SEG), np.int32)
+    seg[:, 0] = -1
+    attach, paths, tstart, ints = [], [], np.zeros(G + 1, np.int64), no_ints.copy()
+    cursor = 0
+    for i in range(G):
+        k0, k1 = int(g._first[i]), int(g._first[i + 1])
+        bw, off = int(widths[i]), int(m._offsets[i])
+        path, dist = select_trunk(weights[k0:k1], edges[k0:k1])
+        co = cd = cross_o = cross_d = 0
+        last_px = leave = None
+        for k, rev in path:
+            e = edges[k0 + k]
+            enter, out = (int(e[7]), int(e[6])) if rev else (int(e[6]), int(e[7]))
+            first, last = (int(e[9]), int(e[8])) if rev else (int(e[8]), int(e[9]))
+            if leave is not None:
+                for a in ([leave] if enter == leave else [leave, enter]):
+                    so, sd = _octile(last_px, a, bw)                  # (onto the first one: a link; on to the second: the crossing)
+                    if a != leave:
+                        cross_o, cross_d = cross_o + so, cross_d + sd
+                    co, cd, last_px = co + so, cd + sd, a
+                    attach.append((off + a, cursor, a // bw, a % bw, co, cd))
+                    cursor += 1
+                so, sd = _octile(last_px, first, bw)
+                co, cd = co + so, cd + sd
+            seg[g.row_order[k0 + k]] = (cursor, int(rev), co, cd)
+            co, cd = co + int(e[11]) - int(e[10]), cd + int(e[10])
+            cursor += int(e[11]) + 1
+            last_px, leave = last, out
+        paths.append([(int(b["root"][k0 + k]), bool(rev)) for k, rev in path])
+        tstart[i + 1] = cursor
+        if path:
+            ks = [k0 + k for k, _ in path]
+            # n_orth, n_diag: those of the branches' rows plus the crossings between two attach pixels of one node
+            ints[i, 0], ints[i, 4], ints[i, 10] = len(path), int(b["n_end"][ks].sum()), int(weights[ks].sum())
+            ints[i, 2], ints[i, 3] = int(b["n_orth"][ks].sum()) + cross_o, int(b["n_diag"][ks].sum()) + cross_d
+    if cursor >= 1 << 30:
+        raise ValueError("skeleton_trace: trunk profiles of %d entries (need < 2^30)" % cursor)
+    tprofile = torch.empty(cursor, L.TRACE_TRUNK_PROFILE, **i32)
+    trunkrows = torch.empty(G, L.TRACE_TRUNK, dtype=torch.int64, device=dev)
+    plan = np.concatenate([offsets, seg.reshape(-1), np.asarray(attach, np.int32).reshape(-1), tstart.astype(np.int32)]).astype(np.int32)
+    plan_dev = torch.from_numpy(plan).to(dev)                            # one upload
+    o0, o1 = n_rows, n_rows + seg.size
+    o2 = o1 + len(attach) * L.TRACE_ATTACH
+    L.trace_gather(groups, ents, count, rank, rank_diag, d2, plan_dev[:o0], profile, plan_dev[o0:o1].view(n_rows, L.TRACE_SEG), edges_dev,
+                   plan_dev[o1:o2].view(len(attach), L.TRACE_ATTACH), tprofile, plan_dev[o2:], trunkrows, groups_dev, nbytes)
+    # the final read: the trunk rows
+    tr = _trace_read(trunkrows)
+    ints[:, 1], ints[:, 5], ints[:, 6], ints[:, 7], ints[:, 8], ints[:, 9] = tr[:, 0], tr[:, 1], tr[:, 2], tr[:, 3], tr[:, 4], tr[:, 5]
+    return SkeletonTraces(g, node_labels, rank, rank_diag, ntab, edges, profile, ints, paths, tprofile, tstart, mm_per_px)
 
 
 def pack_masks(masks, fill: int = 0, foreground: int = 1):

@@ -5,7 +5,7 @@ inference net -> detections + instance masks for one image.
     python examples/train_synthetic.py [--steps 40] [--size 192 | --size 128x192] [--batch 4] [--out /tmp/disyolo_example] [--lock 62-64]
                                        [--classes crack,spall,rebar,stain,joint,void]
                                        [--max-boxes 100] [--max-det 100] [--anchors auto | --anchors w,h,w,h,... (9 pairs)]
-                                       [--tiled 500x700 [--measure [--mm-per-px 0.25] [--min-branch 10]]] [--windows 600x800]
+                                       [--tiled 500x700 [--measure [--mm-per-px 0.25] [--min-branch 10 [--trunk]]]] [--windows 600x800]
 
 It mirrors what the reference's ``train_yolo3_mask.py:237-248`` (train) and ``calculate_test_map.py`` (test) do
 with a real dataset; swap ``synthetic_labels`` for ``disyolo_amd.pre_process.load_verify_contour(path, 'train')``
@@ -109,17 +109,21 @@ def parse_mask_rois(text):
     return int(parts[0]), int(parts[1])
 
 
-def print_measures(res, classes, mm_per_px, min_branch=None):
+def print_measures(res, classes, mm_per_px, min_branch=None, trunk=False):
     """length, width and area of every merged instance, measured on the GPU from the result's cropped masks; with
-    ``min_branch`` also the graph of every skeleton: its branches, its junction pixels and its length without the spurs"""
-    from disyolo_amd.measure import measure_instances, skeleton_graph
+    ``min_branch`` also the graph of every skeleton: its branches, its junction pixels and its length without the spurs; with
+    ``trunk`` also the main path of every graph: its length, its widest point and where in the image that is"""
+    from disyolo_amd.measure import measure_instances, skeleton_graph, skeleton_trace
     m = measure_instances(res, mm_per_px=mm_per_px)
     print("measured %d instances (%d thinning iterations):" % (len(m), m.iterations))
     graph = None if min_branch is None else skeleton_graph(m, min_branch_px=min_branch)
     if graph is not None:
         print("skeleton graphs: spurs below %.1f px pruned in %d analyses (%d of %d instances converged), %d branches" % (
             min_branch, graph.analyses, int(graph.converged.sum()), len(graph), len(graph.branches)))
-    for row in (m if graph is None else graph).table(classes):
+    traced = skeleton_trace(graph) if trunk else None
+    if traced is not None:
+        print("skeleton traces: %d nodes, trunks of %d branches in all" % (len(traced.nodes), int(traced.trunk["n_branches"].sum())))
+    for row in (m if graph is None else graph if traced is None else traced).table(classes):
         line = "  %3d %-8s %.2f  area %7d px  length %8.1f px  width max %6.1f mean %6.1f px" % (
             row["instance"], row["class"], row["score"], row["area_px"], row["length_px"], row["max_width_px"], row["mean_width_px"])
         if mm_per_px is not None:
@@ -128,6 +132,11 @@ def print_measures(res, classes, mm_per_px, min_branch=None):
         if graph is not None:
             line += "  |  pruned length %8.1f px  %3d branches  %3d junction px" % (
                 row["pruned_length_px"], row["n_branches"], row["junction_px"])
+        if traced is not None:
+            line += "  |  trunk %8.1f px over %2d branches, widest %5.1f px at (%d, %d)" % (
+                row["trunk_length_px"], row["trunk_branches"], row["trunk_max_width_px"], row["trunk_widest_yx"][0], row["trunk_widest_yx"][1])
+            if mm_per_px is not None:
+                line += " = %7.1f mm, widest %5.1f mm" % (row["trunk_length_mm"], row["trunk_max_width_mm"])
         print(line)
 
 
@@ -169,6 +178,10 @@ def main():
                     help="--measure: also build the graph of every skeleton and prune its spurs shorter than this many pixels "
                          "(a multiple of 0.5; disyolo_amd.measure.skeleton_graph): adds the pruned length, the branches and "
                          "the junction pixels")
+    ap.add_argument("--trunk", action="store_true",
+                    help="--min-branch: also trace every pruned graph (disyolo_amd.measure.skeleton_trace) and print the trunk of "
+                         "every instance -- the path between its two farthest ends -- with its length, its widest point and where "
+                         "in the image that is")
     ap.add_argument("--windows", type=parse_size, default=None, metavar="HxW",
                     help="window training: the records are synthetic images of this size, larger than the net, and every "
                          "batch image is a net-size window of one of them at scale 1 (defect_train(placement='window')); at "
@@ -176,6 +189,8 @@ def main():
     args = ap.parse_args()
     if args.min_branch is not None and not args.measure:
         ap.error("--min-branch extends the table of --measure: give --measure too")
+    if args.trunk and args.min_branch is None:
+        ap.error("--trunk traces the graph of --min-branch: give --min-branch too (0 prunes nothing)")
     if args.measure and args.tiled is None and args.windows is None:
         ap.error("--measure measures the instances of detect_tiled: give --tiled HxW or --windows HxW")
     classes = [c.strip() for c in args.classes.split(",")]
@@ -226,7 +241,7 @@ def main():
               "(%d annotated), class map has %d labelled pixels" % (inf.H, inf.W, h, w, len(res.tiles), len(res), len(rec["polygons"]),
                                                                    int((res.merged > 0).sum())))
         if args.measure:
-            print_measures(res, classes, args.mm_per_px, args.min_branch)
+            print_measures(res, classes, args.mm_per_px, args.min_branch, args.trunk)
 
     # --- an image larger than the net: tiles of the net's size, an instance that runs through several tiles becomes one
     if args.tiled is not None:
@@ -243,7 +258,7 @@ def main():
             print("  %s %.2f box (%d, %d)-(%d, %d), %d pixels, from tiles %s" % (
                 classes[res.classid[g]], res.score[g], y1, x1, y2, x2, int(res.mask(g).sum()), sorted({t for t, _ in res.members[g]})))
         if args.measure:
-            print_measures(res, classes, args.mm_per_px, args.min_branch)
+            print_measures(res, classes, args.mm_per_px, args.min_branch, args.trunk)
         # the metric of the whole image against the records it was drawn from: every repeat of an instance is an instance
         from disyolo_amd.evaluate import MAP, evaluate
         from disyolo_amd.train_data import rasterize_instance

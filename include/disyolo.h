@@ -731,6 +731,49 @@ int disyolo_skeleton_rows(const int32_t* groups_host, const int32_t* groups, int
  * a capacity that held every row) */
 int disyolo_skeleton_prune(const int32_t* groups_host, const int32_t* groups, int G, int64_t arena_bytes, const int32_t* labels,
                            const int32_t* rowid, const int64_t* rows, int64_t capacity, uint8_t* skel, void* stream);
+/* ---- the traced skeleton graph: nodes, ordered branches, edges, profiles (csrc/trace.hip, measure.skeleton_trace; defined by
+ * tests/trace_ref.py; integers only) ----
+ * They go on from what disyolo_skeleton_* left of the final skeleton: links, labels, rowid, rows; d2 is disyolo_measure_d2's.  The
+ * groups table, its check on the host copy before any launch, the layout of the per-pixel buffers and G = 0 are as above; the
+ * arena must hold fewer than 2^31 elements (positions are int32).  None allocates or synchronises; no block waits for another, and
+ * apart from the union-find none reads what another block writes in the same launch.
+ *
+ * nodes: node_labels int32 = on a pixel of degree >= 3 the smallest index y bw + x of its node (the component under the links
+ * between two such pixels), -1 on every other pixel of the crop.  nodes int64 [capacity, 8], in any order: {group, root, px,
+ * sum_y, sum_x, max_d2, n_attach, 0}; ctrl int32 [1] = the number of nodes (zeroed here; it counts beyond `capacity` while nothing
+ * is written there).  noderow int32 per pixel is scratch.  Five launches: init, merge, flatten, alloc, accumulate. */
+int disyolo_trace_nodes(const int32_t* groups_host, const int32_t* groups, int G, int64_t arena_bytes, const uint8_t* links,
+                        const int32_t* d2, int32_t* node_labels, int32_t* noderow, int64_t* nodes, int64_t capacity, int32_t* ctrl,
+                        void* stream);
+/* rank, rank_diag int32: on a pixel of degree <= 2 the steps from its branch's start and how many of them were diagonal links, -1
+ * on every other pixel of the crop.  The start of a path is its end pixel with the smaller index, the start of a loop its root,
+ * walked first to the linked neighbour with the smaller index.  The pixels of branches are compacted into ents int32
+ * [capacity, 12], in any order (count int32 [1] = how many; zeroed here): {position in the arena, index in the crop, root, the two
+ * in-branch neighbours and the two junction neighbours as arena positions or -1, flags, row number, group, d2, crop width}.  Then
+ * list ranking by pointer jumping over the doubled states (entry, direction) between the two halves of nxt int32 [4 capacity] and
+ * val int64 [4 capacity]: one launch per round, `rounds` >= log2 of the longest branch's pixel count.  3 + rounds launches. */
+int disyolo_trace_rank(const int32_t* groups_host, const int32_t* groups, int G, int64_t arena_bytes, const uint8_t* links,
+                       const int32_t* labels, const int32_t* d2, const int32_t* rowid, const int64_t* rows, int64_t rows_capacity,
+                       int32_t* ents, int64_t capacity, int rounds, int32_t* nxt, int64_t* val, int32_t* count, int32_t* rank,
+                       int32_t* rank_diag, void* stream);
+/* edges int64 [edges_capacity, 12], row r = the branch of row r of disyolo_skeleton_rows: {group, root, end0_kind, end0_id,
+ * end1_kind, end1_id, attach0_px, attach1_px, end0_px, end1_px, inner_diag, last_rank}.  End 0 is at rank 0, end 1 at the last rank.
+ * kind 1: a node, id = its root, attach = the junction pixel linked to; kind 0: a free end, id = the end pixel, attach = -1; kind
+ * 2: a loop, id = the root.  Every slot has one writer.  One launch over the list. */
+int disyolo_trace_edges(const int32_t* groups_host, const int32_t* groups, int G, int64_t arena_bytes, const int32_t* ents,
+                        const int32_t* count, int64_t capacity, const int32_t* rank, const int32_t* rank_diag,
+                        const int32_t* node_labels, int64_t* edges, int64_t edges_capacity, void* stream);
+/* profile int32 [capacity, 4]: every list entry writes {y, x, d2, rank_diag} at offsets[row] + rank (offsets int32 [n_rows]).
+ * tprofile int32 [tprofile_len, 5] = {y, x, d2, cum_orth, cum_diag}, the trunk profiles by the host's plan: seg int32 [n_rows, 4] =
+ * {first entry or -1, reversed, cum_orth and cum_diag at its first entry} per branch row, attach int32 [n_attach, 6] = {arena
+ * position, entry, y, x, cum_orth, cum_diag} per junction pixel between two branches.  trunkrows int64 [G, 8] = {px, sum_q8,
+ * max_d2, the position, y and x of its first occurrence, the last entry's cum_orth and cum_diag} of the entries tstart[g] ..
+ * tstart[g + 1] (tstart int32 [G + 1]).  Two launches; entries outside the buffers are dropped, not written. */
+int disyolo_trace_gather(const int32_t* groups_host, const int32_t* groups, int G, int64_t arena_bytes, const int32_t* ents,
+                         const int32_t* count, int64_t capacity, const int32_t* rank, const int32_t* rank_diag, const int32_t* d2,
+                         const int32_t* offsets, int64_t n_rows, int32_t* profile, const int32_t* seg, const int64_t* edges,
+                         const int32_t* attach, int64_t n_attach, int32_t* tprofile, int64_t tprofile_len, const int32_t* tstart,
+                         int64_t* trunkrows, void* stream);
 /* semantic-segmentation accuracy of evaluate (calculate_test_map.py:303-346): adds the 4x4 pixel
  * confusion counts of two uint8 class maps (0 = background, 1..3 = classes; other values are
  * ignored) to conf int64 [16], conf[true*4 + pred]; the caller zeroes conf before the first image
