@@ -219,6 +219,11 @@ _SIGS = {
     "disyolo_trace_gather": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64] +
                              [C.c_void_p] * 4 + [C.c_int64] + [C.c_void_p] * 4 + [C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
                                                                                  C.c_void_p, C.c_void_p]),
+    "disyolo_shape_sums": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "disyolo_shape_parts": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_void_p]),
+    "disyolo_shape_extents": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int,
+                                        C.c_void_p, C.c_void_p]),
     "disyolo_confusion16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "disyolo_confusion_n": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p]),
     "disyolo_paste_job_size": (C.c_size_t, []),
@@ -1470,6 +1475,47 @@ def trace_gather(groups, ents, count, rank, rank_diag, d2, offsets, profile, seg
                                        _p(rank_diag), _p(d2), _p(offsets), n_rows, _p(profile), _p(seg), _p(edges), _p(attach),
                                        int(attach.shape[0]), _p(tprofile), int(tprofile.shape[0]), _p(tstart), _p(trunkrows),
                                        _stream()), "trace_gather")
+
+
+SHAPE_COLS = 16        # int64 words of a row of disyolo_shape_sums
+
+
+def shape_sums(groups, arena, sums, groups_dev=None, arena_bytes: Optional[int] = None) -> None:
+    """sums int64 CUDA [G, SHAPE_COLS] = n, Sy, Sx, Syy, Sxx, Sxy, ymin, ymax, xmin, xmax, Q1, Q2, Q3, Q4, QD, 0 of the masks in
+    arena, initialised by the call (disyolo_shape_sums).  No synchronisation here."""
+    groups, groups_dev, nbytes = _measure_tables(groups, arena, groups_dev, arena_bytes, "shape_sums")
+    G = int(groups.shape[0])
+    _need(sums, torch.int64, "sums")
+    _need_shape(sums, (G, SHAPE_COLS), "sums")
+    _check(load().disyolo_shape_sums(groups.ctypes.data, _p(groups_dev), G, _p(arena), nbytes, _p(sums), _stream()), "shape_sums")
+
+
+def shape_parts(groups, arena, labels, px, parts, groups_dev=None, arena_bytes: Optional[int] = None) -> None:
+    """labels int32 CUDA: the part (the smallest pixel index of its 8-connected component) on foreground pixels, -1 on the
+    crop's other pixels; parts int64 CUDA [G, 2] = n_parts, largest_part_px; px int32 CUDA per pixel is scratch
+    (disyolo_shape_parts).  No synchronisation here."""
+    groups, groups_dev, nbytes = _measure_tables(groups, arena, groups_dev, arena_bytes, "shape_parts")
+    G = int(groups.shape[0])
+    _need_elems(labels, torch.int32, nbytes, "labels")
+    _need_elems(px, torch.int32, nbytes, "px")
+    _need(parts, torch.int64, "parts")
+    _need_shape(parts, (G, 2), "parts")
+    _check(load().disyolo_shape_parts(groups.ctypes.data, _p(groups_dev), G, _p(arena), nbytes, _p(labels), _p(px), _p(parts),
+                                      _stream()), "shape_parts")
+
+
+def shape_extents(groups, arena, dirs, pminmax, groups_dev=None, dirs_dev=None, arena_bytes: Optional[int] = None) -> None:
+    """pminmax int32 CUDA [G, K, 2]: the minimum and maximum of c_k x + s_k y over every mask for the directions dirs int32
+    [K, 2] (host, checked before the launch; its device copy may be passed in) (disyolo_shape_extents).  No synchronisation
+    here."""
+    groups, groups_dev, nbytes = _measure_tables(groups, arena, groups_dev, arena_bytes, "shape_extents")
+    G = int(groups.shape[0])
+    dirs, dirs_dev = _table(np.asarray(dirs, np.int32).reshape(-1, 2), 2, "dirs", dirs_dev, arena.device)
+    K = int(dirs.shape[0])
+    _need(pminmax, torch.int32, "pminmax")
+    _need_shape(pminmax, (G, K, 2), "pminmax")
+    _check(load().disyolo_shape_extents(groups.ctypes.data, _p(groups_dev), G, _p(arena), nbytes, dirs.ctypes.data, _p(dirs_dev), K,
+                                        _p(pminmax), _stream()), "shape_extents")
 
 
 def polygon_mask(px, py, poly_start, poly_is_out, image_h: int, image_w: int, mask) -> None:

@@ -58,12 +58,35 @@ never on a shortest path); of two arms between the same two nodes the shorter is
 measured straight from attach pixel to attach pixel; an instance of closed loops only has its heaviest loop as trunk.  Host
 synchronisations of skeleton_trace: one read of the edge and node tables, one of the trunk rows.
 
+The shape of an instance (csrc/shape.hip, defined by tests/shape_ref.py) needs no skeleton: it reads the
+mask arena alone, so it takes a ``TiledDetections`` as well as anything above:
+
+    s = instance_shapes(detect_tiled(net, image_rgb), mm_per_px=0.25, axis_deg=0.0)
+    s.orientation_deg, s.rect_long_px, s.rect_short_px, s.rect_angle_deg, s.perimeter_px, s.n_parts, s.n_holes, s.direction
+    s.extents(g), s.rect_corners(g), s.part_labels(g), s.table(class_names)
+
+  sums      n, Sy, Sx, Syy, Sxx, Sxy over the mask, its tight box and Gray's bit quads Q1, Q2, Q3, Q4, QD: the raw int64 table.
+            From it the centroid, the orientation of the major axis (image axes, from +x towards +y, y down: np.eye(9) lies at 45
+            degrees), the axes of the ellipse with the same moments, the perimeter Q2 + (Q1 + Q3 + 2 QD) / sqrt(2), the exact count
+            of pixel sides ``edges`` and the Euler number;
+  parts     the 8-connected components (labels = their smallest pixel index), how many and the largest: whether the merge joined
+            one piece or five fragments; n_holes = n_parts - euler8 counts the 4-connected holes;
+  extents   the minimum and maximum of c x + s y over the mask for K directions (a fixed-point table made on the host): Feret
+            diameters and the smallest of the K / 2 enclosing rectangles, with its long and short side, angle and corners;
+  direction longitudinal / transverse / diagonal against the member's axis ``axis_deg``, "none" for a blob that is not elongated.
+
+What the rules do to the numbers: the rectangle is the best of K / 2 orientations, not the true minimum (K = 180: the long side of
+a bar is overestimated by at most short * sin 1 degree); feret_max of a 1 x 9 bar is 9.06 at 6 degrees, the diagonal of the pixel
+squares; a diagonal gap closes a hole's wall but does not join two holes.  Host synchronisations of instance_shapes: one read of
+the three tables at the end; G = 0, or groups without pixels, launch nothing and read nothing.
+
 Working memory of skeleton_graph beside what measure_arena holds: two int32 arenas (labels, row numbers), two byte arenas
 (links, the pruned skeleton) and the row buffer.  Its host synchronisations: one read per analysis (the row counter and the
 per-group spur flags in one copy; once more if the row buffer was too small) and the final copy.
 """
 from __future__ import annotations
 
+import math
 from typing import List, Optional, Sequence
 
 import numpy as np
@@ -676,6 +699,264 @@ def skeleton_trace(g: SkeletonGraphs, mm_per_px=None, node_labels_out=None, rank
     return SkeletonTraces(g, node_labels, rank, rank_diag, ntab, edges, profile, ints, paths, tprofile, tstart, mm_per_px)
 
 
+# ---- the shape of an instance: orientation, oriented extent, perimeter, parts and holes ---------------------------------------
+SHAPE_COLUMNS = ("n", "Sy", "Sx", "Syy", "Sxx", "Sxy", "ymin", "ymax", "xmin", "xmax", "Q1", "Q2", "Q3", "Q4", "QD", "zero")
+SHAPE_UNIT = 16384                    # a direction's (c, s) and every extent are in 2^-14
+SHAPE_INTS = ("area_px", "n_parts", "largest_part_px", "euler8", "n_holes", "edges", "rect_k")
+SHAPE_FLOATS = ("centroid_y", "centroid_x", "orientation_deg", "axis_major_px", "axis_minor_px", "elongation", "feret_max_px",
+                "feret_max_deg", "feret_min_px", "feret_min_deg", "rect_long_px", "rect_short_px", "rect_angle_deg", "rect_area_px2",
+                "perimeter_px", "compactness", "solidity_rect")
+SHAPE_LENGTHS = ("axis_major", "axis_minor", "feret_max", "feret_min", "rect_long", "rect_short", "perimeter")
+_INT32_MAX, _INT32_MIN = 2 ** 31 - 1, -2 ** 31
+
+
+def shape_directions(K) -> np.ndarray:
+    """int32 [K, 2]: (round(16384 cos(k pi / K)), round(16384 sin(k pi / K))), the table the extents are taken along"""
+    if isinstance(K, (bool, np.bool_)) or not isinstance(K, (int, np.integer)) or not 2 <= int(K) <= 360 or int(K) % 2:
+        raise ValueError("directions must be an even int in 2 .. 360 (got %r)" % (K,))
+    K = int(K)
+    return np.array([[round(SHAPE_UNIT * math.cos(k * math.pi / K)), round(SHAPE_UNIT * math.sin(k * math.pi / K))] for k in range(K)], np.int32)
+
+
+def _shape_read(t: torch.Tensor) -> np.ndarray:
+    """a copy to the host: the one host synchronisation of instance_shapes goes through here"""
+    return t.cpu().numpy()
+
+
+def shape_ext(pminmax, dirs) -> np.ndarray:
+    """int64 [K]: max - min + |c| + |s| per direction (2^-14 px; a pixel is a unit square), 0 for an empty crop"""
+    pm, d = np.asarray(pminmax, np.int64), np.asarray(dirs, np.int64)
+    return np.where(pm[:, 1] >= pm[:, 0], pm[:, 1] - pm[:, 0] + np.abs(d[:, 0]) + np.abs(d[:, 1]), 0)
+
+
+def direction_kind(orientation_deg, elongation, axis_deg, axis_tol_deg=22.5, min_elongation=1.5) -> str:
+    if elongation < min_elongation:
+        return "none"
+    delta = abs(((orientation_deg - axis_deg + 90.0) % 180.0) - 90.0)
+    return "longitudinal" if delta <= axis_tol_deg else "transverse" if delta >= 90.0 - axis_tol_deg else "diagonal"
+
+
+def derive_shape(s, p, pminmax, dirs, origin=(0, 0), mm_per_px=None, axis_deg=None, axis_tol_deg=22.5, min_elongation=1.5) -> dict:
+    """The columns of one instance from its integers (s int [16], SHAPE_COLUMNS; p = n_parts, largest_part_px; pminmax, dirs int
+    [K, 2]; origin = the box's y1, x1): exact Python ints until the last step of every column, then float64.  The expressions are
+    those of tests/shape_ref.py, derive: the two agree bit for bit."""
+    n, Sy, Sx, Syy, Sxx, Sxy = (int(v) for v in s[:6])
+    q1, q2, q3, q4, qd = (int(v) for v in s[10:15])
+    K = len(dirs)
+    e8 = (q1 - q3 - 2 * qd) // 4
+    out = {"area_px": n, "n_parts": int(p[0]), "largest_part_px": int(p[1]), "euler8": e8, "n_holes": int(p[0]) - e8,
+           "edges": q1 + q2 + q3 + 2 * qd}
+    if n == 0:
+        out.update({c: 0.0 for c in SHAPE_FLOATS})
+        out.update(rect_k=0, rect_center=np.zeros(2), rect_corners=np.zeros((4, 2)))
+    else:
+        out["centroid_y"], out["centroid_x"] = Sy / n, Sx / n
+        Mxx, Myy, Mxy = n * Sxx - Sx * Sx, n * Syy - Sy * Sy, n * Sxy - Sx * Sy
+        o = math.degrees(0.5 * math.atan2(2 * Mxy, Mxx - Myy)) % 180.0
+        out["orientation_deg"] = 0.0 if o >= 180.0 else o
+        a, b, c = Mxx / (n * n) + 1.0 / 12.0, Mxy / (n * n), Myy / (n * n) + 1.0 / 12.0
+        l1 = 0.5 * (a + c) + math.hypot(0.5 * (a - c), b)
+        l2 = (a * c - b * b) / l1
+        out["axis_major_px"], out["axis_minor_px"], out["elongation"] = 4.0 * math.sqrt(l1), 4.0 * math.sqrt(l2), math.sqrt(l1 / l2)
+        ext = [int(v) for v in shape_ext(pminmax, dirs)]
+        kmax, kmin = ext.index(max(ext)), ext.index(min(ext))
+        out["feret_max_px"], out["feret_max_deg"] = ext[kmax] / SHAPE_UNIT, 180.0 * kmax / K
+        out["feret_min_px"], out["feret_min_deg"] = ext[kmin] / SHAPE_UNIT, 180.0 * kmin / K
+        prod = [ext[k] * ext[k + K // 2] for k in range(K // 2)]
+        k0 = prod.index(min(prod))
+        k1 = k0 + K // 2
+        kl = k0 if ext[k0] >= ext[k1] else k1
+        out["rect_k"] = k0
+        out["rect_long_px"], out["rect_short_px"] = max(ext[k0], ext[k1]) / SHAPE_UNIT, min(ext[k0], ext[k1]) / SHAPE_UNIT
+        out["rect_angle_deg"], out["rect_area_px2"] = 180.0 * kl / K, prod[k0] / (SHAPE_UNIT * SHAPE_UNIT)
+        # the rectangle in the image: the two projections P0 = c0 x + s0 y, P1 = c1 x + s1 y inverted
+        (c0, s0), (c1, s1) = (int(v) for v in dirs[k0]), (int(v) for v in dirs[k1])
+        h0, h1 = 0.5 * (abs(c0) + abs(s0)), 0.5 * (abs(c1) + abs(s1))
+        lo0, hi0 = int(pminmax[k0][0]) - h0, int(pminmax[k0][1]) + h0
+        lo1, hi1 = int(pminmax[k1][0]) - h1, int(pminmax[k1][1]) + h1
+        det = float(c0 * s1 - s0 * c1)
+        at = lambda P0, P1: (origin[0] + (c0 * P1 - c1 * P0) / det, origin[1] + (P0 * s1 - s0 * P1) / det)
+        out["rect_corners"] = np.array([at(lo0, lo1), at(hi0, lo1), at(hi0, hi1), at(lo0, hi1)], np.float64)
+        out["rect_center"] = np.array(at(0.5 * (lo0 + hi0), 0.5 * (lo1 + hi1)), np.float64)
+        per = q2 + (q1 + q3 + 2 * qd) / math.sqrt(2.0)
+        out["perimeter_px"], out["compactness"] = per, 4.0 * math.pi * n / (per * per)
+        out["solidity_rect"] = n / out["rect_area_px2"]
+    if mm_per_px is not None:
+        f = float(mm_per_px)
+        for c in SHAPE_LENGTHS:
+            out[c + "_mm"] = out[c + "_px"] * f
+        out["area_mm2"], out["rect_area_mm2"] = n * (f * f), out["rect_area_px2"] * (f * f)
+    if axis_deg is not None:
+        out["direction"] = direction_kind(out["orientation_deg"], out["elongation"], float(axis_deg), axis_tol_deg, min_elongation)
+    return out
+
+
+class InstanceShapes:
+    """What ``instance_shapes`` / ``shape_masks`` return.  For the G instances:
+      sums int64 [G,16] (SHAPE_COLUMNS), parts int64 [G,2] = n_parts, largest_part_px, pminmax int32 [G,K,2], directions int32
+                [K,2]: the raw tables everything is derived from (numpy)
+      area_px, n_parts, largest_part_px, euler8, n_holes, edges, rect_k (int64 [G])
+      centroid_y, centroid_x (crop coordinates), orientation_deg, axis_major_px, axis_minor_px, elongation, feret_max_px,
+                feret_max_deg, feret_min_px, feret_min_deg, rect_long_px, rect_short_px, rect_angle_deg, rect_area_px2,
+                perimeter_px, compactness, solidity_rect (float64 [G]); rect_center float64 [G,2] (image y, x; a pixel's centre
+                is at its integer coordinates)
+      mm_per_px, and with it the _mm columns of every length, area_mm2 and rect_area_mm2
+      axis_deg, and with it direction, a list of "longitudinal" / "transverse" / "diagonal" / "none"
+      extents(g) float64 [K] in px; rect_corners(g) float64 [4,2] image y, x; part_labels(g) int32 CUDA view [bh,bw]
+      table(class_names) one dict per instance"""
+
+    def __init__(self, boxes, offsets, labels_arena, sums, parts, pminmax, dirs, mm_per_px=None, axis_deg=None, axis_tol_deg=22.5,
+                 min_elongation=1.5, classid=None, score=None):
+        self.boxes, self._offsets = np.asarray(boxes, np.int32).reshape(-1, 4), list(offsets)
+        self.labels_arena = labels_arena
+        self.directions = np.asarray(dirs, np.int32).reshape(-1, 2)
+        K, G = int(self.directions.shape[0]), int(self.boxes.shape[0])
+        self.sums = np.asarray(sums, np.int64).reshape(G, 16)
+        self.parts = np.asarray(parts, np.int64).reshape(G, 2)
+        self.pminmax = np.asarray(pminmax, np.int32).reshape(G, K, 2)
+        self.mm_per_px = None if mm_per_px is None else float(mm_per_px)
+        self.axis_deg = None if axis_deg is None else float(axis_deg)
+        self.axis_tol_deg, self.min_elongation = float(axis_tol_deg), float(min_elongation)
+        self.classid, self.score = classid, score
+        rows = [derive_shape(self.sums[g], self.parts[g], self.pminmax[g], self.directions, (int(self.boxes[g][0]), int(self.boxes[g][1])),
+                             self.mm_per_px, self.axis_deg, self.axis_tol_deg, self.min_elongation) for g in range(G)]
+        for c in SHAPE_INTS:
+            setattr(self, c, np.array([r[c] for r in rows], np.int64))
+        floats = list(SHAPE_FLOATS)
+        if self.mm_per_px is not None:
+            floats += [c + "_mm" for c in SHAPE_LENGTHS] + ["area_mm2", "rect_area_mm2"]
+        self._floats = tuple(floats)
+        for c in floats:
+            setattr(self, c, np.array([r[c] for r in rows], np.float64))
+        self.rect_center = np.array([r["rect_center"] for r in rows], np.float64).reshape(G, 2)
+        self._corners = np.array([r["rect_corners"] for r in rows], np.float64).reshape(G, 4, 2)
+        if self.axis_deg is not None:
+            self.direction = [r["direction"] for r in rows]
+
+    def __len__(self) -> int:
+        return int(self.boxes.shape[0])
+
+    def extents(self, g: int) -> np.ndarray:
+        return shape_ext(self.pminmax[g], self.directions) / float(SHAPE_UNIT)
+
+    def rect_corners(self, g: int) -> np.ndarray:
+        return self._corners[g].copy()
+
+    def part_labels(self, g: int) -> torch.Tensor:
+        y1, x1, y2, x2 = (int(v) for v in self.boxes[g])
+        n = (y2 - y1) * (x2 - x1)
+        return self.labels_arena[self._offsets[g]:self._offsets[g] + n].view(y2 - y1, x2 - x1)
+
+    def table(self, class_names: Optional[Sequence[str]] = None) -> List[dict]:
+        rows = []
+        for g in range(len(self)):
+            row = {"instance": g, "box": tuple(int(v) for v in self.boxes[g])}
+            if self.classid is not None:
+                k = int(self.classid[g])
+                row["class"] = class_names[k] if class_names is not None else k
+            if self.score is not None:
+                row["score"] = float(self.score[g])
+            row.update({c: int(getattr(self, c)[g]) for c in SHAPE_INTS if c != "rect_k"})
+            row.update({c: float(getattr(self, c)[g]) for c in self._floats})
+            row["rect_center_yx"] = (float(self.rect_center[g][0]), float(self.rect_center[g][1]))
+            if self.axis_deg is not None:
+                row["direction"] = self.direction[g]
+            rows.append(row)
+        return rows
+
+
+def _check_shape(directions, mm_per_px, axis_deg, axis_tol_deg, min_elongation) -> np.ndarray:
+    """-> the direction table"""
+    dirs = shape_directions(directions)
+    if mm_per_px is not None and not (np.isfinite(float(mm_per_px)) and float(mm_per_px) > 0.0):
+        raise ValueError("mm_per_px must be a positive number (got %r)" % (mm_per_px,))
+    if axis_deg is not None and not np.isfinite(float(axis_deg)):
+        raise ValueError("axis_deg must be a finite number (got %r)" % (axis_deg,))
+    if not 0.0 < float(axis_tol_deg) <= 45.0:
+        raise ValueError("axis_tol_deg must be in (0, 45] (got %r)" % (axis_tol_deg,))
+    if not float(min_elongation) >= 1.0:
+        raise ValueError("min_elongation must be at least 1 (got %r)" % (min_elongation,))
+    return dirs
+
+
+def shape_arena(groups, arena, arena_bytes=None, groups_dev=None, directions=180, mm_per_px=None, axis_deg=None, axis_tol_deg=22.5,
+                min_elongation=1.5, classid=None, score=None, labels_out=None) -> InstanceShapes:
+    """The shapes of the crops of an arena: groups int32 [G,8] and arena uint8 CUDA as ``lib.tile_compose`` takes and writes them
+    (a non-zero byte is foreground).  ``labels_out`` (int32 CUDA of at least arena_bytes elements) is used for the part labels
+    when given; its elements between two crops are left untouched.  The arena is only read."""
+    dirs = _check_shape(directions, mm_per_px, axis_deg, axis_tol_deg, min_elongation)
+    groups = np.ascontiguousarray(np.asarray(groups, np.int32).reshape(-1, 8))
+    G, K = int(groups.shape[0]), int(dirs.shape[0])
+    boxes = groups[:, 2:6]
+    offsets = [int(v) * 16 for v in groups[:, 7]]
+    rest = (dirs, mm_per_px, axis_deg, axis_tol_deg, min_elongation, classid, score)
+    if G == 0 or L.measure_blocks(groups) == 0:
+        # nothing to launch and nothing to read: the tables of crops without a pixel are known
+        dev = arena.device if torch.is_tensor(arena) else torch.device("cpu")
+        labels = torch.empty(0, dtype=torch.int32, device=dev) if labels_out is None else labels_out
+        sums = np.zeros((G, 16), np.int64)
+        sums[:, 6], sums[:, 7], sums[:, 8], sums[:, 9] = boxes[:, 2] - boxes[:, 0], -1, boxes[:, 3] - boxes[:, 1], -1
+        pm = np.empty((G, K, 2), np.int32)
+        pm[:, :, 0], pm[:, :, 1] = _INT32_MAX, _INT32_MIN
+        return InstanceShapes(boxes, offsets, labels, sums, np.zeros((G, 2), np.int64), pm, *rest)
+    dev = arena.device
+    nbytes = int(arena.numel()) if arena_bytes is None else int(arena_bytes)
+    if groups_dev is None:
+        groups_dev = torch.from_numpy(groups).to(dev)
+    n = max(nbytes, 1)
+    labels = torch.empty(n, dtype=torch.int32, device=dev) if labels_out is None else labels_out
+    px = torch.empty(n, dtype=torch.int32, device=dev)
+    sums = torch.empty(G, 16, dtype=torch.int64, device=dev)
+    parts = torch.empty(G, 2, dtype=torch.int64, device=dev)
+    pminmax = torch.empty(G, K, 2, dtype=torch.int32, device=dev)
+    L.shape_sums(groups, arena, sums, groups_dev, nbytes)
+    L.shape_parts(groups, arena, labels, px, parts, groups_dev, nbytes)
+    L.shape_extents(groups, arena, dirs, pminmax, groups_dev, None, nbytes)
+    # the one read: the three tables in one transfer (the int32 extrema travel in pairs as int64 words)
+    flat = _shape_read(torch.cat([sums.reshape(-1), parts.reshape(-1), pminmax.reshape(-1).view(torch.int64)]))
+    pm = np.ascontiguousarray(flat[18 * G:]).view(np.int32).reshape(G, K, 2)
+    return InstanceShapes(boxes, offsets, labels, flat[:16 * G].reshape(G, 16), flat[16 * G:18 * G].reshape(G, 2), pm, *rest)
+
+
+def instance_shapes(m, directions=180, mm_per_px=None, axis_deg=None, axis_tol_deg=22.5, min_elongation=1.5,
+                    labels_out=None) -> InstanceShapes:
+    """The shape of every instance of ``m``: an InstanceMeasures, a SkeletonGraphs or SkeletonTraces (their measures), or a
+    ``TiledDetections``, which is read directly -- shapes need no thinning.  ``directions``: K, an even int in 2 .. 360, the
+    directions the extents are taken along (180: one per degree).  ``mm_per_px`` defaults to the scale of ``m``; ``axis_deg``, the
+    member's longitudinal axis in the image (degrees from +x towards +y), adds the direction kind: longitudinal within
+    ``axis_tol_deg`` (in (0, 45]) of it, transverse within that of its normal, diagonal between, "none" for an instance whose
+    elongation is below ``min_elongation`` (>= 1).  ``m`` is not changed."""
+    if isinstance(m, SkeletonTraces):
+        m = m.graphs
+    if isinstance(m, SkeletonGraphs):
+        if mm_per_px is None:
+            mm_per_px = m.mm_per_px
+        m = m.measures
+    if isinstance(m, InstanceMeasures):
+        if mm_per_px is None:
+            mm_per_px = m.mm_per_px
+        if len(m) and (m.groups is None or m.arena is None):
+            _check_shape(directions, mm_per_px, axis_deg, axis_tol_deg, min_elongation)
+            raise ValueError("instance_shapes needs the InstanceMeasures of measure_arena / measure_instances / measure_masks")
+        groups = m.groups if m.groups is not None else np.zeros((0, 8), np.int32)
+        arena = m.arena if m.arena is not None else m.d2_arena.new_empty(0, dtype=torch.uint8)
+        return shape_arena(groups, arena, m.arena_bytes, m.groups_dev, directions, mm_per_px, axis_deg, axis_tol_deg, min_elongation,
+                           m.classid, m.score, labels_out)
+    if not all(hasattr(m, a) for a in ("groups", "groups_dev", "arena", "arena_bytes", "classid", "score")):
+        raise ValueError("instance_shapes needs an InstanceMeasures, a SkeletonGraphs, a SkeletonTraces or a TiledDetections (got %s)"
+                         % type(m).__name__)
+    if mm_per_px is None:
+        mm_per_px = getattr(m, "mm_per_px", None)
+    if len(m) == 0:
+        return shape_arena(np.zeros((0, 8), np.int32), m.arena, 0, None, directions, mm_per_px, axis_deg, axis_tol_deg, min_elongation,
+                           m.classid, m.score, labels_out)
+    if m.groups is None:
+        _check_shape(directions, mm_per_px, axis_deg, axis_tol_deg, min_elongation)
+        raise ValueError("instance_shapes needs the groups table of merge_tiles / detect_tiled")
+    return shape_arena(m.groups, m.arena, m.arena_bytes, m.groups_dev, directions, mm_per_px, axis_deg, axis_tol_deg, min_elongation,
+                       m.classid, m.score, labels_out)
+
+
 def pack_masks(masks, fill: int = 0, foreground: int = 1):
     """a list of 2-D bool / uint8 arrays or tensors -> (groups int32 [G,8] with boxes at the origin, arena uint8 numpy,
     arena_bytes): the layout ``lib.tile_compose`` writes.  ``fill`` goes to the bytes between the crops, ``foreground`` to
@@ -708,3 +989,19 @@ def measure_masks(masks, mm_per_px=None, chunk: int = 8, device=None) -> Instanc
     if len(masks) == 0:
         return measure_arena(groups, torch.empty(0, dtype=torch.uint8), 0, None, mm_per_px, chunk)
     return measure_arena(groups, torch.from_numpy(arena).to(device), arena_bytes, None, mm_per_px, chunk)
+
+
+def shape_masks(masks, directions=180, mm_per_px=None, axis_deg=None, axis_tol_deg=22.5, min_elongation=1.5, device=None,
+                labels_out=None) -> InstanceShapes:
+    """The shapes of a list of masks of any sizes (2-D bool or uint8, arrays or tensors), packed into one arena on the host and
+    uploaded in one copy: ``instance_shapes`` for users of the plain, non-tiled detector."""
+    _check_shape(directions, mm_per_px, axis_deg, axis_tol_deg, min_elongation)
+    masks = list(masks)
+    if device is None:
+        device = next((m.device for m in masks if torch.is_tensor(m) and m.is_cuda), torch.device("cuda:0"))
+    groups, arena, arena_bytes = pack_masks(masks)
+    if len(masks) == 0 or L.measure_blocks(groups) == 0:
+        return shape_arena(groups, torch.empty(0, dtype=torch.uint8), 0, None, directions, mm_per_px, axis_deg, axis_tol_deg,
+                           min_elongation, labels_out=labels_out)
+    return shape_arena(groups, torch.from_numpy(arena).to(device), arena_bytes, None, directions, mm_per_px, axis_deg, axis_tol_deg,
+                       min_elongation, labels_out=labels_out)

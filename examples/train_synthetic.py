@@ -5,7 +5,8 @@ inference net -> detections + instance masks for one image.
     python examples/train_synthetic.py [--steps 40] [--size 192 | --size 128x192] [--batch 4] [--out /tmp/disyolo_example] [--lock 62-64]
                                        [--classes crack,spall,rebar,stain,joint,void]
                                        [--max-boxes 100] [--max-det 100] [--anchors auto | --anchors w,h,w,h,... (9 pairs)]
-                                       [--tiled 500x700 [--measure [--mm-per-px 0.25] [--min-branch 10 [--trunk]]]] [--windows 600x800]
+                                       [--tiled 500x700 [--measure [--mm-per-px 0.25] [--min-branch 10 [--trunk]]] [--shape [--axis-deg 0]]]
+                                       [--windows 600x800]
 
 It mirrors what the reference's ``train_yolo3_mask.py:237-248`` (train) and ``calculate_test_map.py`` (test) do
 with a real dataset; swap ``synthetic_labels`` for ``disyolo_amd.pre_process.load_verify_contour(path, 'train')``
@@ -140,6 +141,23 @@ def print_measures(res, classes, mm_per_px, min_branch=None, trunk=False):
         print(line)
 
 
+def print_shapes(res, classes, mm_per_px, axis_deg=None):
+    """orientation, enclosing rectangle, perimeter, parts and holes of every merged instance, from the result's cropped masks
+    alone (no thinning); with ``axis_deg`` also whether it runs along, across or diagonal to the member's axis"""
+    from disyolo_amd.measure import instance_shapes
+    s = instance_shapes(res, mm_per_px=mm_per_px, axis_deg=axis_deg)
+    print("shapes of %d instances (%d directions):" % (len(s), len(s.directions)))
+    for row in s.table(classes):
+        line = "  %3d %-8s %.2f  area %7d px  at %5.1f deg  rect %7.1f x %6.1f px at %5.1f deg  perimeter %8.1f px  %2d parts (largest %d px)  %2d holes" % (
+            row["instance"], row["class"], row["score"], row["area_px"], row["orientation_deg"], row["rect_long_px"], row["rect_short_px"],
+            row["rect_angle_deg"], row["perimeter_px"], row["n_parts"], row["largest_part_px"], row["n_holes"])
+        if mm_per_px is not None:
+            line += "  |  rect %6.1f x %5.1f mm  perimeter %7.1f mm" % (row["rect_long_mm"], row["rect_short_mm"], row["perimeter_mm"])
+        if axis_deg is not None:
+            line += "  |  %s" % row["direction"]
+        print(line)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=40)
@@ -182,6 +200,12 @@ def main():
                     help="--min-branch: also trace every pruned graph (disyolo_amd.measure.skeleton_trace) and print the trunk of "
                          "every instance -- the path between its two farthest ends -- with its length, its widest point and where "
                          "in the image that is")
+    ap.add_argument("--shape", action="store_true",
+                    help="with --tiled: print orientation, enclosing rectangle, perimeter, parts and holes of every merged instance "
+                         "(disyolo_amd.measure.instance_shapes; --mm-per-px adds the columns in mm)")
+    ap.add_argument("--axis-deg", type=float, default=None, metavar="DEG",
+                    help="--shape: the member's longitudinal axis in the image, in degrees from +x towards +y; adds whether an "
+                         "instance runs longitudinal, transverse or diagonal to it")
     ap.add_argument("--windows", type=parse_size, default=None, metavar="HxW",
                     help="window training: the records are synthetic images of this size, larger than the net, and every "
                          "batch image is a net-size window of one of them at scale 1 (defect_train(placement='window')); at "
@@ -191,6 +215,10 @@ def main():
         ap.error("--min-branch extends the table of --measure: give --measure too")
     if args.trunk and args.min_branch is None:
         ap.error("--trunk traces the graph of --min-branch: give --min-branch too (0 prunes nothing)")
+    if args.shape and args.tiled is None:
+        ap.error("--shape describes the instances of detect_tiled: give --tiled HxW")
+    if args.axis_deg is not None and not args.shape:
+        ap.error("--axis-deg classifies the orientations of --shape: give --shape too")
     if args.measure and args.tiled is None and args.windows is None:
         ap.error("--measure measures the instances of detect_tiled: give --tiled HxW or --windows HxW")
     classes = [c.strip() for c in args.classes.split(",")]
@@ -259,6 +287,8 @@ def main():
                 classes[res.classid[g]], res.score[g], y1, x1, y2, x2, int(res.mask(g).sum()), sorted({t for t, _ in res.members[g]})))
         if args.measure:
             print_measures(res, classes, args.mm_per_px, args.min_branch, args.trunk)
+        if args.shape:
+            print_shapes(res, classes, args.mm_per_px, args.axis_deg)
         # the metric of the whole image against the records it was drawn from: every repeat of an instance is an instance
         from disyolo_amd.evaluate import MAP, evaluate
         from disyolo_amd.train_data import rasterize_instance

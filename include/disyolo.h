@@ -774,6 +774,35 @@ int disyolo_trace_gather(const int32_t* groups_host, const int32_t* groups, int 
                          const int32_t* offsets, int64_t n_rows, int32_t* profile, const int32_t* seg, const int64_t* edges,
                          const int32_t* attach, int64_t n_attach, int32_t* tprofile, int64_t tprofile_len, const int32_t* tstart,
                          int64_t* trunkrows, void* stream);
+/* ---- the shape of an instance: moment sums, tight box and bit quads; 8-connected parts; extents along K directions
+ * (csrc/shape.hip, measure.instance_shapes; defined by tests/shape_ref.py; integers only) ----
+ * groups, arena (arena_bytes), the check on the host copy before any launch, the layout of the per-pixel buffers (arena_bytes
+ * elements, the elements between two crops never read and never written) and G = 0 are as for disyolo_measure_*; a non-zero byte
+ * is foreground, everything outside a crop background.  None allocates or synchronises; no block waits for another; integer
+ * atomics only: exact and order-independent.
+ *
+ * sums int64 [G, 16] = {n, Sy, Sx, Syy, Sxx, Sxy, ymin, ymax, xmin, xmax, Q1, Q2, Q3, Q4, QD, 0}, initialised here (a group
+ * without foreground keeps ymin, ymax, xmin, xmax = bh, -1, bw, -1): the sums over the foreground of a pixel's crop coordinates
+ * and their products, the tight box (inclusive), and the bit quads over the (bh + 1)(bw + 1) 2x2 windows of the crop padded by a
+ * ring of background -- the windows with one / three / four pixels set, QD two on a diagonal, Q2 two otherwise.  With sides
+ * <= 32767 every sum fits int64.  Two launches: the rows, then one over the arena in which a block walks 8 consecutive chunks of
+ * the plan and issues one atomic per group among them and column (for the box only where it changes the row). */
+int disyolo_shape_sums(const int32_t* groups_host, const int32_t* groups, int G, const uint8_t* arena, int64_t arena_bytes,
+                       int64_t* sums, void* stream);
+/* labels int32: on a foreground pixel the smallest index y bw + x of its 8-connected part, -1 on every other pixel of the crop.
+ * parts int64 [G, 2] = {n_parts, largest_part_px} (zeroed here).  px int32 per pixel is scratch (a root's pixel count).  Five
+ * launches: init (a pixel starts at the first pixel of its row run within its wave's 64 pixels), merge (union-find as
+ * disyolo_skeleton_label, with path halving: the result does not depend on the order of arrival), flatten, count, roots. */
+int disyolo_shape_parts(const int32_t* groups_host, const int32_t* groups, int G, const uint8_t* arena, int64_t arena_bytes,
+                        int32_t* labels, int32_t* px, int64_t* parts, void* stream);
+/* pminmax int32 [G, K, 2] = the minimum and maximum over the foreground of c_k x + s_k y for the K directions dirs int32 [K, 2] =
+ * {c_k, s_k} (a unit vector in 2^-14; the table is made on the host, no kernel evaluates a cosine); (INT32_MAX, INT32_MIN) for a
+ * group without foreground.  dirs_host is checked before any launch: K even in 2 .. 360 and |c|, |s| <= 16384 (the projection
+ * then fits int32), otherwise DISYOLO_E_ARG.  Two launches: the rows, then one over the arena in which only boundary pixels
+ * (foreground with a background 4-neighbour, which hold the same extrema) are projected and a block issues at most 2 K atomics,
+ * none where the row already holds a value as good. */
+int disyolo_shape_extents(const int32_t* groups_host, const int32_t* groups, int G, const uint8_t* arena, int64_t arena_bytes,
+                          const int32_t* dirs_host, const int32_t* dirs, int K, int32_t* pminmax, void* stream);
 /* semantic-segmentation accuracy of evaluate (calculate_test_map.py:303-346): adds the 4x4 pixel
  * confusion counts of two uint8 class maps (0 = background, 1..3 = classes; other values are
  * ignored) to conf int64 [16], conf[true*4 + pred]; the caller zeroes conf before the first image
