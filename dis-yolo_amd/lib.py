@@ -224,6 +224,12 @@ _SIGS = {
                                       C.c_void_p]),
     "disyolo_shape_extents": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int,
                                         C.c_void_p, C.c_void_p]),
+    "disyolo_outline_edges": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64] + [C.c_void_p] * 6 +
+                              [C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "disyolo_outline_loops": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64] + [C.c_void_p] * 7 +
+                              [C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "disyolo_outline_gather": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                         C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
     "disyolo_confusion16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "disyolo_confusion_n": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p]),
     "disyolo_paste_job_size": (C.c_size_t, []),
@@ -1516,6 +1522,74 @@ def shape_extents(groups, arena, dirs, pminmax, groups_dev=None, dirs_dev=None, 
     _need_shape(pminmax, (G, K, 2), "pminmax")
     _check(load().disyolo_shape_extents(groups.ctypes.data, _p(groups_dev), G, _p(arena), nbytes, dirs.ctypes.data, _p(dirs_dev), K,
                                         _p(pminmax), _stream()), "shape_extents")
+
+
+OUTLINE_ROW = 12       # int64 words of a loop's row of disyolo_outline_loops
+OUTLINE_PLAN = 8       # int32 words of a loop's plan for disyolo_outline_gather
+OUTLINE_WORK = 10      # int64 words of work per list entry
+OUTLINE_MAX_LIST = 2 ** 30 - 1
+
+
+def _outline_list(ekey, nxt, flag, aterm, work) -> int:
+    """the per-entry buffers of an edge list -> its capacity"""
+    _need(ekey, torch.int32, "ekey")
+    cap = int(ekey.numel())
+    if nxt is not None:
+        _need_elems(nxt, torch.int32, cap, "nxt")
+    _need_elems(flag, torch.uint8, cap, "flag")
+    if aterm is not None:
+        _need_elems(aterm, torch.int32, cap, "aterm")
+    if work is not None:
+        _need_elems(work, torch.int64, OUTLINE_WORK * cap, "work")
+    return cap
+
+
+def outline_edges(groups, arena, first, sides, ekey, nxt, flag, aterm, work, ctrl, groups_dev=None, arena_bytes: Optional[int] = None) -> None:
+    """The boundary edges of every mask, listed: first int32 and sides uint8 CUDA in the arena's layout, ekey, nxt, aterm int32 and
+    flag uint8 CUDA per list entry (the capacity is ekey's length), work int64 CUDA of OUTLINE_WORK words per entry, ctrl int32
+    CUDA [4], zeroed by the call (disyolo_outline_edges).  No synchronisation here."""
+    groups, groups_dev, nbytes = _measure_tables(groups, arena, groups_dev, arena_bytes, "outline_edges")
+    _need_elems(first, torch.int32, nbytes, "first")
+    _need_elems(sides, torch.uint8, nbytes, "sides")
+    cap = _outline_list(ekey, nxt, flag, aterm, work)
+    _need_elems(ctrl, torch.int32, 4, "ctrl")
+    _check(load().disyolo_outline_edges(groups.ctypes.data, _p(groups_dev), int(groups.shape[0]), _p(arena), nbytes, _p(first), _p(sides),
+                                        _p(ekey), _p(nxt), _p(flag), _p(aterm), cap, _p(work), int(work.numel()), _p(ctrl), _stream()),
+           "outline_edges")
+
+
+def outline_loops(groups, arena, part_labels, first, sides, ekey, nxt, flag, aterm, rounds: int, work, eidx, rows, ctrl, groups_dev=None,
+                  arena_bytes: Optional[int] = None) -> None:
+    """After ``outline_edges`` on the same buffers: rows int64 CUDA [L, OUTLINE_ROW], one per loop in the order of arrival, and
+    eidx int32 CUDA [capacity, 3]; part_labels = the labels of ``shape_parts``; 2^rounds must reach the longest loop's edges
+    (disyolo_outline_loops).  No synchronisation here."""
+    groups, groups_dev, nbytes = _measure_tables(groups, arena, groups_dev, arena_bytes, "outline_loops")
+    _need_elems(part_labels, torch.int32, nbytes, "part_labels")
+    _need_elems(first, torch.int32, nbytes, "first")
+    _need_elems(sides, torch.uint8, nbytes, "sides")
+    cap = _outline_list(ekey, nxt, flag, aterm, work)
+    _need_elems(eidx, torch.int32, 3 * cap, "eidx")
+    _need_table(rows, torch.int64, OUTLINE_ROW, "rows")
+    _need_elems(ctrl, torch.int32, 4, "ctrl")
+    _check(load().disyolo_outline_loops(groups.ctypes.data, _p(groups_dev), int(groups.shape[0]), _p(arena), nbytes, _p(part_labels),
+                                        _p(first), _p(sides), _p(ekey), _p(nxt), _p(flag), _p(aterm), cap, int(rounds), _p(work),
+                                        int(work.numel()), _p(eidx), _p(rows), int(rows.shape[0]), _p(ctrl), _stream()), "outline_loops")
+
+
+def outline_gather(groups, arena, ekey, flag, eidx, ctrl, plan, points, corners, groups_dev=None, arena_bytes: Optional[int] = None) -> None:
+    """After ``outline_loops``: plan int32 CUDA [L, OUTLINE_PLAN] per row of its rows; points int32 CUDA [N, 2] and corners int32
+    CUDA [C, 2] take the chains and rings in image (x, y) (disyolo_outline_gather).  The arena is not read.  No synchronisation
+    here."""
+    groups, groups_dev, nbytes = _measure_tables(groups, arena, groups_dev, arena_bytes, "outline_gather")
+    cap = _outline_list(ekey, None, flag, None, None)
+    _need_elems(eidx, torch.int32, 3 * cap, "eidx")
+    _need_elems(ctrl, torch.int32, 4, "ctrl")
+    _need_table(plan, torch.int32, OUTLINE_PLAN, "plan")
+    _need_table(points, torch.int32, 2, "points")
+    _need_table(corners, torch.int32, 2, "corners")
+    _check(load().disyolo_outline_gather(groups.ctypes.data, _p(groups_dev), int(groups.shape[0]), nbytes, _p(ekey), _p(flag), _p(eidx),
+                                         cap, _p(ctrl), _p(plan), int(plan.shape[0]), _p(points), int(points.shape[0]), _p(corners),
+                                         int(corners.shape[0]), _stream()), "outline_gather")
 
 
 def polygon_mask(px, py, poly_start, poly_is_out, image_h: int, image_w: int, mask) -> None:

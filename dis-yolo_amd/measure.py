@@ -80,6 +80,22 @@ a bar is overestimated by at most short * sin 1 degree); feret_max of a 1 x 9 ba
 squares; a diagonal gap closes a hole's wall but does not join two holes.  Host synchronisations of instance_shapes: one read of
 the three tables at the end; G = 0, or groups without pixels, launch nothing and read nothing.
 
+The outlines of an instance (csrc/outline.hip, defined by tests/outline_ref.py) turn it back into what
+annotation tools and the loader exchange: closed borders.
+
+    o = instance_outlines(s)            # s = instance_shapes(...), or anything instance_shapes takes
+    o.loops, o.loops_of(g), o.points(i), o.corners(i), o.parts, o.polygons(g), o.record(image_size=(h, w)), o.table(class_names)
+
+  loop      a cycle of the successor permutation of the boundary edges (pixel sides between foreground and background, walked
+            clockwise, the diagonal tested first: 8-connected foreground); outer borders and holes, each with its depth and parent;
+  points    the pixel border as cv2.findContours(RETR_TREE, CHAIN_APPROX_NONE) lists it, start point included;
+  corners   the ring of turning corners on the corner grid, whose shoelace sum is exactly twice the enclosed area;
+  record    the polygons sorted by (depth, key): 'out' and 'in' alternate with the depth, so an island in a hole is drawn after
+            the hole -- with all 'out' before all 'in' the loader loses it.
+
+Host synchronisations of instance_outlines with an InstanceShapes given: one read of the loop table, one of the points and
+corners (none with points=False); G = 0, or masks without a pixel, launch nothing and read nothing.
+
 Working memory of skeleton_graph beside what measure_arena holds: two int32 arenas (labels, row numbers), two byte arenas
 (links, the pruned skeleton) and the row buffer.  Its host synchronisations: one read per analysis (the row counter and the
 per-group spur flags in one copy; once more if the row buffer was too small) and the final copy.
@@ -898,7 +914,10 @@ def shape_arena(groups, arena, arena_bytes=None, groups_dev=None, directions=180
         sums[:, 6], sums[:, 7], sums[:, 8], sums[:, 9] = boxes[:, 2] - boxes[:, 0], -1, boxes[:, 3] - boxes[:, 1], -1
         pm = np.empty((G, K, 2), np.int32)
         pm[:, :, 0], pm[:, :, 1] = _INT32_MAX, _INT32_MIN
-        return InstanceShapes(boxes, offsets, labels, sums, np.zeros((G, 2), np.int64), pm, *rest)
+        out = InstanceShapes(boxes, offsets, labels, sums, np.zeros((G, 2), np.int64), pm, *rest)
+        out.groups, out.groups_dev, out.arena = groups, groups_dev, arena
+        out.arena_bytes = (int(arena.numel()) if torch.is_tensor(arena) else 0) if arena_bytes is None else int(arena_bytes)
+        return out
     dev = arena.device
     nbytes = int(arena.numel()) if arena_bytes is None else int(arena_bytes)
     if groups_dev is None:
@@ -915,7 +934,9 @@ def shape_arena(groups, arena, arena_bytes=None, groups_dev=None, directions=180
     # the one read: the three tables in one transfer (the int32 extrema travel in pairs as int64 words)
     flat = _shape_read(torch.cat([sums.reshape(-1), parts.reshape(-1), pminmax.reshape(-1).view(torch.int64)]))
     pm = np.ascontiguousarray(flat[18 * G:]).view(np.int32).reshape(G, K, 2)
-    return InstanceShapes(boxes, offsets, labels, flat[:16 * G].reshape(G, 16), flat[16 * G:18 * G].reshape(G, 2), pm, *rest)
+    out = InstanceShapes(boxes, offsets, labels, flat[:16 * G].reshape(G, 16), flat[16 * G:18 * G].reshape(G, 2), pm, *rest)
+    out.groups, out.groups_dev, out.arena, out.arena_bytes = groups, groups_dev, arena, nbytes       # (what instance_outlines reads)
+    return out
 
 
 def instance_shapes(m, directions=180, mm_per_px=None, axis_deg=None, axis_tol_deg=22.5, min_elongation=1.5,
@@ -1005,3 +1026,243 @@ def shape_masks(masks, directions=180, mm_per_px=None, axis_deg=None, axis_tol_d
                            min_elongation, labels_out=labels_out)
     return shape_arena(groups, torch.from_numpy(arena).to(device), arena_bytes, None, directions, mm_per_px, axis_deg, axis_tol_deg,
                        min_elongation, labels_out=labels_out)
+
+
+# ---- the outlines of an instance: ordered borders, holes, loader records -----------------------------------------------------------
+OUTLINE_COLUMNS = ("instance", "kind", "depth", "parent", "part", "key_px", "key_side", "n_edges", "n_points", "n_corners", "area2")
+OUTLINE_PART_COLUMNS = ("instance", "part", "area_px", "n_holes")
+
+
+def _outline_read(t: torch.Tensor) -> np.ndarray:
+    """a copy to the host: every host synchronisation of instance_outlines goes through here"""
+    return t.cpu().numpy()
+
+
+def _outline_bad(what: str):
+    return L.DisyoloError("instance_outlines: the loop table does not describe the shapes (%s)" % what)
+
+
+def order_loops(rows):
+    """The rows of ``lib.outline_loops`` (int64 [L, 12], in any order) -> (table int64 [L, 11] (OUTLINE_COLUMNS) sorted by
+    (instance, depth, key), order int64 [L] = the row of ``rows`` behind every row of the table).  The nesting follows the rule
+    tests/outline_ref.py asserts against point-in-ring: a hole's parent is the outer loop of its part; an outer loop's parent is
+    the loop through the E side of the first foreground pixel west of its key pixel if that is a hole, otherwise that loop's
+    parent (a sibling further west: a smaller key, so the chain ends); none without such a pixel."""
+    rows = np.asarray(rows, np.int64).reshape(-1, L.OUTLINE_ROW)
+    n = int(rows.shape[0])
+    by_key = np.lexsort((rows[:, 1], rows[:, 0]))
+    r = rows[by_key]
+    inst, key, area2, part, west = r[:, 0], r[:, 1], r[:, 5], r[:, 6], r[:, 7]
+    ident = (inst << 32) | key
+    kind = (area2 < 0).astype(np.int64)
+    if n and ((area2 == 0).any() or (key < 0).any() or (np.diff(ident) <= 0).any() or (key % 4 != 2 * kind).any()):
+        raise _outline_bad("keys")
+
+    def find(i, k):
+        at = np.minimum(np.searchsorted(ident, (i << 32) | k), max(n - 1, 0))
+        if len(at) and (ident[at] != ((i << 32) | k)).any():
+            raise _outline_bad("a loop names one that is not there")
+        return at
+
+    parent = np.full(n, -1, np.int64)
+    holes = np.flatnonzero(kind == 1)
+    parent[holes] = find(inst[holes], 4 * part[holes])
+    outer = np.flatnonzero((kind == 0) & (west >= 0))
+    met = find(inst[outer], west[outer])
+    if (met >= outer).any() or (parent[holes] >= holes).any():
+        raise _outline_bad("nesting")
+    for i, w in zip(outer.tolist(), met.tolist()):                   # (ascending keys: the sibling to the west is resolved)
+        parent[i] = w if kind[w] == 1 else parent[w]
+    depth = np.zeros(n, np.int64)
+    for _ in range(n):
+        deeper = np.where(parent >= 0, depth[parent] + 1, 0)
+        if np.array_equal(deeper, depth):
+            break
+        depth = deeper
+    if (depth % 2 != kind).any():
+        raise _outline_bad("depths")
+    final = np.lexsort((key, depth, inst))
+    pos = np.empty(n, np.int64)
+    pos[final] = np.arange(n)
+    table = np.stack([inst, kind, depth, np.where(parent >= 0, pos[np.maximum(parent, 0)], -1), part, key // 4, key % 4, r[:, 2], r[:, 3],
+                      r[:, 4], area2], axis=1)[final].reshape(n, len(OUTLINE_COLUMNS))
+    return table, by_key[final]
+
+
+class InstanceOutlines:
+    """What ``instance_outlines`` / ``outline_masks`` return.  For the L loops (closed borders) of the G instances:
+      loops     int64 [L, 11] (OUTLINE_COLUMNS): instance, kind (0 an outer border, 1 a hole), depth (the loops around it), parent
+                (a row of this table or -1), part (the smallest pixel index of its 8-connected part in the crop), key_px and
+                key_side (its smallest edge: pixel index in the crop and 0 = N .. 3 = W), n_edges (pixel sides), n_points,
+                n_corners, area2 (twice the enclosed area, negative for a hole); sorted by (instance, depth, key)
+      loops_of(g)   the rows of instance g;  point_offsets, corner_offsets int64 [L + 1]
+      points(i)     int32 [n_points, 2] (x, y), image coordinates: the pixel border of loop i as cv2.findContours(RETR_TREE,
+                CHAIN_APPROX_NONE) lists it, start point included
+      corners(i)    int32 [n_corners, 2] (x, y): the ring of turning corners on the corner grid, image coordinates -- pixel (x, y)
+                covers [x, x + 1] x [y, y + 1], so a corner c lies at c - 0.5 in the convention where a pixel's centre has integer
+                coordinates; its shoelace sum is area2
+      points_dev, corners_dev   the same int32 CUDA arrays [N, 2] and [C, 2], every loop at its offset (None with points=False)
+      parts     int64 [P, 4] (OUTLINE_PART_COLUMNS): per instance and 8-connected part its area and its holes
+      polygons(g)   the loader's dicts {'type': 'out' | 'in', 'all_points_x', 'all_points_y'} of instance g in record order: the
+                order matters, an island in a hole is drawn after the hole
+      record(image=, image_size=, class_names=)   what ``train_data.defect_train`` takes;  table(class_names)  one dict per loop"""
+
+    def __init__(self, shapes, loops, points=None, corners=None, points_dev=None, corners_dev=None):
+        self.shapes, self.boxes, self.classid, self.score = shapes, shapes.boxes, shapes.classid, shapes.score
+        self.loops = np.asarray(loops, np.int64).reshape(-1, len(OUTLINE_COLUMNS))
+        self.point_offsets = np.concatenate([[0], np.cumsum(self.loops[:, 8])]).astype(np.int64)
+        self.corner_offsets = np.concatenate([[0], np.cumsum(self.loops[:, 9])]).astype(np.int64)
+        self._points, self._corners, self.points_dev, self.corners_dev = points, corners, points_dev, corners_dev
+        self._first = np.searchsorted(self.loops[:, 0], np.arange(len(shapes) + 1))
+        lp = self.loops
+        ident = (lp[:, 0] << 32) | lp[:, 4]
+        roots, inv = np.unique(ident, return_inverse=True)
+        area2, holes = np.zeros(len(roots), np.int64), np.zeros(len(roots), np.int64)
+        np.add.at(area2, inv, lp[:, 10])
+        np.add.at(holes, inv, lp[:, 1])
+        self.parts = np.stack([roots >> 32, roots & 0xffffffff, area2 // 2, holes], axis=1).reshape(-1, 4)
+
+    def __len__(self) -> int:
+        return int(self.boxes.shape[0])
+
+    def loops_of(self, g: int) -> np.ndarray:
+        return self.loops[self._first[g]:self._first[g + 1]]
+
+    def _rows_of(self, g: int) -> range:
+        return range(int(self._first[g]), int(self._first[g + 1]))
+
+    def points(self, i: int) -> np.ndarray:
+        if self._points is None:
+            raise ValueError("instance_outlines was called with points=False")
+        return self._points[self.point_offsets[i]:self.point_offsets[i + 1]]
+
+    def corners(self, i: int) -> np.ndarray:
+        if self._corners is None:
+            raise ValueError("instance_outlines was called with points=False")
+        return self._corners[self.corner_offsets[i]:self.corner_offsets[i + 1]]
+
+    def polygons(self, g: int) -> List[dict]:
+        out = []
+        for i in self._rows_of(g):
+            pts = self.points(i)
+            out.append({"type": "out" if self.loops[i, 2] % 2 == 0 else "in", "all_points_x": pts[:, 0].tolist(),
+                        "all_points_y": pts[:, 1].tolist()})
+        return out
+
+    def record(self, image=None, image_size=None, class_names: Optional[Sequence[str]] = None) -> dict:
+        """One record of the loader: the instances that have a border (an empty mask has no polygon, and the loader refuses an
+        instance that rasterises to nothing), their classes from ``classid`` (all class 0 without one), and ``image`` (RGB uint8
+        [H, W, 3]) or ``image_size`` = (h, w).  ``class_names``: the class list (default: the configured one)."""
+        if (image is None) == (image_size is None):
+            raise ValueError("record needs image or image_size, one of them")
+        if class_names is None:
+            from . import config as cfg
+            class_names = cfg.CLASSES
+        keep = [g for g in range(len(self)) if self._first[g + 1] > self._first[g]]
+        cls = [int(self.classid[g]) if self.classid is not None else 0 for g in keep]
+        rec = {"image": image} if image is not None else {"image_size": (int(image_size[0]), int(image_size[1]))}
+        rec["class_names"] = [class_names[k] for k in cls]
+        rec["polygons"] = [self.polygons(g) for g in keep]
+        return rec
+
+    def table(self, class_names: Optional[Sequence[str]] = None) -> List[dict]:
+        rows = []
+        for i, r in enumerate(self.loops):
+            row = {c: int(v) for c, v in zip(OUTLINE_COLUMNS, r)}
+            row["kind"] = "hole" if r[1] else "outer"
+            g = int(r[0])
+            row["box"] = tuple(int(v) for v in self.boxes[g])
+            if self.classid is not None:
+                k = int(self.classid[g])
+                row["class"] = class_names[k] if class_names is not None else k
+            row["area_px"] = abs(int(r[10])) / 2.0
+            rows.append(row)
+        return rows
+
+
+def _check_outline_sizes(arena_bytes: int, E: int) -> None:
+    if 4 * int(arena_bytes) >= 2 ** 31:
+        raise ValueError("instance_outlines: an arena of %d bytes (an edge's key is 4 (offset + pixel) + side: need 4 * arena_bytes < 2^31)"
+                         % arena_bytes)
+    if E > L.OUTLINE_MAX_LIST:
+        raise ValueError("instance_outlines: %d boundary edges (need fewer than 2^30)" % E)
+
+
+def instance_outlines(m, points: bool = True) -> InstanceOutlines:
+    """The outlines of every instance of ``m``: an ``InstanceShapes`` of ``instance_shapes`` / ``shape_arena`` / ``shape_masks``, or
+    anything ``instance_shapes`` takes (it is then called with directions=2).  The shapes say before any launch how many edges
+    and loops there are; the borders are cycles of a permutation of the boundary edges (csrc/outline.hip, defined by
+    tests/outline_ref.py).  ``points=False`` stops after the loop table.  Host synchronisations with an
+    InstanceShapes given: one read of the loop table, one of the points and corners; none for G = 0 or masks without a pixel."""
+    s = m if isinstance(m, InstanceShapes) else instance_shapes(m, directions=2)
+    if any(getattr(s, a, None) is None for a in ("groups", "arena", "arena_bytes")):
+        raise ValueError("instance_outlines needs the InstanceShapes of shape_arena / instance_shapes / shape_masks")
+    G = len(s)
+    E, n_loops = int(s.edges.sum()), int((s.n_parts + s.n_holes).sum())
+    nbytes = int(s.arena_bytes)
+    _check_outline_sizes(nbytes, E)
+    empty = np.zeros((0, 2), np.int32)
+    if G == 0 or E == 0:
+        return InstanceOutlines(s, np.zeros((0, len(OUTLINE_COLUMNS)), np.int64), empty if points else None, empty if points else None)
+    dev = s.arena.device
+    groups = s.groups
+    groups_dev = s.groups_dev if s.groups_dev is not None else torch.from_numpy(groups).to(dev)
+    i32 = lambda *shape: torch.empty(*shape, dtype=torch.int32, device=dev)
+    u8 = lambda *shape: torch.empty(*shape, dtype=torch.uint8, device=dev)
+    first, sides = i32(max(nbytes, 1)), u8(max(nbytes, 1))
+    ekey, nxt, aterm, flag, eidx = i32(E), i32(E), i32(E), u8(E), i32(E, 3)
+    work = torch.empty(L.OUTLINE_WORK * E, dtype=torch.int64, device=dev)
+    rows = torch.empty(n_loops, L.OUTLINE_ROW, dtype=torch.int64, device=dev)
+    ctrl = i32(4)
+    rounds = max(int(s.edges.max()) - 1, 0).bit_length()           # 2^rounds >= the edges of a group >= those of a loop of it
+    L.outline_edges(groups, s.arena, first, sides, ekey, nxt, flag, aterm, work, ctrl, groups_dev, nbytes)
+    L.outline_loops(groups, s.arena, s.labels_arena, first, sides, ekey, nxt, flag, aterm, rounds, work, eidx, rows, ctrl, groups_dev, nbytes)
+    flat = _outline_read(torch.cat([rows.reshape(-1), ctrl.view(torch.int64)]))
+    listed, taken, over, _ = (int(v) for v in np.ascontiguousarray(flat[-2:]).view(np.int32))
+    if over or listed != E or taken != n_loops:
+        raise _outline_bad("%d edges listed and %d loops found where the shapes give %d and %d%s"
+                           % (listed, taken, E, n_loops, ", a list overflowed" if over else ""))
+    raw = flat[:-2].reshape(n_loops, L.OUTLINE_ROW)
+    loops, order = order_loops(raw)
+    inst = loops[:, 0]
+    if n_loops and (inst.min() < 0 or inst.max() >= G):
+        raise _outline_bad("instances")
+    if not (np.array_equal(_sum_by(inst, 1 - loops[:, 1], G), s.n_parts) and np.array_equal(_sum_by(inst, loops[:, 1], G), s.n_holes)
+            and np.array_equal(_sum_by(inst, loops[:, 7], G), s.edges) and np.array_equal(_sum_by(inst, loops[:, 10], G), 2 * s.area_px)):
+        raise _outline_bad("the parts, holes, edges or areas per instance differ")
+    if not points:
+        return InstanceOutlines(s, loops)
+    out = InstanceOutlines(s, loops)
+    N, C = int(out.point_offsets[-1]), int(out.corner_offsets[-1])
+    if N > L.OUTLINE_MAX_LIST or C > L.OUTLINE_MAX_LIST:
+        raise _outline_bad("points")
+    plan = outline_plan(groups, out, raw, order)
+    pts, cor = i32(N, 2), i32(C, 2)
+    L.outline_gather(groups, s.arena, ekey, flag, eidx, ctrl, torch.from_numpy(plan).to(dev), pts, cor, groups_dev, nbytes)
+    both = _outline_read(torch.cat([pts.reshape(-1), cor.reshape(-1)]))
+    out._points, out._corners = both[:2 * N].reshape(N, 2), both[2 * N:].reshape(C, 2)
+    out.points_dev, out.corners_dev = pts, cor
+    return out
+
+
+def outline_plan(groups, out: InstanceOutlines, raw, order) -> np.ndarray:
+    """int32 [L, 8], what ``lib.outline_gather`` takes: per row of ``raw`` (the rows of ``lib.outline_loops`` as they arrived; ``order``
+    from ``order_loops``) where its loop's points and corners begin in the sorted output, the run its chain starts with and its
+    runs, and its crop's width, first arena element, x1 and y1"""
+    plan = np.zeros((len(order), L.OUTLINE_PLAN), np.int32)
+    gr = np.asarray(groups, np.int64).reshape(-1, 8)[out.loops[:, 0]]
+    plan[order] = np.stack([out.point_offsets[:-1], out.corner_offsets[:-1], raw[order, 10], raw[order, 9], gr[:, 5] - gr[:, 3],
+                            gr[:, 7] * 16, gr[:, 3], gr[:, 2]], axis=1).astype(np.int32)
+    return plan
+
+
+def _sum_by(inst, v, G) -> np.ndarray:
+    out = np.zeros(G, np.int64)
+    np.add.at(out, inst, v)
+    return out
+
+
+def outline_masks(masks, device=None) -> InstanceOutlines:
+    """The outlines of a list of masks of any sizes (2-D bool or uint8, arrays or tensors): ``instance_outlines`` on top of
+    ``pack_masks``, for users of the plain, non-tiled detector."""
+    return instance_outlines(shape_masks(masks, directions=2, device=device))

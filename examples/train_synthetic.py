@@ -5,7 +5,8 @@ inference net -> detections + instance masks for one image.
     python examples/train_synthetic.py [--steps 40] [--size 192 | --size 128x192] [--batch 4] [--out /tmp/disyolo_example] [--lock 62-64]
                                        [--classes crack,spall,rebar,stain,joint,void]
                                        [--max-boxes 100] [--max-det 100] [--anchors auto | --anchors w,h,w,h,... (9 pairs)]
-                                       [--tiled 500x700 [--measure [--mm-per-px 0.25] [--min-branch 10 [--trunk]]] [--shape [--axis-deg 0]]]
+                                       [--tiled 500x700 [--measure [--mm-per-px 0.25] [--min-branch 10 [--trunk]]] [--shape [--axis-deg 0]]
+                                                        [--outline [FILE.json]]]
                                        [--windows 600x800]
 
 It mirrors what the reference's ``train_yolo3_mask.py:237-248`` (train) and ``calculate_test_map.py`` (test) do
@@ -158,6 +159,28 @@ def print_shapes(res, classes, mm_per_px, axis_deg=None):
         print(line)
 
 
+def print_outlines(res, classes, image_hw, path):
+    """the loop table of ``instance_outlines`` and, with a path, the loader's record of the detections as JSON"""
+    import json
+    from disyolo_amd import measure
+    o = measure.instance_outlines(res)
+    print("outlines: %d loops of %d instances, %d border pixels, %d corners" % (len(o.loops), len(o), int(o.point_offsets[-1]),
+                                                                            int(o.corner_offsets[-1])))
+    print("  loop inst class    kind  depth parent   edges  points corners   area_px  first point")
+    for i, row in enumerate(o.table(classes)):
+        if i == 40:
+            print("  ... and %d more" % (len(o.loops) - 40))
+            break
+        x, y = (int(v) for v in o.points(i)[0])
+        print("  %4d %4d %-8s %-5s %5d %6d %7d %7d %7d %9.1f  (%d, %d)" % (
+            i, row["instance"], row["class"], row["kind"], row["depth"], row["parent"], row["n_edges"], row["n_points"], row["n_corners"],
+            row["area_px"], x, y))
+    if path:
+        with open(path, "w") as f:
+            json.dump(o.record(image_size=image_hw, class_names=classes), f)
+        print("outlines: the record of %d instances written to %s" % (len(set(o.loops[:, 0].tolist())), path))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=40)
@@ -206,6 +229,10 @@ def main():
     ap.add_argument("--axis-deg", type=float, default=None, metavar="DEG",
                     help="--shape: the member's longitudinal axis in the image, in degrees from +x towards +y; adds whether an "
                          "instance runs longitudinal, transverse or diagonal to it")
+    ap.add_argument("--outline", nargs="?", const="", default=None, metavar="FILE.json",
+                    help="with --tiled: print the ordered borders of every merged instance -- outer borders, holes, islands in "
+                         "holes (disyolo_amd.measure.instance_outlines) -- and, with a file name, write them as one record of the "
+                         "loader (image_size, class_names, polygons) to check in an annotation tool or to train on")
     ap.add_argument("--windows", type=parse_size, default=None, metavar="HxW",
                     help="window training: the records are synthetic images of this size, larger than the net, and every "
                          "batch image is a net-size window of one of them at scale 1 (defect_train(placement='window')); at "
@@ -217,6 +244,8 @@ def main():
         ap.error("--trunk traces the graph of --min-branch: give --min-branch too (0 prunes nothing)")
     if args.shape and args.tiled is None:
         ap.error("--shape describes the instances of detect_tiled: give --tiled HxW")
+    if args.outline is not None and args.tiled is None:
+        ap.error("--outline outlines the instances of detect_tiled: give --tiled HxW")
     if args.axis_deg is not None and not args.shape:
         ap.error("--axis-deg classifies the orientations of --shape: give --shape too")
     if args.measure and args.tiled is None and args.windows is None:
@@ -289,6 +318,8 @@ def main():
             print_measures(res, classes, args.mm_per_px, args.min_branch, args.trunk)
         if args.shape:
             print_shapes(res, classes, args.mm_per_px, args.axis_deg)
+        if args.outline is not None:
+            print_outlines(res, classes, (th, tw), args.outline)
         # the metric of the whole image against the records it was drawn from: every repeat of an instance is an instance
         from disyolo_amd.evaluate import MAP, evaluate
         from disyolo_amd.train_data import rasterize_instance

@@ -803,6 +803,42 @@ int disyolo_shape_parts(const int32_t* groups_host, const int32_t* groups, int G
  * none where the row already holds a value as good. */
 int disyolo_shape_extents(const int32_t* groups_host, const int32_t* groups, int G, const uint8_t* arena, int64_t arena_bytes,
                           const int32_t* dirs_host, const int32_t* dirs, int K, int32_t* pminmax, void* stream);
+/* ---- outlines of the crops of an arena (csrc/outline.hip; the definition is tests/outline_ref.py) --------------------------------
+ * A boundary edge is (p, s): a foreground pixel and a side 0 = N, 1 = E, 2 = S, 3 = W whose neighbour across it is background
+ * (outside the crop is background); its successor is the diagonal pixel ahead with side s - 1 if that pixel is foreground, else the
+ * pixel ahead with side s, else p with side s + 1.  The cycles of the successor are the borders.  All three calls take the groups
+ * table as disyolo_measure_d2 does and return DISYOLO_E_ARG for a bad table, a null pointer, 4 * arena_bytes >= 2^31 (an edge's key
+ * in the arena is 4 (off + p) + s) or a capacity of 2^30 or more; they launch nothing for G = 0 or a plan without a block.
+ *
+ * disyolo_outline_edges: the list.  first int32 and sides uint8 in the arena's layout = a pixel's first list entry (-1 without one)
+ * and the mask of its boundary sides; per entry (capacity of them, = the sum of the shapes' edges) ekey int32 = its key, nxt int32 =
+ * its successor's entry, flag uint8 = 1: its predecessor belongs to another pixel | 2: to another side, aterm int32 = its term of the
+ * shoelace sum.  work int64 [>= 10 * capacity].  ctrl int32 [4] (zeroed here) = the entries listed, the rows taken, bit 0: the list
+ * overflowed | bit 1: the rows did, 0: the host reads it with the rows, nothing faults, and every later kernel returns at once when
+ * a bit is set. */
+int disyolo_outline_edges(const int32_t* groups_host, const int32_t* groups, int G, const uint8_t* arena, int64_t arena_bytes,
+                          int32_t* first, uint8_t* sides, int32_t* ekey, int32_t* nxt, uint8_t* flag, int32_t* aterm,
+                          int64_t capacity, int64_t* work, int64_t work_elems, int32_t* ctrl, void* stream);
+/* the loops, after disyolo_outline_edges on the same buffers; part_labels = disyolo_shape_parts' labels of the arena.  rounds
+ * launches of min-propagation give every entry its loop's smallest key, the cycle is cut in front of that edge, and rounds launches
+ * of list ranking give the sums from an entry to the end: 2^rounds must reach the longest loop's edges.  rows int64
+ * [rows_capacity, 12], one per loop in the order the key edges arrived (an atomic counter, ctrl[1]) = instance, key = 4 p + s in its
+ * crop, n_edges, n_points, n_corners, area2 (> 0: an outer border), part, west = the key of the loop through the E side of the first
+ * foreground pixel west of an outer loop's key pixel (-1: none), the smallest key of an E side, the runs of one owner (0: one pixel),
+ * the run the chain starts with, 0.  eidx int32 [capacity, 3] = per entry its loop's row, its index among the loop's points and
+ * among its corners. */
+int disyolo_outline_loops(const int32_t* groups_host, const int32_t* groups, int G, const uint8_t* arena, int64_t arena_bytes,
+                          const int32_t* part_labels, const int32_t* first, const uint8_t* sides, const int32_t* ekey,
+                          const int32_t* nxt, const uint8_t* flag, const int32_t* aterm, int64_t capacity, int rounds, int64_t* work,
+                          int64_t work_elems, int32_t* eidx, int64_t* rows, int64_t rows_capacity, int32_t* ctrl, void* stream);
+/* the points and corners, after disyolo_outline_loops: plan int32 [rows_capacity, 8] per row of rows = where its points begin, where
+ * its corners begin, rows columns 10 and 9, its crop's width, first arena element, x1, y1.  points int32 [n_points, 2] = (x, y) of the
+ * pixel chain (cv2's CHAIN_APPROX_NONE border: the run of the start edge, then the others in reverse), corners int32 [n_corners, 2]
+ * = the ring of turning corners on the corner grid, both in the image.  One writer per element; a place outside the buffers is
+ * skipped. */
+int disyolo_outline_gather(const int32_t* groups_host, const int32_t* groups, int G, int64_t arena_bytes, const int32_t* ekey,
+                           const uint8_t* flag, const int32_t* eidx, int64_t capacity, const int32_t* ctrl, const int32_t* plan,
+                           int64_t rows_capacity, int32_t* points, int64_t n_points, int32_t* corners, int64_t n_corners, void* stream);
 /* semantic-segmentation accuracy of evaluate (calculate_test_map.py:303-346): adds the 4x4 pixel
  * confusion counts of two uint8 class maps (0 = background, 1..3 = classes; other values are
  * ignored) to conf int64 [16], conf[true*4 + pred]; the caller zeroes conf before the first image
