@@ -294,13 +294,8 @@ extern "C" int disyolo_measure_counts(const int32_t* groups_host, const int32_t*
                                       double* partials, int64_t partials_len, double* sum_sqrt, void* stream) {
   DY_REQUIRE(G <= 0 || (groups_host && groups && arena && skel && d2 && counts && partials && sum_sqrt),
              "measure_counts: null pointer");
-  DY_REQUIRE(G >= 0 && arena_bytes >= 0, "measure_counts: bad args (G = %d, arena_bytes = %lld)", G, (long long)arena_bytes);
-  if (G == 0) return DISYOLO_OK;
-  int64_t blocks = 0;
-  {
-    const int rc = measure_tables("measure_counts", groups_host, G, arena_bytes, &blocks, nullptr);
-    if (rc != DISYOLO_OK) return rc;
-  }
+  ME_ARGS("measure_counts");
+  ME_PLAN("measure_counts", nullptr);
   DY_REQUIRE(partials_len >= blocks, "measure_counts: %lld partials for %lld blocks", (long long)partials_len, (long long)blocks);
   // (groups without a pixel still get their zero row and their zero sum)
   return measure_counts_run(groups, G, (int)blocks, arena, skel, d2, counts, partials, sum_sqrt, stream);

@@ -262,11 +262,7 @@ static int outline_edges_run(const int32_t* groups, int G, int blocks, const uin
     return outline_edges_run(groups, G, blocks, arena, first, sides, ekey, nxt, flag, aterm, capacity, work, ctrl, s);
   });
   hipStream_t st = (hipStream_t)stream;
-  const hipError_t e = hipMemsetAsync(ctrl, 0, 4 * sizeof(int32_t), st);
-  if (e != hipSuccess) {
-    disyolo_set_error("outline_edges: hipMemsetAsync failed: %s", hipGetErrorString(e));
-    return DISYOLO_E_HIP;
-  }
+  ME_ZERO("outline_edges", ctrl, 4 * sizeof(int32_t), st);
   if (blocks == 0) return DISYOLO_OK;
   hipLaunchKernelGGL(outline_mark_kernel, dim3(blocks), dim3(ME_T), 0, st, (const int*)groups, G, (const unsigned char*)arena,
                      (int*)first, (unsigned char*)sides, (int*)ekey, capacity, (int*)ctrl);
@@ -287,16 +283,11 @@ extern "C" int disyolo_outline_edges(const int32_t* groups_host, const int32_t* 
                                      int64_t capacity, int64_t* work, int64_t work_elems, int32_t* ctrl, void* stream) {
   DY_REQUIRE(G <= 0 || (groups_host && groups && arena && first && sides && ctrl && ((ekey && nxt && flag && aterm && work) || capacity == 0)),
              "outline_edges: null pointer");
-  DY_REQUIRE(G >= 0 && arena_bytes >= 0, "outline_edges: bad args (G = %d, arena_bytes = %lld)", G, (long long)arena_bytes);
+  ME_ARGS("outline_edges");
   OL_LIMITS("outline_edges");
   DY_REQUIRE(work_elems >= OL_WORK * capacity, "outline_edges: work holds %lld words, %lld entries need %lld", (long long)work_elems,
              (long long)capacity, (long long)(OL_WORK * capacity));
-  if (G == 0) return DISYOLO_OK;
-  int64_t blocks = 0;
-  {
-    const int rc = measure_tables("outline_edges", groups_host, G, arena_bytes, &blocks, nullptr);
-    if (rc != DISYOLO_OK) return rc;
-  }
+  ME_PLAN("outline_edges", nullptr);
   // (groups without a pixel still get the zero counters)
   return outline_edges_run(groups, G, (int)blocks, arena, first, sides, ekey, nxt, flag, aterm, (int)capacity, work, ctrl, stream);
 }
@@ -344,15 +335,15 @@ extern "C" int disyolo_outline_loops(const int32_t* groups_host, const int32_t* 
   DY_REQUIRE(G <= 0 || (groups_host && groups && arena && part_labels && first && sides && ctrl && (rows || rows_capacity == 0) &&
                         ((ekey && nxt && flag && aterm && work && eidx) || capacity == 0)),
              "outline_loops: null pointer");
-  DY_REQUIRE(G >= 0 && arena_bytes >= 0, "outline_loops: bad args (G = %d, arena_bytes = %lld)", G, (long long)arena_bytes);
+  ME_ARGS("outline_loops");
   OL_LIMITS("outline_loops");
   DY_REQUIRE(work_elems >= OL_WORK * capacity, "outline_loops: work holds %lld words, %lld entries need %lld", (long long)work_elems,
              (long long)capacity, (long long)(OL_WORK * capacity));
   DY_REQUIRE(rows_capacity >= 0 && rows_capacity < (1ll << 31), "outline_loops: a capacity of %lld rows (need 0 .. 2^31 - 1)",
              (long long)rows_capacity);
   DY_REQUIRE(rounds >= 0 && rounds <= 31, "outline_loops: rounds = %d (need 0 .. 31)", rounds);
-  ME_TABLES("outline_loops", nullptr);
-  if (capacity == 0) return DISYOLO_OK;
+  ME_PLAN("outline_loops", nullptr);
+  if (blocks == 0 || capacity == 0) return DISYOLO_OK;
   return outline_loops_run(groups, G, arena, part_labels, first, sides, ekey, nxt, flag, aterm, (int)capacity, rounds, work, eidx, rows,
                            (int)rows_capacity, ctrl, stream);
 }
@@ -380,14 +371,14 @@ extern "C" int disyolo_outline_gather(const int32_t* groups_host, const int32_t*
   DY_REQUIRE(G <= 0 || (groups_host && groups && ctrl && ((ekey && flag && eidx) || capacity == 0) && (plan || rows_capacity == 0) &&
                         (points || n_points == 0) && (corners || n_corners == 0)),
              "outline_gather: null pointer");
-  DY_REQUIRE(G >= 0 && arena_bytes >= 0, "outline_gather: bad args (G = %d, arena_bytes = %lld)", G, (long long)arena_bytes);
+  ME_ARGS("outline_gather");
   OL_LIMITS("outline_gather");
   DY_REQUIRE(rows_capacity >= 0 && rows_capacity < (1ll << 31), "outline_gather: a capacity of %lld rows (need 0 .. 2^31 - 1)",
              (long long)rows_capacity);
   DY_REQUIRE(n_points >= 0 && n_points <= OL_MAX_LIST && n_corners >= 0 && n_corners <= OL_MAX_LIST,
              "outline_gather: %lld points and %lld corners (need 0 .. 2^30 - 1)", (long long)n_points, (long long)n_corners);
-  ME_TABLES("outline_gather", nullptr);
-  if (capacity == 0 || rows_capacity == 0) return DISYOLO_OK;
+  ME_PLAN("outline_gather", nullptr);
+  if (blocks == 0 || capacity == 0 || rows_capacity == 0) return DISYOLO_OK;
   return outline_gather_run(ekey, flag, eidx, (int)capacity, ctrl, plan, (int)rows_capacity, points, (int)n_points, corners,
                             (int)n_corners, stream);
 }

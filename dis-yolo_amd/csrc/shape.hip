@@ -13,20 +13,19 @@
 //                       by shuffles, over the four waves in LDS, then one atomic per block and column
 //   shape_parts_init    labels = the first pixel of the pixel's row run within its wave's 64 pixels (-1 off the foreground),
 //                       px = 0
-//   shape_parts_merge   the union-find of skeleton_label over the 8-neighbour foreground: the larger root is hung under the
-//                       smaller with an atomic min, so a part ends at its smallest index whatever the order of arrival.  A pair
-//                       is merged from its upper (left) pixel, and only where the run structure does not already join it; a
-//                       walk to the root halves the path behind it
-//   shape_parts_flatten labels = the root of every foreground pixel
+//   shape_parts_merge   the union-find of arena_labels.h over the 8-neighbour foreground: a part ends at its smallest index
+//                       whatever the order of arrival.  A pair is merged from its upper (left) pixel, and only where the run
+//                       structure does not already join it
+//   labels_flatten      labels = the root of every foreground pixel (arena_labels.h)
 //   shape_parts_count   px[root] += 1 per foreground pixel, summed per lane, then per wave and root first
 //   shape_parts_roots   every root adds 1 to its group's n_parts and takes a max on largest_part_px, per wave first
 //   shape_extents_init  the [G,K,2] rows (INT32_MAX, INT32_MIN)
 //   shape_extents       the boundary pixels (foreground with a background 4-neighbour) of a block are listed in LDS; thread k
 //                       projects the list onto direction k and issues at most two atomics, and none where the group's row
 //                       already holds a value as good; a block without a boundary pixel returns at once
-// No block waits for another: the retry loops of the merge are lock-free as in skeleton.hip.  Integer atomics only: two runs give
-// the same bits.  The union-find is repeated here and not shared, so that skeleton.hip and trace.hip stay as they are.
-#include "measure_common.h"
+// No block waits for another: the retry loops of the merge are lock-free (arena_labels.h).  Integer atomics only: two runs give
+// the same bits.
+#include "arena_labels.h"
 
 namespace {
 
@@ -35,17 +34,6 @@ constexpr int SH_SUMS = 11;          // the columns that are sums, in the order 
 constexpr int SH_K_MAX = 360;
 constexpr int SH_UNIT = 16384;       // a direction's (c, s) is a unit vector in 2^-14: |c x + s y| <= 16384 * 65532 < 2^31
 constexpr int SH_WAVES = ME_T / 64;
-
-__device__ __forceinline__ int wave_sum_i(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ int wave_min_i(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
-  return v;
-}
 
 // ---- sums ------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(ME_T) void shape_sums_init_kernel(const int* groups, int G, long long* sums) {
@@ -60,22 +48,6 @@ __global__ __launch_bounds__(ME_T) void shape_sums_init_kernel(const int* groups
 __device__ __forceinline__ void quad(unsigned a, unsigned b, unsigned c, unsigned d, int* q) {
   const unsigned s = a + b + c + d;
   q[0] += s == 1, q[1] += s == 2 && a != d, q[2] += s == 3, q[3] += s == 4, q[4] += s == 2 && a == d;
-}
-
-// crop_of_block (measure_common.h) for any block number of the plan, not the launch's own: the sums launch walks several
-__device__ __forceinline__ Crop crop_of(const int* groups, int G, int block) {
-  int lo = 0, hi = G - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (groups[mid * 8 + 6] <= block) lo = mid; else hi = mid - 1;
-  }
-  const int* g = groups + lo * 8;
-  Crop c;
-  c.g = lo, c.bh = g[4] - g[2], c.bw = g[5] - g[3];
-  c.area = c.bh * c.bw;
-  c.p0 = (block - g[6]) * ME_CHUNK;
-  c.off = (size_t)g[7] * 16;
-  return c;
 }
 
 struct ShapeAcc {
@@ -204,34 +176,6 @@ __global__ __launch_bounds__(ME_T) void shape_parts_init_kernel(const int* group
   }
 }
 
-// Within the merge and the flatten launch the label array is touched with agent-scope atomics only: a plain load could be
-// served from another XCD's L2.  A label never grows and L[i] <= i always, so every walk ends at a root.
-__device__ __forceinline__ int uf_load(int* L, int i) { return __hip_atomic_load(L + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-// Path halving on the way: a pixel met on the walk is hung under its grandparent, an ancestor with a smaller index, by the same
-// atomic min -- on a solid blob the roots of the row runs would otherwise form chains as long as the blob is high.
-__device__ __forceinline__ int uf_find(int* L, int i) {
-  for (;;) {
-    const int p = uf_load(L, i);
-    if (p == i) return i;
-    const int gp = uf_load(L, p);
-    if (gp == p) return p;
-    __hip_atomic_fetch_min(L + i, gp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    i = gp;
-  }
-}
-
-__device__ __forceinline__ void uf_union(int* L, int a, int b) {
-  for (;;) {
-    a = uf_find(L, a), b = uf_find(L, b);
-    if (a == b) return;
-    if (a < b) { const int t = a; a = b, b = t; }
-    const int old = __hip_atomic_fetch_min(L + a, b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (old == a) return;            // a was a root and hangs under b now (halving never touches a root)
-    a = old;                         // another thread hung a under `old` first: L[a] = min(old, b), and old is joined with b
-  }
-}
-
 // Forward neighbours only.  E: the two pixels began under one start unless the right one opens a wave's 64 pixels.  S: when W and
 // SW are foreground too and neither p nor S opens a wave, p ~ W and S ~ SW began joined and the pair (W, SW) is merged (or, by
 // the same rule, left to a pair further left that is): nothing to do.  SW, SE: only when S is background -- a foreground S is
@@ -258,19 +202,6 @@ __global__ __launch_bounds__(ME_T) void shape_parts_merge_kernel(const int* grou
       if (w && r[-1]) uf_union(L, p, p + bw - 1);
       if (e && r[1]) uf_union(L, p, p + bw + 1);
     }
-  }
-}
-
-__global__ __launch_bounds__(ME_T) void shape_parts_flatten_kernel(const int* groups, int G, int* labels) {
-  const Crop c = crop_of_block(groups, G);
-  int* L = labels + c.off;
-#pragma unroll
-  for (int k = 0; k < ME_PX; ++k) {
-    const int p = c.p0 + k * ME_T + threadIdx.x;
-    if (p >= c.area) break;
-    const int l = uf_load(L, p);
-    if (l < 0 || l == p) continue;
-    __hip_atomic_store(L + p, uf_find(L, l), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // (any ancestor is a valid parent)
   }
 }
 
@@ -403,14 +334,9 @@ static int shape_sums_run(const int32_t* groups, int G, int blocks, const uint8_
 extern "C" int disyolo_shape_sums(const int32_t* groups_host, const int32_t* groups, int G, const uint8_t* arena, int64_t arena_bytes,
                                   int64_t* sums, void* stream) {
   DY_REQUIRE(G <= 0 || (groups_host && groups && arena && sums), "shape_sums: null pointer");
-  DY_REQUIRE(G >= 0 && arena_bytes >= 0, "shape_sums: bad args (G = %d, arena_bytes = %lld)", G, (long long)arena_bytes);
+  ME_ARGS("shape_sums");
   DY_REQUIRE(G < (1 << 26), "shape_sums: G = %d (need < 2^26)", G);
-  if (G == 0) return DISYOLO_OK;
-  int64_t blocks = 0;
-  {
-    const int rc = measure_tables("shape_sums", groups_host, G, arena_bytes, &blocks, nullptr);
-    if (rc != DISYOLO_OK) return rc;
-  }
+  ME_PLAN("shape_sums", nullptr);
   // (groups without a pixel still get their empty row)
   return shape_sums_run(groups, G, (int)blocks, arena, sums, stream);
 }
@@ -419,11 +345,7 @@ static int shape_parts_run(const int32_t* groups, int G, int blocks, const uint8
                            void* stream) {
   DY_RECORD_OR_RUN([=](void* s) { return shape_parts_run(groups, G, blocks, arena, labels, px, parts, s); });
   hipStream_t st = (hipStream_t)stream;
-  const hipError_t e = hipMemsetAsync(parts, 0, (size_t)G * 2 * sizeof(int64_t), st);
-  if (e != hipSuccess) {
-    disyolo_set_error("shape_parts: hipMemsetAsync failed: %s", hipGetErrorString(e));
-    return DISYOLO_E_HIP;
-  }
+  ME_ZERO("shape_parts", parts, (size_t)G * 2 * sizeof(int64_t), st);
   if (blocks == 0) return DISYOLO_OK;
   const int* g = (const int*)groups;
   const unsigned char* a = (const unsigned char*)arena;
@@ -431,7 +353,7 @@ static int shape_parts_run(const int32_t* groups, int G, int blocks, const uint8
   DY_CHECK_LAUNCH();
   hipLaunchKernelGGL(shape_parts_merge_kernel, dim3(blocks), dim3(ME_T), 0, st, g, G, a, (int*)labels);
   DY_CHECK_LAUNCH();
-  hipLaunchKernelGGL(shape_parts_flatten_kernel, dim3(blocks), dim3(ME_T), 0, st, g, G, (int*)labels);
+  hipLaunchKernelGGL(labels_flatten_kernel<>, dim3(blocks), dim3(ME_T), 0, st, g, G, (int*)labels);
   DY_CHECK_LAUNCH();
   hipLaunchKernelGGL(shape_parts_count_kernel, dim3((blocks + SH_WALK - 1) / SH_WALK), dim3(ME_T), 0, st, g, G, blocks,
                      (const int*)labels, (int*)px);
@@ -445,13 +367,8 @@ static int shape_parts_run(const int32_t* groups, int G, int blocks, const uint8
 extern "C" int disyolo_shape_parts(const int32_t* groups_host, const int32_t* groups, int G, const uint8_t* arena, int64_t arena_bytes,
                                    int32_t* labels, int32_t* px, int64_t* parts, void* stream) {
   DY_REQUIRE(G <= 0 || (groups_host && groups && arena && labels && px && parts), "shape_parts: null pointer");
-  DY_REQUIRE(G >= 0 && arena_bytes >= 0, "shape_parts: bad args (G = %d, arena_bytes = %lld)", G, (long long)arena_bytes);
-  if (G == 0) return DISYOLO_OK;
-  int64_t blocks = 0;
-  {
-    const int rc = measure_tables("shape_parts", groups_host, G, arena_bytes, &blocks, nullptr);
-    if (rc != DISYOLO_OK) return rc;
-  }
+  ME_ARGS("shape_parts");
+  ME_PLAN("shape_parts", nullptr);
   // (groups without a pixel still get their zero row)
   return shape_parts_run(groups, G, (int)blocks, arena, labels, px, parts, stream);
 }
@@ -473,19 +390,15 @@ static int shape_extents_run(const int32_t* groups, int G, int blocks, const uin
 extern "C" int disyolo_shape_extents(const int32_t* groups_host, const int32_t* groups, int G, const uint8_t* arena, int64_t arena_bytes,
                                      const int32_t* dirs_host, const int32_t* dirs, int K, int32_t* pminmax, void* stream) {
   DY_REQUIRE(G <= 0 || (groups_host && groups && arena && dirs_host && dirs && pminmax), "shape_extents: null pointer");
-  DY_REQUIRE(G >= 0 && arena_bytes >= 0, "shape_extents: bad args (G = %d, arena_bytes = %lld)", G, (long long)arena_bytes);
+  ME_ARGS("shape_extents");
   DY_REQUIRE(G < (1 << 20), "shape_extents: G = %d (need < 2^20)", G);
-  if (G == 0) return DISYOLO_OK;
+  if (G == 0) return DISYOLO_OK;                                      // (no directions are asked of a call without groups)
   DY_REQUIRE(K >= 2 && K <= SH_K_MAX && K % 2 == 0, "shape_extents: K = %d directions (need an even number in 2 .. %d)", K, SH_K_MAX);
   for (int k = 0; k < K; ++k)
     DY_REQUIRE(dirs_host[2 * k] >= -SH_UNIT && dirs_host[2 * k] <= SH_UNIT && dirs_host[2 * k + 1] >= -SH_UNIT &&
                    dirs_host[2 * k + 1] <= SH_UNIT,
                "shape_extents: direction %d is (%d, %d) (need |c|, |s| <= %d)", k, dirs_host[2 * k], dirs_host[2 * k + 1], SH_UNIT);
-  int64_t blocks = 0;
-  {
-    const int rc = measure_tables("shape_extents", groups_host, G, arena_bytes, &blocks, nullptr);
-    if (rc != DISYOLO_OK) return rc;
-  }
+  ME_PLAN("shape_extents", nullptr);
   // (groups without a pixel still get their (INT32_MAX, INT32_MIN) rows)
   return shape_extents_run(groups, G, (int)blocks, arena, dirs, K, pminmax, stream);
 }

@@ -5,31 +5,21 @@
 // a block owns ME_CHUNK consecutive pixels of a crop, every buffer lies in the arena's layout, one element per pixel, and the
 // elements between two crops are never read and never written.
 //   skeleton_classify   skel -> links: bit k of a pixel's byte = it is linked to its neighbour P(2+k) (N, NE, E, SE, S, SW, W, NW)
-//   skeleton_init       labels = the pixel's own index on P pixels (degree <= 2), -1 elsewhere
-//   skeleton_merge      union-find over the links between two P pixels: the larger root is hung under the smaller one with an
-//                       atomic min, so a component ends at its smallest index whatever the order of arrival
-//   skeleton_flatten    labels = the root of every P pixel
-//   skeleton_alloc      every root draws a row number from one counter and writes its row's head
+//   links_init          labels = the pixel's own index on P pixels (degree <= 2), -1 elsewhere          } arena_labels.h, with
+//   links_merge         union-find over the links between two P pixels                                    } BranchPixels and
+//   labels_flatten      labels = the root of every P pixel: its branch's smallest index                   } BranchRow below
+//   roots_alloc         every root draws a row number from one counter and writes its row's head          }
 //   skeleton_accum      every P pixel adds its integers to its branch's row (summed per wave and row first); J pixels add
 //                       to the [G,4] junction table
 //   skeleton_finish     the spur bit of every row from M2, and one flag per group that has a spur
 //   skeleton_prune      deletes the pixels whose row is a spur
-// No block waits for another: the retry loops of the merge are lock-free (each turn either succeeds or meets a label that
-// another thread has made smaller), and what one launch writes is read with plain loads only by later launches.
-#include "measure_common.h"
+// No block waits for another: the retry loops of the merge are lock-free (arena_labels.h), and what one launch writes is read
+// with plain loads only by later launches.
+#include "arena_labels.h"
 
 namespace {
 
-constexpr int SK_ROW = 12;           // int64 words of a row: group, root, px, n_orth, n_diag, n_end, n_attach, sum_q8, max_d2,
-                                     // min_d2, spur, 0
 constexpr int SK_M2_MAX = 2 * 32767;
-
-// the offset of neighbour P(2+k) in a crop of pitch bw
-__device__ __forceinline__ int nb_offset(int k, int bw) {
-  const int dy = (k == 0 || k == 1 || k == 7) ? -1 : (k >= 3 && k <= 5) ? 1 : 0;
-  const int dx = (k >= 1 && k <= 3) ? 1 : (k >= 5) ? -1 : 0;
-  return dy * bw + dx;
-}
 
 __global__ __launch_bounds__(ME_T) void skeleton_classify_kernel(const int* groups, int G, const unsigned char* src,
                                                                  unsigned char* skel, unsigned char* links, int copy) {
@@ -55,105 +45,22 @@ __global__ __launch_bounds__(ME_T) void skeleton_classify_kernel(const int* grou
   }
 }
 
-// ---- labels: union-find ---------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(ME_T) void skeleton_init_kernel(const int* groups, int G, const unsigned char* skel,
-                                                             const unsigned char* links, int* labels) {
-  const Crop c = crop_of_block(groups, G);
-#pragma unroll
-  for (int k = 0; k < ME_PX; ++k) {
-    const int p = c.p0 + k * ME_T + threadIdx.x;
-    if (p >= c.area) break;
-    labels[c.off + p] = (skel[c.off + p] && __popc(links[c.off + p]) <= 2) ? p : -1;
-  }
-}
+// ---- labels and rows: what arena_labels.h is told ----------------------------------------------------------------------------
+// the P pixels: on the skeleton (an off pixel has no link either) with at most two links
+struct BranchPixels {
+  const unsigned char* skel;
+  __device__ bool seed(size_t i, unsigned links) const { return skel[i] && member(links); }
+  __device__ static bool member(unsigned links) { return __popc(links) <= 2; }
+};
 
-// Within the merge and the flatten launch the label array is touched with agent-scope atomics only: a plain load could be
-// served from another XCD's L2.  A label never grows and L[i] <= i always, so every walk ends at a root.
-__device__ __forceinline__ int uf_load(int* L, int i) { return __hip_atomic_load(L + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-__device__ __forceinline__ int uf_find(int* L, int i) {
-  for (int p; (p = uf_load(L, i)) != i;) i = p;
-  return i;
-}
-
-__device__ __forceinline__ void uf_union(int* L, int a, int b) {
-  for (;;) {
-    a = uf_find(L, a), b = uf_find(L, b);
-    if (a == b) return;
-    if (a < b) { const int t = a; a = b, b = t; }
-    const int old = __hip_atomic_fetch_min(L + a, b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (old == a) return;            // a was a root and hangs under b now
-    a = old;                         // another thread hung a under `old` first: L[a] = min(old, b), and old is joined with b
-  }
-}
-
-// a pair is merged from its upper (or, in a row, left) pixel: bits 2 .. 5 = E, SE, S, SW
-__global__ __launch_bounds__(ME_T) void skeleton_merge_kernel(const int* groups, int G, const unsigned char* links, int* labels) {
-  const Crop c = crop_of_block(groups, G);
-  const unsigned char* lk = links + c.off;
-  int* L = labels + c.off;
-#pragma unroll
-  for (int k = 0; k < ME_PX; ++k) {
-    const int p = c.p0 + k * ME_T + threadIdx.x;
-    if (p >= c.area) break;
-    const unsigned l = lk[p];
-    if ((l & 0x3c) == 0 || __popc(l) > 2) continue;
-#pragma unroll
-    for (int b = 2; b <= 5; ++b) {
-      if (!(l >> b & 1)) continue;
-      const int q = p + nb_offset(b, c.bw);
-      if (__popc(lk[q]) <= 2) uf_union(L, p, q);
-    }
-  }
-}
-
-__global__ __launch_bounds__(ME_T) void skeleton_flatten_kernel(const int* groups, int G, int* labels) {
-  const Crop c = crop_of_block(groups, G);
-  int* L = labels + c.off;
-#pragma unroll
-  for (int k = 0; k < ME_PX; ++k) {
-    const int p = c.p0 + k * ME_T + threadIdx.x;
-    if (p >= c.area) break;
-    const int l = uf_load(L, p);
-    if (l < 0 || l == p) continue;
-    __hip_atomic_store(L + p, uf_find(L, l), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // (any ancestor is a valid parent)
-  }
-}
-
-// ---- rows -----------------------------------------------------------------------------------------------------------------
 // ctrl int32 [1 + G]: word 0 = the row counter, which keeps counting beyond `capacity` without anything being written there;
 // word 1 + g != 0 <=> group g has a spur.  junctions int64 [G, 4] = junction_px, jj_orth, jj_diag, n_branches.
-__global__ __launch_bounds__(ME_T) void skeleton_alloc_kernel(const int* groups, int G, const int* labels, int* rowid,
-                                                              long long* rows, int capacity, int* ctrl,
-                                                              unsigned long long* junctions) {
-  const Crop c = crop_of_block(groups, G);
-#pragma unroll
-  for (int k = 0; k < ME_PX; ++k) {
-    const int p = c.p0 + k * ME_T + threadIdx.x;
-    if (p >= c.area) break;
-    if (labels[c.off + p] != p) continue;
-    const int id = atomicAdd(&ctrl[0], 1);
-    rowid[c.off + p] = id;
-    atomicAdd(&junctions[(size_t)c.g * 4 + 3], 1ull);
-    if (id < capacity) {
-      long long* r = rows + (size_t)id * SK_ROW;
-      r[0] = c.g, r[1] = p;
-#pragma unroll
-      for (int q = 2; q < SK_ROW; ++q) r[q] = q == 9 ? 0x7fffffffll : 0;
-    }
-  }
-}
-
-// floor(sqrt(65536 d2)): the half-width in 1/256 px, bit by bit in integers (d2 < 2^31: the root has 24 bits)
-__device__ __forceinline__ unsigned isqrt_q8(int d2) {
-  const unsigned long long v = (unsigned long long)(unsigned)d2 << 16;
-  unsigned r = 0;
-  for (int b = 23; b >= 0; --b) {
-    const unsigned t = r | 1u << b;
-    if ((unsigned long long)t * t <= v) r = t;
-  }
-  return r;
-}
+struct BranchRow {
+  static constexpr int WIDTH = SK_ROW;
+  unsigned long long* junctions;
+  __device__ void drawn(int g) const { atomicAdd(&junctions[(size_t)g * 4 + 3], 1ull); }
+  __device__ static long long empty(int q) { return q == SK_MIN_D2 ? 0x7fffffffll : 0; }
+};
 
 // Most waves hold no skeleton pixel at all, and those of a wave that does mostly belong to one branch: the lanes of a wave
 // that share a row add their integers up first (a leader per distinct row, found by ballot), and only the leader touches the
@@ -207,14 +114,14 @@ __global__ __launch_bounds__(ME_T) void skeleton_accum_kernel(const int* groups,
       const int mx = wave_max_i(mine ? d : 0), mn = -wave_max_i(mine ? -d : -0x7fffffff);
       if (lane == leader) {
         unsigned long long* r = rows + (size_t)lid * SK_ROW;
-        atomicAdd(&r[2], (unsigned long long)px);
-        if (so) atomicAdd(&r[3], (unsigned long long)so);
-        if (sd) atomicAdd(&r[4], (unsigned long long)sd);
-        if (se) atomicAdd(&r[5], (unsigned long long)se);
-        if (sa) atomicAdd(&r[6], (unsigned long long)sa);
-        atomicAdd(&r[7], (unsigned long long)sq);
-        atomicMax(&r[8], (unsigned long long)mx);
-        atomicMin(&r[9], (unsigned long long)mn);
+        atomicAdd(&r[SK_PX], (unsigned long long)px);
+        if (so) atomicAdd(&r[SK_N_ORTH], (unsigned long long)so);
+        if (sd) atomicAdd(&r[SK_N_DIAG], (unsigned long long)sd);
+        if (se) atomicAdd(&r[SK_N_END], (unsigned long long)se);
+        if (sa) atomicAdd(&r[SK_N_ATTACH], (unsigned long long)sa);
+        atomicAdd(&r[SK_SUM_Q8], (unsigned long long)sq);
+        atomicMax(&r[SK_MAX_D2], (unsigned long long)mx);
+        atomicMin(&r[SK_MIN_D2], (unsigned long long)mn);
       }
     }
   }
@@ -232,10 +139,10 @@ __global__ __launch_bounds__(ME_T) void skeleton_finish_kernel(long long* rows, 
   const long long i = (long long)blockIdx.x * ME_T + threadIdx.x;
   if (i >= min(ctrl[0], capacity)) return;
   long long* r = rows + (size_t)i * SK_ROW;
-  const long long t2 = (long long)M2 - 2 * r[3] - r[5];
-  const int spur = r[5] == 1 && r[6] == 1 && t2 > 0 && 8 * r[4] * r[4] < t2 * t2;
-  r[10] = spur;
-  if (spur) atomicOr(&ctrl[1 + (int)r[0]], 1);
+  const long long t2 = (long long)M2 - 2 * r[SK_N_ORTH] - r[SK_N_END];
+  const int spur = r[SK_N_END] == 1 && r[SK_N_ATTACH] == 1 && t2 > 0 && 8 * r[SK_N_DIAG] * r[SK_N_DIAG] < t2 * t2;
+  r[SK_SPUR] = spur;
+  if (spur) atomicOr(&ctrl[1 + (int)r[SK_GROUP]], 1);
 }
 
 __global__ __launch_bounds__(ME_T) void skeleton_prune_kernel(const int* groups, int G, const int* labels, const int* rowid,
@@ -248,7 +155,7 @@ __global__ __launch_bounds__(ME_T) void skeleton_prune_kernel(const int* groups,
     const int root = labels[c.off + p];
     if (root < 0) continue;
     const int id = rowid[c.off + root];
-    if (id < capacity && rows[(size_t)id * SK_ROW + 10]) skel[c.off + p] = 0;
+    if (id < capacity && rows[(size_t)id * SK_ROW + SK_SPUR]) skel[c.off + p] = 0;
   }
 }
 
@@ -274,13 +181,13 @@ static int skeleton_label_run(const int32_t* groups, int G, int blocks, const ui
                               void* stream) {
   DY_RECORD_OR_RUN([=](void* s) { return skeleton_label_run(groups, G, blocks, skel, links, labels, s); });
   hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(skeleton_init_kernel, dim3(blocks), dim3(ME_T), 0, st, (const int*)groups, G, (const unsigned char*)skel,
+  hipLaunchKernelGGL(links_init_kernel<BranchPixels>, dim3(blocks), dim3(ME_T), 0, st, (const int*)groups, G,
+                     BranchPixels{(const unsigned char*)skel}, (const unsigned char*)links, (int*)labels);
+  DY_CHECK_LAUNCH();
+  hipLaunchKernelGGL(links_merge_kernel<BranchPixels>, dim3(blocks), dim3(ME_T), 0, st, (const int*)groups, G,
                      (const unsigned char*)links, (int*)labels);
   DY_CHECK_LAUNCH();
-  hipLaunchKernelGGL(skeleton_merge_kernel, dim3(blocks), dim3(ME_T), 0, st, (const int*)groups, G, (const unsigned char*)links,
-                     (int*)labels);
-  DY_CHECK_LAUNCH();
-  hipLaunchKernelGGL(skeleton_flatten_kernel, dim3(blocks), dim3(ME_T), 0, st, (const int*)groups, G, (int*)labels);
+  hipLaunchKernelGGL(labels_flatten_kernel<LINKS_HALVE>, dim3(blocks), dim3(ME_T), 0, st, (const int*)groups, G, (int*)labels);
   DY_CHECK_LAUNCH();
   return DISYOLO_OK;
 }
@@ -299,15 +206,11 @@ static int skeleton_rows_run(const int32_t* groups, int G, int blocks, const uin
     return skeleton_rows_run(groups, G, blocks, links, labels, d2, rowid, rows, capacity, M2, ctrl, junctions, s);
   });
   hipStream_t st = (hipStream_t)stream;
-  hipError_t e = hipMemsetAsync(ctrl, 0, (size_t)(G + 1) * sizeof(int32_t), st);
-  if (e == hipSuccess) e = hipMemsetAsync(junctions, 0, (size_t)G * 4 * sizeof(int64_t), st);
-  if (e != hipSuccess) {
-    disyolo_set_error("skeleton_rows: hipMemsetAsync failed: %s", hipGetErrorString(e));
-    return DISYOLO_E_HIP;
-  }
+  ME_ZERO("skeleton_rows", ctrl, (size_t)(G + 1) * sizeof(int32_t), st);
+  ME_ZERO("skeleton_rows", junctions, (size_t)G * 4 * sizeof(int64_t), st);
   if (blocks == 0) return DISYOLO_OK;
-  hipLaunchKernelGGL(skeleton_alloc_kernel, dim3(blocks), dim3(ME_T), 0, st, (const int*)groups, G, (const int*)labels,
-                     (int*)rowid, (long long*)rows, capacity, (int*)ctrl, (unsigned long long*)junctions);
+  hipLaunchKernelGGL(roots_alloc_kernel<BranchRow>, dim3(blocks), dim3(ME_T), 0, st, (const int*)groups, G, (const int*)labels,
+                     (int*)rowid, (long long*)rows, capacity, (int*)ctrl, BranchRow{(unsigned long long*)junctions});
   DY_CHECK_LAUNCH();
   hipLaunchKernelGGL(skeleton_accum_kernel, dim3(blocks), dim3(ME_T), 0, st, (const int*)groups, G, (const unsigned char*)links,
                      (const int*)labels, (const int*)d2, (const int*)rowid, (unsigned long long*)rows, capacity,
@@ -326,16 +229,11 @@ extern "C" int disyolo_skeleton_rows(const int32_t* groups_host, const int32_t* 
                                      int64_t* rows, int64_t capacity, int M2, int32_t* ctrl, int64_t* junctions, void* stream) {
   DY_REQUIRE(G <= 0 || (groups_host && groups && links && labels && d2 && rowid && ctrl && junctions && (rows || capacity == 0)),
              "skeleton_rows: null pointer");
-  DY_REQUIRE(G >= 0 && arena_bytes >= 0, "skeleton_rows: bad args (G = %d, arena_bytes = %lld)", G, (long long)arena_bytes);
+  ME_ARGS("skeleton_rows");
   DY_REQUIRE(capacity >= 0 && capacity < (1ll << 31), "skeleton_rows: a capacity of %lld rows (need 0 .. 2^31 - 1)",
              (long long)capacity);
   DY_REQUIRE(M2 >= 0 && M2 <= SK_M2_MAX, "skeleton_rows: M2 = %d (twice min_branch_px: need 0 .. %d)", M2, SK_M2_MAX);
-  if (G == 0) return DISYOLO_OK;
-  int64_t blocks = 0;
-  {
-    const int rc = measure_tables("skeleton_rows", groups_host, G, arena_bytes, &blocks, nullptr);
-    if (rc != DISYOLO_OK) return rc;
-  }
+  ME_PLAN("skeleton_rows", nullptr);
   // (groups without a pixel still get their zero flag and their zero junction row)
   return skeleton_rows_run(groups, G, (int)blocks, links, labels, d2, rowid, rows, (int)capacity, M2, ctrl, junctions, stream);
 }

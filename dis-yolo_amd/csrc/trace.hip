@@ -7,9 +7,10 @@
 // the elements between two crops are never read and never written.  The P pixels (degree <= 2, the pixels of branches) are
 // compacted once into a list of entries, in any order; everything after that sweeps the list, not the arena, and writes to
 // places that do not depend on the list's order.
-//   trace_node_init / merge / flatten   the union-find of skeleton_label over the links between two J pixels (degree >= 3): the
-//                       larger root is hung under the smaller with an atomic min, so a node ends at its smallest index
-//   trace_node_alloc / accum            every node root draws a row; every J pixel adds its integers to its node's row
+//   links_init / links_merge / labels_flatten   the union-find of skeleton_label (arena_labels.h) over the links between two J
+//                       pixels (degree >= 3, NodePixels below): a node ends at its smallest index
+//   roots_alloc         every node root draws a row (NodeRow below)
+//   trace_node_accum    every J pixel adds its integers to its node's row
 //   trace_compact       every P pixel draws a list index and writes its entry: where it is, its (at most two) in-branch
 //                       neighbours and its (at most two) J neighbours, each in ascending link bit
 //   trace_link          the doubled state (entry, direction): state 2 i + s of entry i moves on to its neighbour s; its successor
@@ -24,12 +25,11 @@
 //                       host's plan
 //   trace_trunk_rows    one block per instance reduces its trunk profile: integer sums, the maximum with its first position
 // No block waits for another and none reads what another block writes in the same launch, the union-find apart, whose retry
-// loops are lock-free as in skeleton.hip.  The union-find is repeated here and not shared, so that skeleton.hip stays as it is.
-#include "measure_common.h"
+// loops are lock-free (arena_labels.h).
+#include "arena_labels.h"
 
 namespace {
 
-constexpr int TR_SK_ROW = 12;        // int64 words of a branch row of disyolo_skeleton_rows (n_end at 5, n_attach at 6)
 constexpr int TR_NODE = 8;           // int64 words of a node row: group, root, px, sum_y, sum_x, max_d2, n_attach, 0
 constexpr int TR_EDGE = 12;          // int64 words of an edge row: group, root, end0_kind, end0_id, end1_kind, end1_id, attach0_px,
                                      // attach1_px, end0_px, end1_px, inner_diag (rank_diag of the last pixel), last_rank (px - 1)
@@ -43,92 +43,18 @@ constexpr int TR_PROF = 4;           // int32 words of a branch profile entry: y
 constexpr int TR_TPROF = 5;          // int32 words of a trunk profile entry: y, x, d2, cum_orth, cum_diag
 constexpr int TR_TRUNK = 8;          // int64 words of a trunk row: px, sum_q8, max_d2, max_pos, max_y, max_x, cum_orth, cum_diag (last)
 
-__device__ __forceinline__ int nb_offset(int k, int bw) {
-  const int dy = (k == 0 || k == 1 || k == 7) ? -1 : (k >= 3 && k <= 5) ? 1 : 0;
-  const int dx = (k >= 1 && k <= 3) ? 1 : (k >= 5) ? -1 : 0;
-  return dy * bw + dx;
-}
+// ---- nodes: what arena_labels.h is told --------------------------------------------------------------------------------------
+// the J pixels: three links or more (an off pixel has none)
+struct NodePixels {
+  __device__ bool seed(size_t, unsigned links) const { return member(links); }
+  __device__ static bool member(unsigned links) { return __popc(links) >= 3; }
+};
 
-// ---- nodes: union-find over the J-J links --------------------------------------------------------------------------------
-__global__ __launch_bounds__(ME_T) void trace_node_init_kernel(const int* groups, int G, const unsigned char* links, int* nlab) {
-  const Crop c = crop_of_block(groups, G);
-#pragma unroll
-  for (int k = 0; k < ME_PX; ++k) {
-    const int p = c.p0 + k * ME_T + threadIdx.x;
-    if (p >= c.area) break;
-    nlab[c.off + p] = __popc(links[c.off + p]) >= 3 ? p : -1;
-  }
-}
-
-// Within the merge and the flatten launch the label array is touched with agent-scope atomics only (see skeleton.hip).
-__device__ __forceinline__ int uf_load(int* L, int i) { return __hip_atomic_load(L + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-__device__ __forceinline__ int uf_find(int* L, int i) {
-  for (int p; (p = uf_load(L, i)) != i;) i = p;
-  return i;
-}
-
-__device__ __forceinline__ void uf_union(int* L, int a, int b) {
-  for (;;) {
-    a = uf_find(L, a), b = uf_find(L, b);
-    if (a == b) return;
-    if (a < b) { const int t = a; a = b, b = t; }
-    const int old = __hip_atomic_fetch_min(L + a, b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (old == a) return;
-    a = old;
-  }
-}
-
-__global__ __launch_bounds__(ME_T) void trace_node_merge_kernel(const int* groups, int G, const unsigned char* links, int* nlab) {
-  const Crop c = crop_of_block(groups, G);
-  const unsigned char* lk = links + c.off;
-  int* L = nlab + c.off;
-#pragma unroll
-  for (int k = 0; k < ME_PX; ++k) {
-    const int p = c.p0 + k * ME_T + threadIdx.x;
-    if (p >= c.area) break;
-    const unsigned l = lk[p];
-    if ((l & 0x3c) == 0 || __popc(l) < 3) continue;
-#pragma unroll
-    for (int b = 2; b <= 5; ++b) {
-      if (!(l >> b & 1)) continue;
-      const int q = p + nb_offset(b, c.bw);
-      if (__popc(lk[q]) >= 3) uf_union(L, p, q);
-    }
-  }
-}
-
-__global__ __launch_bounds__(ME_T) void trace_node_flatten_kernel(const int* groups, int G, int* nlab) {
-  const Crop c = crop_of_block(groups, G);
-  int* L = nlab + c.off;
-#pragma unroll
-  for (int k = 0; k < ME_PX; ++k) {
-    const int p = c.p0 + k * ME_T + threadIdx.x;
-    if (p >= c.area) break;
-    const int l = uf_load(L, p);
-    if (l < 0 || l == p) continue;
-    __hip_atomic_store(L + p, uf_find(L, l), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-}
-
-__global__ __launch_bounds__(ME_T) void trace_node_alloc_kernel(const int* groups, int G, const int* nlab, int* noderow,
-                                                                long long* nodes, int capacity, int* ctrl) {
-  const Crop c = crop_of_block(groups, G);
-#pragma unroll
-  for (int k = 0; k < ME_PX; ++k) {
-    const int p = c.p0 + k * ME_T + threadIdx.x;
-    if (p >= c.area) break;
-    if (nlab[c.off + p] != p) continue;
-    const int id = atomicAdd(&ctrl[0], 1);
-    noderow[c.off + p] = id;
-    if (id < capacity) {
-      long long* r = nodes + (size_t)id * TR_NODE;
-      r[0] = c.g, r[1] = p;
-#pragma unroll
-      for (int q = 2; q < TR_NODE; ++q) r[q] = 0;
-    }
-  }
-}
+struct NodeRow {
+  static constexpr int WIDTH = TR_NODE;
+  __device__ void drawn(int) const {}
+  __device__ static long long empty(int) { return 0; }
+};
 
 // (J pixels are few beside the arena: one atomic per pixel and column)
 __global__ __launch_bounds__(ME_T) void trace_node_accum_kernel(const int* groups, int G, const unsigned char* links, const int* nlab,
@@ -209,8 +135,8 @@ __global__ __launch_bounds__(ME_T) void trace_compact_kernel(const int* groups, 
     }
     const int id = rowid[c.off + root];
     if (id >= 0 && id < rows_capacity) {
-      const long long* r = rows + (size_t)id * TR_SK_ROW;
-      if (r[5] == 0 && r[6] == 0) flags |= F_LOOP;                     // no end and no attachment: every pixel has two neighbours
+      const long long* r = rows + (size_t)id * SK_ROW;
+      if (r[SK_N_END] == 0 && r[SK_N_ATTACH] == 0) flags |= F_LOOP;                    // no end and no attachment: every pixel has two neighbours
     }
     int* e = ents + (size_t)idx * TR_ENT;
     e[E_POS] = (int)c.off + p, e[E_P] = p, e[E_ROOT] = root, e[E_NB0] = nb[0], e[E_NB1] = nb[1], e[E_ATT0] = att[0], e[E_ATT1] = att[1];
@@ -361,23 +287,6 @@ __global__ __launch_bounds__(ME_T) void trace_gather_kernel(const int* ents, con
   o[0] = y, o[1] = x, o[2] = e[E_D2], o[3] = sg[2] + (k - dg), o[4] = sg[3] + dg;
 }
 
-// floor(sqrt(65536 d2)) in integers, as skeleton.hip
-__device__ __forceinline__ unsigned isqrt_q8(int d2) {
-  const unsigned long long v = (unsigned long long)(unsigned)d2 << 16;
-  unsigned r = 0;
-  for (int b = 23; b >= 0; --b) {
-    const unsigned t = r | 1u << b;
-    if ((unsigned long long)t * t <= v) r = t;
-  }
-  return r;
-}
-
-__device__ __forceinline__ long long wave_max_ll(long long v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
-  return v;
-}
-
 // one block per instance: tstart int32 [G + 1] = where its trunk profile begins.  The maximum with its first position is the
 // maximum of (d2 << 32 | ~position)
 __global__ __launch_bounds__(ME_T) void trace_trunk_rows_kernel(const int* tstart, const int* tprofile, int tprofile_len,
@@ -417,22 +326,18 @@ static int trace_nodes_run(const int32_t* groups, int G, int blocks, const uint8
                            int32_t* noderow, int64_t* nodes, int capacity, int32_t* ctrl, void* stream) {
   DY_RECORD_OR_RUN([=](void* s) { return trace_nodes_run(groups, G, blocks, links, d2, node_labels, noderow, nodes, capacity, ctrl, s); });
   hipStream_t st = (hipStream_t)stream;
-  const hipError_t e = hipMemsetAsync(ctrl, 0, sizeof(int32_t), st);
-  if (e != hipSuccess) {
-    disyolo_set_error("trace_nodes: hipMemsetAsync failed: %s", hipGetErrorString(e));
-    return DISYOLO_E_HIP;
-  }
+  ME_ZERO("trace_nodes", ctrl, sizeof(int32_t), st);
   if (blocks == 0) return DISYOLO_OK;
   const int* g = (const int*)groups;
   const unsigned char* lk = (const unsigned char*)links;
-  hipLaunchKernelGGL(trace_node_init_kernel, dim3(blocks), dim3(ME_T), 0, st, g, G, lk, (int*)node_labels);
+  hipLaunchKernelGGL(links_init_kernel<NodePixels>, dim3(blocks), dim3(ME_T), 0, st, g, G, NodePixels{}, lk, (int*)node_labels);
   DY_CHECK_LAUNCH();
-  hipLaunchKernelGGL(trace_node_merge_kernel, dim3(blocks), dim3(ME_T), 0, st, g, G, lk, (int*)node_labels);
+  hipLaunchKernelGGL(links_merge_kernel<NodePixels>, dim3(blocks), dim3(ME_T), 0, st, g, G, lk, (int*)node_labels);
   DY_CHECK_LAUNCH();
-  hipLaunchKernelGGL(trace_node_flatten_kernel, dim3(blocks), dim3(ME_T), 0, st, g, G, (int*)node_labels);
+  hipLaunchKernelGGL(labels_flatten_kernel<LINKS_HALVE>, dim3(blocks), dim3(ME_T), 0, st, g, G, (int*)node_labels);
   DY_CHECK_LAUNCH();
-  hipLaunchKernelGGL(trace_node_alloc_kernel, dim3(blocks), dim3(ME_T), 0, st, g, G, (const int*)node_labels, (int*)noderow,
-                     (long long*)nodes, capacity, (int*)ctrl);
+  hipLaunchKernelGGL(roots_alloc_kernel<NodeRow>, dim3(blocks), dim3(ME_T), 0, st, g, G, (const int*)node_labels, (int*)noderow,
+                     (long long*)nodes, capacity, (int*)ctrl, NodeRow{});
   DY_CHECK_LAUNCH();
   hipLaunchKernelGGL(trace_node_accum_kernel, dim3(blocks), dim3(ME_T), 0, st, g, G, lk, (const int*)node_labels, (const int*)d2,
                      (const int*)noderow, (unsigned long long*)nodes, capacity);
@@ -445,14 +350,9 @@ extern "C" int disyolo_trace_nodes(const int32_t* groups_host, const int32_t* gr
                                    int32_t* ctrl, void* stream) {
   DY_REQUIRE(G <= 0 || (groups_host && groups && links && d2 && node_labels && noderow && ctrl && (nodes || capacity == 0)),
              "trace_nodes: null pointer");
-  DY_REQUIRE(G >= 0 && arena_bytes >= 0, "trace_nodes: bad args (G = %d, arena_bytes = %lld)", G, (long long)arena_bytes);
+  ME_ARGS("trace_nodes");
   DY_REQUIRE(capacity >= 0 && capacity < (1ll << 31), "trace_nodes: a capacity of %lld rows (need 0 .. 2^31 - 1)", (long long)capacity);
-  if (G == 0) return DISYOLO_OK;
-  int64_t blocks = 0;
-  {
-    const int rc = measure_tables("trace_nodes", groups_host, G, arena_bytes, &blocks, nullptr);
-    if (rc != DISYOLO_OK) return rc;
-  }
+  ME_PLAN("trace_nodes", nullptr);
   // (groups without a pixel still get the zero counter)
   return trace_nodes_run(groups, G, (int)blocks, links, d2, node_labels, noderow, nodes, (int)capacity, ctrl, stream);
 }
@@ -465,11 +365,7 @@ static int trace_rank_run(const int32_t* groups, int G, int blocks, const uint8_
                           rank, rank_diag, s);
   });
   hipStream_t st = (hipStream_t)stream;
-  const hipError_t e = hipMemsetAsync(count, 0, sizeof(int32_t), st);
-  if (e != hipSuccess) {
-    disyolo_set_error("trace_rank: hipMemsetAsync failed: %s", hipGetErrorString(e));
-    return DISYOLO_E_HIP;
-  }
+  ME_ZERO("trace_rank", count, sizeof(int32_t), st);
   if (blocks == 0) return DISYOLO_OK;
   hipLaunchKernelGGL(trace_compact_kernel, dim3(blocks), dim3(ME_T), 0, st, (const int*)groups, G, (const unsigned char*)links,
                      (const int*)labels, (const int*)d2, (const int*)rowid, (const long long*)rows, rows_capacity, (int*)ents,
@@ -500,18 +396,13 @@ extern "C" int disyolo_trace_rank(const int32_t* groups_host, const int32_t* gro
   DY_REQUIRE(G <= 0 || (groups_host && groups && links && labels && d2 && rowid && count && rank && rank_diag &&
                         (rows || rows_capacity == 0) && ((ents && nxt && val) || capacity == 0)),
              "trace_rank: null pointer");
-  DY_REQUIRE(G >= 0 && arena_bytes >= 0, "trace_rank: bad args (G = %d, arena_bytes = %lld)", G, (long long)arena_bytes);
+  ME_ARGS("trace_rank");
   TR_ARENA("trace_rank");
   DY_REQUIRE(capacity >= 0 && capacity <= TR_MAX_LIST, "trace_rank: a capacity of %lld list entries (need 0 .. 2^30)", (long long)capacity);
   DY_REQUIRE(rows_capacity >= 0 && rows_capacity < (1ll << 31), "trace_rank: a capacity of %lld rows (need 0 .. 2^31 - 1)",
              (long long)rows_capacity);
   DY_REQUIRE(rounds >= 0 && rounds <= 31, "trace_rank: rounds = %d (need 0 .. 31)", rounds);
-  if (G == 0) return DISYOLO_OK;
-  int64_t blocks = 0;
-  {
-    const int rc = measure_tables("trace_rank", groups_host, G, arena_bytes, &blocks, nullptr);
-    if (rc != DISYOLO_OK) return rc;
-  }
+  ME_PLAN("trace_rank", nullptr);
   return trace_rank_run(groups, G, (int)blocks, links, labels, d2, rowid, rows, (int)rows_capacity, ents, (int)capacity, rounds, nxt, val,
                         count, rank, rank_diag, stream);
 }
@@ -578,14 +469,9 @@ extern "C" int disyolo_trace_gather(const int32_t* groups_host, const int32_t* g
   DY_REQUIRE(n_attach >= 0 && n_attach <= TR_MAX_LIST && tprofile_len >= 0 && tprofile_len <= TR_MAX_LIST,
              "trace_gather: a plan of %lld attach entries and %lld profile entries (need 0 .. 2^30 each)", (long long)n_attach,
              (long long)tprofile_len);
-  DY_REQUIRE(G >= 0 && arena_bytes >= 0, "trace_gather: bad args (G = %d, arena_bytes = %lld)", G, (long long)arena_bytes);
+  ME_ARGS("trace_gather");
   TR_ARENA("trace_gather");
-  if (G == 0) return DISYOLO_OK;
-  int64_t blocks = 0;
-  {
-    const int rc = measure_tables("trace_gather", groups_host, G, arena_bytes, &blocks, nullptr);
-    if (rc != DISYOLO_OK) return rc;
-  }
+  ME_PLAN("trace_gather", nullptr);
   // (groups without a pixel still get their zero trunk row)
   return trace_gather_run(G, ents, count, (int)capacity, rank, rank_diag, d2, arena_bytes, offsets, (int)n_rows, profile, seg, edges, attach,
                           (int)n_attach, tprofile, (int)tprofile_len, tstart, trunkrows, stream);

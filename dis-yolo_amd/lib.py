@@ -1246,14 +1246,16 @@ def tile_group_counts(groups, arena, gt, gt_bits, pairs, image_hw, groups_dev=No
     return counts
 
 
-def _measure_tables(groups, arena, groups_dev, arena_bytes, what: str):
-    """the groups table (host copy checked by the library before any launch, device copy uploaded when not given), the arena
-    and the bytes of it in use, as every measure_* call takes them"""
-    _need(arena, torch.uint8, "arena")
-    groups, groups_dev = _table(np.asarray(groups, np.int32).reshape(-1, 8), 8, "groups", groups_dev, arena.device)
-    nbytes = int(arena.numel()) if arena_bytes is None else int(arena_bytes)
-    if not 0 <= nbytes <= int(arena.numel()):
-        raise DisyoloError("%s: arena_bytes = %d, the arena holds %d" % (what, nbytes, int(arena.numel())))
+def _arena_tables(groups, buf, groups_dev, arena_bytes, what: str, holder: str = "arena"):
+    """the groups table (host copy checked by the library before any launch, device copy uploaded when not given) and the
+    elements in use of ``buf``, as every call over the arena takes them.  ``holder`` names buf in the message: "arena", the
+    uint8 masks themselves, or "buffer", any per-pixel buffer in the arena's layout"""
+    if holder == "arena":
+        _need(buf, torch.uint8, "arena")
+    groups, groups_dev = _table(np.asarray(groups, np.int32).reshape(-1, 8), 8, "groups", groups_dev, buf.device)
+    nbytes = int(buf.numel()) if arena_bytes is None else int(arena_bytes)
+    if not 0 <= nbytes <= int(buf.numel()):
+        raise DisyoloError("%s: arena_bytes = %d, the %s holds %d" % (what, nbytes, holder, int(buf.numel())))
     return groups, groups_dev, nbytes
 
 
@@ -1277,7 +1279,7 @@ def measure_d2(groups, arena, colg, d2, groups_dev=None, arena_bytes: Optional[i
     """groups [G,8] (tile_compose_plan; host int32, checked before the launch, its device copy may be passed in); arena uint8
     CUDA (what tile_compose wrote; ``arena_bytes`` of it, all by default); colg int16 CUDA scratch and d2 int32 CUDA out, each
     of at least arena_bytes elements in the arena's layout (disyolo_measure_d2).  Elements between crops are left untouched."""
-    groups, groups_dev, nbytes = _measure_tables(groups, arena, groups_dev, arena_bytes, "measure_d2")
+    groups, groups_dev, nbytes = _arena_tables(groups, arena, groups_dev, arena_bytes, "measure_d2")
     _need_elems(colg, torch.int16, nbytes, "colg")
     _need_elems(d2, torch.int32, nbytes, "d2")
     _check(load().disyolo_measure_d2(groups.ctypes.data, _p(groups_dev), int(groups.shape[0]), _p(arena), nbytes, _p(colg), _p(d2),
@@ -1289,7 +1291,7 @@ def measure_thin(groups, arena, skel, tmp, flags, iters, it0: int, chunk: int, g
     """``chunk`` iterations of Zhang-Suen thinning, numbered from ``it0``, for all groups (disyolo_measure_thin): skel, tmp
     uint8 CUDA of at least arena_bytes elements, flags int32 CUDA [chunk+1,G] (a non-zero word of the last row: that group
     still changed), iters int32 CUDA [G].  No synchronisation here: the caller reads the last flags row."""
-    groups, groups_dev, nbytes = _measure_tables(groups, arena, groups_dev, arena_bytes, "measure_thin")
+    groups, groups_dev, nbytes = _arena_tables(groups, arena, groups_dev, arena_bytes, "measure_thin")
     G = int(groups.shape[0])
     _need_elems(skel, torch.uint8, nbytes, "skel")
     _need_elems(tmp, torch.uint8, nbytes, "tmp")
@@ -1304,7 +1306,7 @@ def measure_thin(groups, arena, skel, tmp, flags, iters, it0: int, chunk: int, g
 def measure_counts(groups, arena, skel, d2, groups_dev=None, arena_bytes: Optional[int] = None):
     """-> (counts int64 CUDA [G,8] = area, skel_px, n_orth, n_diag, n_end, max_d2, max_d2_skel, 0; sum_sqrt f64 CUDA [G]) of the
     masks in arena, their skeletons in skel and their squared distances in d2 (disyolo_measure_counts)"""
-    groups, groups_dev, nbytes = _measure_tables(groups, arena, groups_dev, arena_bytes, "measure_counts")
+    groups, groups_dev, nbytes = _arena_tables(groups, arena, groups_dev, arena_bytes, "measure_counts")
     G = int(groups.shape[0])
     _need_elems(skel, torch.uint8, nbytes, "skel")
     _need_elems(d2, torch.int32, nbytes, "d2")
@@ -1315,15 +1317,6 @@ def measure_counts(groups, arena, skel, d2, groups_dev=None, arena_bytes: Option
     _check(load().disyolo_measure_counts(groups.ctypes.data, _p(groups_dev), G, _p(arena), nbytes, _p(skel), _p(d2), _p(counts),
                                          _p(partials), int(partials.numel()), _p(sum_sqrt), _stream()), "measure_counts")
     return counts, sum_sqrt
-
-
-def _skeleton_tables(groups, like, groups_dev, arena_bytes, what: str):
-    """the groups table and the elements in use of the per-pixel buffers, as every skeleton_* call takes them"""
-    groups, groups_dev = _table(np.asarray(groups, np.int32).reshape(-1, 8), 8, "groups", groups_dev, like.device)
-    nbytes = int(like.numel()) if arena_bytes is None else int(arena_bytes)
-    if not 0 <= nbytes <= int(like.numel()):
-        raise DisyoloError("%s: arena_bytes = %d, the buffer holds %d" % (what, nbytes, int(like.numel())))
-    return groups, groups_dev, nbytes
 
 
 SKELETON_ROW = 12      # int64 words of a branch row (disyolo_skeleton_rows)
@@ -1338,7 +1331,7 @@ def _need_rows(rows: torch.Tensor) -> None:
 def skeleton_classify(groups, src, skel, links, groups_dev=None, arena_bytes: Optional[int] = None) -> None:
     """src uint8 CUDA (a non-zero byte is a skeleton pixel) -> links uint8 CUDA, the link bits of every pixel; skel uint8 CUDA
     gets the 0 / 1 state of src unless it IS src (disyolo_skeleton_classify).  All in the arena's layout."""
-    groups, groups_dev, nbytes = _skeleton_tables(groups, src, groups_dev, arena_bytes, "skeleton_classify")
+    groups, groups_dev, nbytes = _arena_tables(groups, src, groups_dev, arena_bytes, "skeleton_classify", "buffer")
     _need(src, torch.uint8, "src")
     _need_elems(skel, torch.uint8, nbytes, "skel")
     _need_elems(links, torch.uint8, nbytes, "links")
@@ -1349,7 +1342,7 @@ def skeleton_classify(groups, src, skel, links, groups_dev=None, arena_bytes: Op
 def skeleton_label(groups, skel, links, labels, groups_dev=None, arena_bytes: Optional[int] = None) -> None:
     """labels int32 CUDA: the branch label (its smallest pixel index) on pixels of degree <= 2, -1 on the crop's other pixels
     (disyolo_skeleton_label: init, merge, flatten)"""
-    groups, groups_dev, nbytes = _skeleton_tables(groups, skel, groups_dev, arena_bytes, "skeleton_label")
+    groups, groups_dev, nbytes = _arena_tables(groups, skel, groups_dev, arena_bytes, "skeleton_label", "buffer")
     _need(skel, torch.uint8, "skel")
     _need_elems(links, torch.uint8, nbytes, "links")
     _need_elems(labels, torch.int32, nbytes, "labels")
@@ -1362,7 +1355,7 @@ def skeleton_rows(groups, links, labels, d2, rowid, rows, M2: int, ctrl, junctio
     """the branch rows int64 CUDA [capacity, SKELETON_ROW] in any order, ctrl int32 CUDA [1 + G] (the branch count, which may
     exceed the capacity, and one spur flag per group) and junctions int64 CUDA [G,4] (disyolo_skeleton_rows); rowid int32 CUDA
     per pixel is scratch.  No synchronisation here: the caller reads ctrl."""
-    groups, groups_dev, nbytes = _skeleton_tables(groups, links, groups_dev, arena_bytes, "skeleton_rows")
+    groups, groups_dev, nbytes = _arena_tables(groups, links, groups_dev, arena_bytes, "skeleton_rows", "buffer")
     G = int(groups.shape[0])
     _need(links, torch.uint8, "links")
     _need_elems(labels, torch.int32, nbytes, "labels")
@@ -1379,7 +1372,7 @@ def skeleton_rows(groups, links, labels, d2, rowid, rows, M2: int, ctrl, junctio
 
 def skeleton_prune(groups, labels, rowid, rows, skel, groups_dev=None, arena_bytes: Optional[int] = None) -> None:
     """zeroes the bytes of skel whose branch is a spur by its row (disyolo_skeleton_prune)"""
-    groups, groups_dev, nbytes = _skeleton_tables(groups, skel, groups_dev, arena_bytes, "skeleton_prune")
+    groups, groups_dev, nbytes = _arena_tables(groups, skel, groups_dev, arena_bytes, "skeleton_prune", "buffer")
     _need(skel, torch.uint8, "skel")
     _need_elems(labels, torch.int32, nbytes, "labels")
     _need_elems(rowid, torch.int32, nbytes, "rowid")
@@ -1403,7 +1396,7 @@ def trace_nodes(groups, links, d2, node_labels, noderow, nodes, ctrl, groups_dev
     """node_labels int32 CUDA: the node (its smallest pixel index) on pixels of degree >= 3, -1 on the crop's other pixels; nodes
     int64 CUDA [capacity, TRACE_NODE] in any order and ctrl int32 CUDA [1], their number (disyolo_trace_nodes); noderow int32
     CUDA per pixel is scratch.  No synchronisation here."""
-    groups, groups_dev, nbytes = _skeleton_tables(groups, links, groups_dev, arena_bytes, "trace_nodes")
+    groups, groups_dev, nbytes = _arena_tables(groups, links, groups_dev, arena_bytes, "trace_nodes", "buffer")
     _need(links, torch.uint8, "links")
     _need_elems(d2, torch.int32, nbytes, "d2")
     _need_elems(node_labels, torch.int32, nbytes, "node_labels")
@@ -1421,7 +1414,7 @@ def trace_rank(groups, links, labels, d2, rowid, rows, ents, rounds: int, nxt, v
     int32 CUDA [1], its length (disyolo_trace_rank).  nxt int32 and val int64 CUDA [4 capacity] are the two state buffers of the
     ``rounds`` pointer-jumping rounds (2^rounds >= the longest branch's pixels - 1).  labels, rowid, rows: as skeleton_rows left
     them.  No synchronisation here."""
-    groups, groups_dev, nbytes = _skeleton_tables(groups, links, groups_dev, arena_bytes, "trace_rank")
+    groups, groups_dev, nbytes = _arena_tables(groups, links, groups_dev, arena_bytes, "trace_rank", "buffer")
     _need(links, torch.uint8, "links")
     for t, name in ((labels, "labels"), (d2, "d2"), (rowid, "rowid"), (rank, "rank"), (rank_diag, "rank_diag")):
         _need_elems(t, torch.int32, nbytes, name)
@@ -1439,7 +1432,7 @@ def trace_rank(groups, links, labels, d2, rowid, rows, ents, rounds: int, nxt, v
 def trace_edges(groups, ents, count, rank, rank_diag, node_labels, edges, groups_dev=None, arena_bytes: Optional[int] = None) -> None:
     """edges int64 CUDA [rows, TRACE_EDGE]: what the two ends of every branch are, row r for the branch of row r of skeleton_rows
     (disyolo_trace_edges)"""
-    groups, groups_dev, nbytes = _skeleton_tables(groups, rank, groups_dev, arena_bytes, "trace_edges")
+    groups, groups_dev, nbytes = _arena_tables(groups, rank, groups_dev, arena_bytes, "trace_edges", "buffer")
     _need_table(ents, torch.int32, TRACE_ENT, "ents")
     _need_elems(count, torch.int32, 1, "count")
     _need(rank, torch.int32, "rank")
@@ -1457,7 +1450,7 @@ def trace_gather(groups, ents, count, rank, rank_diag, d2, offsets, profile, seg
     [rows]); tprofile int32 CUDA [n, TRACE_TRUNK_PROFILE]: the trunk profiles by the plan seg int32 CUDA [rows, TRACE_SEG] and
     attach int32 CUDA [m, TRACE_ATTACH]; trunkrows int64 CUDA [G, TRACE_TRUNK] over the entries tstart int32 CUDA [G + 1] bounds
     (disyolo_trace_gather).  No synchronisation here."""
-    groups, groups_dev, nbytes = _skeleton_tables(groups, rank, groups_dev, arena_bytes, "trace_gather")
+    groups, groups_dev, nbytes = _arena_tables(groups, rank, groups_dev, arena_bytes, "trace_gather", "buffer")
     G = int(groups.shape[0])
     _need_table(ents, torch.int32, TRACE_ENT, "ents")
     _need_elems(count, torch.int32, 1, "count")
@@ -1489,7 +1482,7 @@ SHAPE_COLS = 16        # int64 words of a row of disyolo_shape_sums
 def shape_sums(groups, arena, sums, groups_dev=None, arena_bytes: Optional[int] = None) -> None:
     """sums int64 CUDA [G, SHAPE_COLS] = n, Sy, Sx, Syy, Sxx, Sxy, ymin, ymax, xmin, xmax, Q1, Q2, Q3, Q4, QD, 0 of the masks in
     arena, initialised by the call (disyolo_shape_sums).  No synchronisation here."""
-    groups, groups_dev, nbytes = _measure_tables(groups, arena, groups_dev, arena_bytes, "shape_sums")
+    groups, groups_dev, nbytes = _arena_tables(groups, arena, groups_dev, arena_bytes, "shape_sums")
     G = int(groups.shape[0])
     _need(sums, torch.int64, "sums")
     _need_shape(sums, (G, SHAPE_COLS), "sums")
@@ -1500,7 +1493,7 @@ def shape_parts(groups, arena, labels, px, parts, groups_dev=None, arena_bytes: 
     """labels int32 CUDA: the part (the smallest pixel index of its 8-connected component) on foreground pixels, -1 on the
     crop's other pixels; parts int64 CUDA [G, 2] = n_parts, largest_part_px; px int32 CUDA per pixel is scratch
     (disyolo_shape_parts).  No synchronisation here."""
-    groups, groups_dev, nbytes = _measure_tables(groups, arena, groups_dev, arena_bytes, "shape_parts")
+    groups, groups_dev, nbytes = _arena_tables(groups, arena, groups_dev, arena_bytes, "shape_parts")
     G = int(groups.shape[0])
     _need_elems(labels, torch.int32, nbytes, "labels")
     _need_elems(px, torch.int32, nbytes, "px")
@@ -1514,7 +1507,7 @@ def shape_extents(groups, arena, dirs, pminmax, groups_dev=None, dirs_dev=None, 
     """pminmax int32 CUDA [G, K, 2]: the minimum and maximum of c_k x + s_k y over every mask for the directions dirs int32
     [K, 2] (host, checked before the launch; its device copy may be passed in) (disyolo_shape_extents).  No synchronisation
     here."""
-    groups, groups_dev, nbytes = _measure_tables(groups, arena, groups_dev, arena_bytes, "shape_extents")
+    groups, groups_dev, nbytes = _arena_tables(groups, arena, groups_dev, arena_bytes, "shape_extents")
     G = int(groups.shape[0])
     dirs, dirs_dev = _table(np.asarray(dirs, np.int32).reshape(-1, 2), 2, "dirs", dirs_dev, arena.device)
     K = int(dirs.shape[0])
@@ -1548,7 +1541,7 @@ def outline_edges(groups, arena, first, sides, ekey, nxt, flag, aterm, work, ctr
     """The boundary edges of every mask, listed: first int32 and sides uint8 CUDA in the arena's layout, ekey, nxt, aterm int32 and
     flag uint8 CUDA per list entry (the capacity is ekey's length), work int64 CUDA of OUTLINE_WORK words per entry, ctrl int32
     CUDA [4], zeroed by the call (disyolo_outline_edges).  No synchronisation here."""
-    groups, groups_dev, nbytes = _measure_tables(groups, arena, groups_dev, arena_bytes, "outline_edges")
+    groups, groups_dev, nbytes = _arena_tables(groups, arena, groups_dev, arena_bytes, "outline_edges")
     _need_elems(first, torch.int32, nbytes, "first")
     _need_elems(sides, torch.uint8, nbytes, "sides")
     cap = _outline_list(ekey, nxt, flag, aterm, work)
@@ -1563,7 +1556,7 @@ def outline_loops(groups, arena, part_labels, first, sides, ekey, nxt, flag, ate
     """After ``outline_edges`` on the same buffers: rows int64 CUDA [L, OUTLINE_ROW], one per loop in the order of arrival, and
     eidx int32 CUDA [capacity, 3]; part_labels = the labels of ``shape_parts``; 2^rounds must reach the longest loop's edges
     (disyolo_outline_loops).  No synchronisation here."""
-    groups, groups_dev, nbytes = _measure_tables(groups, arena, groups_dev, arena_bytes, "outline_loops")
+    groups, groups_dev, nbytes = _arena_tables(groups, arena, groups_dev, arena_bytes, "outline_loops")
     _need_elems(part_labels, torch.int32, nbytes, "part_labels")
     _need_elems(first, torch.int32, nbytes, "first")
     _need_elems(sides, torch.uint8, nbytes, "sides")
@@ -1580,7 +1573,7 @@ def outline_gather(groups, arena, ekey, flag, eidx, ctrl, plan, points, corners,
     """After ``outline_loops``: plan int32 CUDA [L, OUTLINE_PLAN] per row of its rows; points int32 CUDA [N, 2] and corners int32
     CUDA [C, 2] take the chains and rings in image (x, y) (disyolo_outline_gather).  The arena is not read.  No synchronisation
     here."""
-    groups, groups_dev, nbytes = _measure_tables(groups, arena, groups_dev, arena_bytes, "outline_gather")
+    groups, groups_dev, nbytes = _arena_tables(groups, arena, groups_dev, arena_bytes, "outline_gather")
     cap = _outline_list(ekey, None, flag, None, None)
     _need_elems(eidx, torch.int32, 3 * cap, "eidx")
     _need_elems(ctrl, torch.int32, 4, "ctrl")
